@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the hot path: Mray/s (+ ms/frame) of the ReSTIR DI frame.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints the
+line. Everything else the line can carry is measured only with --full (see below).
 
 Both forms work for N > 1. Called plainly (no RANK / WORLD_SIZE in the environment) with --gpus N > 1, this process starts
 N FRESH child processes of itself — one per GPU, rendezvous on 127.0.0.1 — BEFORE it makes any GPU call, relays rank 0's
@@ -21,11 +24,16 @@ by the NATIVE strip driver of librestir_rt.so (csrc/strip_mg.cpp): sparse 87-row
 exchanged with RCCL send/recv over xGMI before each spatial pass, no host wait in a steady frame.
 torch.distributed only distributes the RCCL unique id and reduces the timings.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), config, build_id.
+--full adds, each from frames or contexts of its own outside the timed region: value_pipelined, kernel_ms and
+gpu_event_median_ms (HIP events), pcie_inclusive, bvh_walks_per_frame, verified_vs_kernel_sequence, also_3840x2160, and
   roofline     — spatial_resampling: SURVEY §8(d) algorithmic bytes per launch / HIP-event time (`frac`, the
                  contract figure) next to the counter-measured HBM traffic of the same binary
                  (`hbm_frac_measured`; null when profiles/ holds no PMC pass of this library build)
   cpu_baseline — the oracle (CPU restatement) timed on this host's cores, N=1 only.
+N > 1 with --full: strip_driver statistics, verified_vs_single_context and single_gpu_on_this_node.
+
+--dump-outputs DIR: what the timed path computed in its last step, as float32 .npy files (dump_outputs below).
 """
 import argparse
 import hashlib
@@ -113,6 +121,45 @@ def committed_pmc(sha, build_id):
         out["traffic"] = d.get("hbm_bytes_per_launch")
         out["valu"] = d.get("valu_issue_frac")
     return out
+
+
+# --dump-outputs: at most this many pixels of each array; larger images are written as the same seeded sample of pixels in every run
+# of the same size (1920x1080: the accumulation buffer whole, 33 MB, and 1 Mi pixels of the RGBA8 image, 17 MB; 64 MB at most in all)
+DUMP_ACC_PIXELS = 2_500_000
+DUMP_RGBA8_PIXELS = 1 << 20
+DUMP_SEED = 2024
+
+
+def dump_outputs(dirname, r, rows, width, height, rank, world, dist):
+    """What rt_frame hands its caller after the last timed step: the float accumulation buffer (`accumulation.npy`, HDR RGBA) and
+    the tone-mapped RGBA8 image (`pixels.npy`, as float32), pixel rows in row-major order. N > 1: every rank downloads its own rows
+    and rank 0 assembles the frame."""
+    import numpy as np
+
+    from cedec_2024_rt_amd import api
+
+    a, b = rows
+    own = slice(a - r.local_row0, b - r.local_row0)
+    acc = r.download(api.RT_BUF_ACCUMULATION).reshape(r.local_rows, width, 4)[own]
+    pix = r.download(api.RT_BUF_PIXELS).reshape(r.local_rows, width, 4)[own]
+    if world > 1:
+        parts = [None] * world
+        dist.gather_object((np.ascontiguousarray(acc), np.ascontiguousarray(pix)), parts if rank == 0 else None, dst=0)
+        if rank != 0:
+            return
+        acc = np.concatenate([p[0] for p in parts], axis=0)
+        pix = np.concatenate([p[1] for p in parts], axis=0)
+    assert acc.shape == (height, width, 4) and pix.shape == (height, width, 4), (acc.shape, pix.shape)
+
+    def sample(img, limit):
+        if height * width <= limit:
+            return img
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(height * width, limit, replace=False))
+        return img.reshape(-1, 4)[idx]
+
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "accumulation.npy"), sample(acc, DUMP_ACC_PIXELS).astype(np.float32))
+    np.save(os.path.join(dirname, "pixels.npy"), sample(pix, DUMP_RGBA8_PIXELS).astype(np.float32))
 
 
 class Watchdog:
@@ -298,6 +345,11 @@ def _main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--width", type=int, default=W)
     ap.add_argument("--height", type=int, default=H)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: pipelined frames, per-kernel events, PCIe-inclusive frames, "
+                         "BVH walks, verification, the 3840x2160 line, the roofline and the CPU baseline")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         launch_ranks(args, sys.argv[1:])  # does not return
@@ -561,11 +613,14 @@ def _main():
     # N > 1: the native strip driver's frame loop (always pipelined: its look-ahead is what hides the halo exchanges).
     R = run(width, height, K, Wm, pipelined=(world > 1))
     r, mg, frame, total_rays, elapsed = R["r"], R["mg"], R["frame"], R["rays"], R["dt"]
+    if args.dump_outputs:
+        wd.tick("writing the outputs of the last timed frame", 600)
+        dump_outputs(args.dump_outputs, r, R["bounds"][rank], width, height, rank, world, dist)
     info = r.scene_info()
     pipelined_dt = None
     # profiling runs (tools/profile_round.sh: RT_TUNING=14=0,17=0) keep every kernel of the process un-overlapped: no pipelined region
     no_pipelined = bool(os.environ.get("BENCH_NO_PIPELINED")) or any(kv.split("=")[0] in ("14", "17") for kv in filter(None, os.environ.get("RT_TUNING", "").split(",")))
-    if world == 1 and not no_pipelined:
+    if args.full and world == 1 and not no_pipelined:
         r.tuning(14, -1)
         r.tuning(17, -1)
         frame, _, pipelined_dt = timed(r, None, r.frame, frame, width, height, K, Wm)
@@ -575,7 +630,7 @@ def _main():
     single_ref = None
     spatial_ms = per_kernel = algo_bytes = pcie_ms = event_median = two_launch = None
     verified = mg_stats = walks = verified_seq = None
-    if world == 1:
+    if args.full and world == 1:
         # algorithmic bytes of the three spatial launches of one timed frame (RNG replay, untimed): pass k of
         # frame f reads the buffer the previous pass wrote; the count only depends on the shaded bits
         fmid = Wm + 1 + K // 2
@@ -669,7 +724,7 @@ def _main():
                                                        np.ascontiguousarray(hist_seq[f_][shaded_mask]).view(np.uint8))
                                         for f_ in hist_seq.dtype.names if f_ != "pad"))
             seq.close()
-    else:
+    elif args.full:
         st = mg.stats()
         mine = dict(rank=rank, rows=list(R["bounds"][rank]), host_us_per_frame=round(st["host_ns"] / K / 1e3, 1),
                     plan_wait_us_per_frame=round(st["plan_wait_ns"] / K / 1e3, 1), cold_frames=st["cold_frames"],
@@ -737,7 +792,7 @@ def _main():
     # config #5 on the same N GPUs (4x the pixels: a strip is then large enough to amortise the per-kernel
     # latency floor that bounds strong scaling of the 2.3 ms 1080p frame).
     also_4k = None
-    if (width, height) == (W, H) and not os.environ.get("BENCH_NO_4K"):
+    if args.full and (width, height) == (W, H) and not os.environ.get("BENCH_NO_4K"):
         R4 = run(3840, 2160, 10, 3, pipelined=(world > 1))
         also_4k = {"workload": "same scene and options at 3840x2160 (the frame of BASELINE config #5)", "steps": 10, "warmup": 3,
                    "frames": "pipelined (native strip driver)" if world > 1 else "back to back on one stream, as the headline",
@@ -798,13 +853,19 @@ def _main():
                     "note": "a whole-frame context on rank 0's GPU, timed in this run while the other ranks waited: the N = 1 line's `value` "
                             "is the un-pipelined frame, this line's `value` is pipelined throughput — compare like with like"}
             out["config"]["strips"] = [list(b) for b in R["bounds"]]
-            out["strip_driver"] = mg_stats
+            if mg_stats is not None:
+                out["strip_driver"] = mg_stats
             if verified is not None:
                 out["verified_vs_single_context"] = verified
         if also_4k is not None:
             out["also_3840x2160"] = also_4k
         if world == 1:
             sha = lib_sha256()
+            out["lib_sha256"] = sha
+            out["build_id"] = lib_build_id
+            out["value_definition"] = ("un-pipelined frames of SURVEY 8(d): K frames back to back on one stream, wall clock; since round 5. Rounds 1-4 "
+                                       "reported the pipelined throughput here: compare across rounds through `value_pipelined` (--full)")
+        if world == 1 and args.full:
             pmc = committed_pmc(sha, lib_build_id)
             contract_ach = algo_bytes / (spatial_ms * 1e-3) / 1e9
             traffic = pmc["traffic"]
@@ -833,13 +894,9 @@ def _main():
                                               "source": "profiles/r06_gather_ceiling.jsonl (tools/gather_ceiling.hip, one MI355X box of this pool)"},
                 "valu_issue_frac_weighted": pmc["valu"],
             }
-            out["lib_sha256"] = sha
-            out["build_id"] = lib_build_id
             out["kernel_ms"] = per_kernel
             if two_launch is not None:
                 out["kernel_ms_two_launch_stage0"] = two_launch
-            out["value_definition"] = ("un-pipelined frames of SURVEY 8(d): K frames back to back on one stream, wall clock; since round 5. Rounds 1-4 "
-                                       "reported the pipelined throughput here: compare across rounds through `value_pipelined`")
             out["gpu_event_median_ms"] = event_median
             # SURVEY 8(d)'s frame time = GPU-event median of >= 50 un-overlapped frames
             out["value_gpu_event_median"] = {"value": total_rays / event_median / 1e3, "unit": "Mray/s", "ms_per_frame": event_median,

@@ -63,9 +63,47 @@ def test_world_size_mismatch_is_one_null_line():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_frame(tmp_path):
+    """a plain run: the headline fields, exactly --steps timed steps, none of what --full measures; --dump-outputs writes the
+    last timed frame, bit for bit what a context that renders frames 1..warmup+steps hands its caller"""
+    import numpy as np
+
+    from cedec_2024_rt_amd import api, scenes
+    from cedec_2024_rt_amd.types import bench_options
+
+    w, h, steps, warm = 480, 270, 3, 2
+    rc, lines, err = _run_bench({}, "--gpus", "1", "--steps", str(steps), "--warmup", str(warm), "--width", str(w), "--height", str(h),
+                                "--dump-outputs", str(tmp_path / "out"), timeout=300)
+    assert rc == 0, err[-3000:]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "Mray/s" and d["unit"] == "Mray/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == steps and d["warmup"] == warm and d["value"] > 0 and d["ms_per_step"] > 0
+    assert not {"kernel_ms", "value_pipelined", "verified_vs_kernel_sequence", "cpu_baseline", "roofline", "also_3840x2160"} & set(d)
+    acc = np.load(tmp_path / "out" / "accumulation.npy")
+    pix = np.load(tmp_path / "out" / "pixels.npy")
+    assert acc.dtype == np.float32 and pix.dtype == np.float32 and acc.shape == pix.shape == (h, w, 4)
+
+    tris = scenes.make_blocks_restir()
+    r = api.Renderer(w, h, device=0)
+    r.set_scene(tris)
+    r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
+    r.set_options(bench_options())
+    for f in range(1, warm + steps + 1):
+        r.frame(f)
+    r.sync()
+    ref_acc = r.download(api.RT_BUF_ACCUMULATION).reshape(h, w, 4)
+    ref_pix = r.download(api.RT_BUF_PIXELS).reshape(h, w, 4)
+    r.close()
+    assert np.array_equal(acc.view(np.uint32), ref_acc.view(np.uint32))
+    assert np.array_equal(pix, ref_pix.astype(np.float32))
+
+
+@pytest.mark.gpu
 def test_plain_launch_two_ranks_shm_is_verified():
-    """the documented command, two ranks on ONE GPU with the exact SHM transport: one line, two-strip frame == single context"""
-    rc, lines, err = _run_bench({"BENCH_DEV_SHM": "1", "BENCH_NO_4K": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1")
+    """the documented command, two ranks on ONE GPU with the exact SHM transport: one line, two-strip frame == single context
+    (--full: the verification and the single-GPU frames are measured only there)"""
+    rc, lines, err = _run_bench({"BENCH_DEV_SHM": "1", "BENCH_NO_4K": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full")
     assert rc == 0, err[-3000:]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
@@ -84,7 +122,7 @@ def test_plain_launch_eight_ranks_shm_is_verified():
     gather of the verification — end to end on this box's one GPU over the exact SHM transport, at a reduced size (640 x 720:
     eight 90-row strips, the thinnest the 87-row halo allows). The assembled eight-strip frame == a single context's, bit for bit."""
     rc, lines, err = _run_bench({"BENCH_DEV_SHM": "1", "BENCH_NO_4K": "1", "BENCH_LAUNCH_TIMEOUT_S": "800"},
-                                "--gpus", "8", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "720", timeout=900)
+                                "--gpus", "8", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "720", "--full", timeout=900)
     assert rc == 0, err[-3000:]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
@@ -113,7 +151,7 @@ def test_plain_launch_two_gpus_real_rccl():
     over real RCCL send/recv; the assembled frame must equal a single context's (BENCH_VERIFY defaults to on there)"""
     if _gpu_count() < 2:
         pytest.skip("one GPU on this box: RCCL refuses two ranks on one device")
-    rc, lines, err = _run_bench({"BENCH_NO_4K": "1"}, "--gpus", "2", "--steps", "5", "--warmup", "2")
+    rc, lines, err = _run_bench({"BENCH_NO_4K": "1"}, "--gpus", "2", "--steps", "5", "--warmup", "2", "--full")
     assert rc == 0, err[-3000:]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])

@@ -1,5 +1,5 @@
 """Mean of every collected counter per frame kernel (1920x1080 launches) from one rocprofv3 --pmc result directory:
-  rocprofv3 --pmc C1 C2 ... -d DIR -o pmc -- python3 bench.py --no-cpu-baseline --steps 12 --warmup 2
+  rocprofv3 --pmc C1 C2 ... -d DIR -o pmc -- python3 bench.py --full --no-cpu-baseline --steps 12 --warmup 2
   python tools/pmc_probe.py DIR"""
 import collections, glob, json, os, sqlite3, sys
 
