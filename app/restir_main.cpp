@@ -8,7 +8,7 @@
  *   restir_app [--obj scene.obj | --tris scene.tris] [--size W H] [--frames N]
  *              [--eye x y z] [--lookat x y z] [--temporal 0|1] [--spatial 0|1]
  *              [--shadowed 0|1] [--visreuse 0|1] [--accumulate 0|1] [--by-kernel]
- *              [--example 10|7|8|9|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
+ *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
@@ -16,6 +16,10 @@
  * host libm), on --threads host threads (default: all). No GPU call is made: it runs on a machine without one.
  * Defaults then follow 04_ao.cpp (256x256 is the BASELINE size; camera (8,8,8) -> (0,0,0), common/misc.hpp:217-218);
  * --rgba writes the W*H RGBA8 bytes in the reference's storage order (what its pixel buffer holds).
+ * --example 6: the same ambient occlusion ON THE GPU through rt_path_trace (examples/06_ao_hiprt/06_ao_hiprt.cu:35-91, the
+ * same image as 04_ao's kernel). Defaults follow 06_ao_hiprt.cpp:79-80: 1920x1080, camera (8,8,8) -> (0,0,0), fovy pi/4.
+ * --frames K times K launches after one warm-up (host clock around rt_sync) and prints ms per launch and Mray/s in the
+ * reference's rays (W*H primary rays + 64 per hit pixel); --rgba / --ppm / --png as for --example 4.
  *
  * --ranks N: the multi-GPU frame loop: N processes, forked before anything touches a GPU,
  * rank r on device r, each rendering one row strip through the native strip driver (rt_mg_*: sparse
@@ -113,6 +117,35 @@ static void write_png(const char* path, int W, int H, const uint8_t* rgb /* W*H*
     chunk("IDAT", z);
     chunk("IEND", {});
     fclose(f);
+}
+
+/* the ambient-occlusion image (W*H RGBA8 in the reference's storage order, bottom row first) as --rgba / --ppm / --png ask */
+static int write_ao_image(const std::vector<uint8_t>& px, int W, int H, const std::string& rgba, const std::string& ppm, const std::string& png)
+{
+    if (!rgba.empty())
+    {
+        FILE* f = fopen(rgba.c_str(), "wb");
+        if (!f) { fprintf(stderr, "cannot write %s\n", rgba.c_str()); return 1; }
+        fwrite(px.data(), 1, px.size(), f);
+        fclose(f);
+    }
+    if (!ppm.empty())
+    {
+        FILE* f = fopen(ppm.c_str(), "wb");
+        if (!f) { fprintf(stderr, "cannot write %s\n", ppm.c_str()); return 1; }
+        fprintf(f, "P6\n%d %d\n255\n", W, H);
+        for (int y = H - 1; y >= 0; --y)
+            for (int x = 0; x < W; ++x) fwrite(&px[4 * ((size_t)y * W + x)], 1, 3, f);
+        fclose(f);
+    }
+    if (!png.empty())
+    {
+        std::vector<uint8_t> rgb((size_t)W * H * 3);
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) memcpy(&rgb[3 * ((size_t)y * W + x)], &px[4 * ((size_t)(H - 1 - y) * W + x)], 3);
+        write_png(png.c_str(), W, H, rgb.data());
+    }
+    return 0;
 }
 
 static void die(rt_ctx* c, const char* what, int rc)
@@ -407,32 +440,35 @@ int main(int argc, char** argv)
         for (size_t i = 0; i < (size_t)W * H; ++i) hit += px[4 * i] != 32 || px[4 * i + 1] != 32;
         printf("triangles: %zu\n04_ao %dx%d: %.1f ms on %d host thread(s), %zu of %zu pixels hit\n", triangles.size(), W, H, ms,
                threads > 0 ? threads : (int)(hw ? hw : 1), hit, (size_t)W * H);
-        if (!rgba.empty())
-        {
-            FILE* f = fopen(rgba.c_str(), "wb");
-            if (!f) { fprintf(stderr, "cannot write %s\n", rgba.c_str()); return 1; }
-            fwrite(px.data(), 1, px.size(), f);
-            fclose(f);
-        }
-        if (!ppm.empty())
-        {
-            FILE* f = fopen(ppm.c_str(), "wb");
-            if (!f) { fprintf(stderr, "cannot write %s\n", ppm.c_str()); return 1; }
-            fprintf(f, "P6\n%d %d\n255\n", W, H);
-            for (int y = H - 1; y >= 0; --y)
-                for (int x = 0; x < W; ++x) fwrite(&px[4 * ((size_t)y * W + x)], 1, 3, f);
-            fclose(f);
-        }
-        if (!png.empty())
-        {
-            std::vector<uint8_t> rgb((size_t)W * H * 3);
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x) memcpy(&rgb[3 * ((size_t)y * W + x)], &px[4 * ((size_t)(H - 1 - y) * W + x)], 3);
-            write_png(png.c_str(), W, H, rgb.data());
-        }
-        return 0;
+        return write_ao_image(px, W, H, rgba, ppm, png);
     }
-    if (example != 10 && example != 7 && example != 8 && example != 9) { fprintf(stderr, "--example 10, 7, 8, 9 or 4\n"); return 2; }
+    if (example == 6)
+    {
+        /* BASELINE config #1 on the GPU: 06_ao_hiprt (= 04_ao's kernelMain) through rt_path_trace; defaults of 06_ao_hiprt.cpp:79-80 */
+        if (!cam_set) { eye[0] = eye[1] = eye[2] = 8.0f; lookat[0] = lookat[1] = lookat[2] = 0.0f; }
+        if (ranks > 1) { fprintf(stderr, "--example 6 runs on one GPU\n"); return 2; }
+        if (frames < 1) frames = 1;
+        rt_ctx* ctx = nullptr;
+        int rc = rt_create(0, W, H, 0, H, 0, &ctx);
+        if (rc != RT_OK) die(ctx, "rt_create", rc);
+        CK(rt_scene_set(ctx, triangles.data(), (uint32_t)triangles.size()));
+        CK(rt_camera_lookat(ctx, eye, lookat, up, 3.14159265358979323846f / 4.0f));
+        CK(rt_path_trace(ctx, 6, 0)); /* warm-up */
+        CK(rt_sync(ctx));
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int k = 0; k < frames; ++k) CK(rt_path_trace(ctx, 6, 0));
+        CK(rt_sync(ctx));
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / frames;
+        uint64_t rays = 0;
+        CK(rt_path_trace_rays(ctx, &rays));
+        std::vector<uint8_t> px((size_t)W * H * 4);
+        CK(rt_download(ctx, RT_BUF_PIXELS, px.data(), px.size()));
+        CK(rt_destroy(ctx));
+        printf("triangles: %zu\n06_ao_hiprt %dx%d: %.3f ms per launch (%d launches after one warm-up), %llu rays per launch, %.0f Mray/s\n",
+               triangles.size(), W, H, ms, frames, (unsigned long long)rays, (double)rays / ms / 1e3);
+        return write_ao_image(px, W, H, rgba, ppm, png);
+    }
+    if (example != 10 && example != 7 && example != 8 && example != 9) { fprintf(stderr, "--example 10, 7, 8, 9, 6 or 4\n"); return 2; }
 
     if (ranks > 1)
     {

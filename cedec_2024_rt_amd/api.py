@@ -490,8 +490,20 @@ class Renderer:
         return out.value
 
     def path_trace(self, example, frame):
-        """`path_trace` of examples/07_pt (example=7) or examples/09_ris (example=9)."""
+        """`path_trace` of examples/07_pt (example=7), 08_nee (8) or 09_ris (9); 4 / 6: the ambient occlusion of
+        examples/04_ao / 06_ao_hiprt (see ambient_occlusion)."""
         self._ck(self.L.rt_path_trace(self.h, int(example), int(frame)))
+
+    def ambient_occlusion(self, example=6):
+        """The `kernelMain` of examples/06_ao_hiprt (example=6) or examples/04_ao (4) on the GPU: 64 occlusion rays per hit
+        pixel, written straight into RT_BUF_PIXELS (the accumulation buffer is left alone). Returns the context's own rows
+        as (rows, W, 4) uint8 in storage order (row r = the reference's pixelIdx range [r*W, (r+1)*W))."""
+        if int(example) not in (4, 6):
+            raise ValueError("ambient_occlusion: example must be 4 (04_ao) or 6 (06_ao_hiprt)")
+        self.path_trace(example, 0)
+        px = self.download(RT_BUF_PIXELS).view(np.uint8).reshape(self.local_rows, self.W, 4)
+        r0 = self.rows[0] - self.local_row0
+        return px[r0:r0 + self.rows[1] - self.rows[0]].copy()
 
     def path_trace_rays(self):
         a = C.c_uint64()

@@ -1486,6 +1486,136 @@ RT_DEV uint32_t occluded_batch_plain(const WideView& bvh, uint32_t* __restrict__
     return occluded;
 }
 
+/* n_rays any-hit rays of ONE lane from the origin ro, t in [tmin, tmax], walked back to back with the refill pass of
+ * occluded_batch_plain: a lane starts its next ray as soon as its current one is settled, and next_dir() draws that ray's
+ * direction only then (the ambient-occlusion rays of 04_ao.cu:62-73, generated in the reference's draw order). The refill pass
+ * runs when at least REFILL lanes wait or nobody walks. Returns the number of rays that hit something. Per-ray steps and results are those of trace_wide<true>. */
+template <int STRIDE, int REFILL, class NextDir>
+RT_DEV int occluded_count_refill(const WideView& bvh, uint32_t* __restrict__ lds_stack, const f3 ro, int n_rays, const float tmin,
+                                 const float tmax, NextDir next_dir)
+{
+    if (bvh.n_tris <= 0) return 0;
+    constexpr uint32_t NONE = 0x7fffffffu;
+    const int lane_slot = threadIdx.x;
+    int occluded = 0;
+    uint32_t ovf[WIDE_OVF_STACK];
+    int sp = 0;
+    auto push = [&](uint32_t e) {
+        if (sp < WIDE_LDS_STACK) lds_stack[sp * STRIDE + lane_slot] = e;
+        else ovf[sp - WIDE_LDS_STACK] = e;
+        ++sp;
+    };
+    auto pop = [&]() -> uint32_t {
+        --sp;
+        uint32_t e;
+        if (sp < WIDE_LDS_STACK) e = lds_stack[sp * STRIDE + lane_slot];
+        else e = ovf[sp - WIDE_LDS_STACK];
+        return e;
+    };
+    f3 rd = F3(0.0f, 0.0f, 1.0f), inv = F3(0.0f, 0.0f, 1.0f);
+    bool px = true, py = true, pz = true;
+    uint32_t cur = NONE, pend = NONE, pend2 = NONE;
+    for (;;)
+    {
+        if ((int)cur < 0 && pend2 == NONE)
+        {
+            if (pend == NONE) pend = cur; else pend2 = cur;
+            cur = sp ? pop() : NONE;
+        }
+        const bool has_inner = cur < NONE;
+        const bool has_pend = pend != NONE;
+        const bool live = has_inner || has_pend;
+        const bool want = !live && n_rays > 0;
+        const unsigned long long bl = __ballot(live), bw = __ballot(want);
+        if (bl == 0ull && bw == 0ull) break; /* the whole wavefront is done */
+        if (bw != 0ull && (bl == 0ull || __popcll(bw) >= REFILL))
+        {
+            if (want)
+            {
+                --n_rays;
+                rd = next_dir();
+                inv = F3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+                inv.x = fminf(fmaxf(inv.x, -1e30f), 1e30f);
+                inv.y = fminf(fmaxf(inv.y, -1e30f), 1e30f);
+                inv.z = fminf(fmaxf(inv.z, -1e30f), 1e30f);
+                px = inv.x >= 0.0f; py = inv.y >= 0.0f; pz = inv.z >= 0.0f;
+                cur = 0u; sp = 0;
+            }
+            continue;
+        }
+        if (!live) continue; /* waits for the refill pass */
+        const unsigned long long bi = __ballot(has_inner), bp = __ballot(has_pend);
+        const int parked = __popcll(bp) + __popcll(__ballot(pend2 != NONE));
+        if (bp != 0ull && (bi == 0ull || RT_LEAF_DEN * parked >= RT_LEAF_NUM * __popcll(bl)))
+        {
+            if (has_pend)
+            {
+                const float4* g = bvh.rec + WIDE_STRIDE * (size_t)(pend & ~WIDE_LEAF_BIT);
+                const float4 t0 = g[0], t1 = g[1], t2 = g[2];
+                pend = pend2; pend2 = NONE;
+                const f3 v0 = F3(t0.x, t0.y, t0.z), v1 = F3(t0.w, t1.x, t1.y), v2 = F3(t1.z, t1.w, t2.x);
+                float t, u, v;
+                if (intersect_ray_triangle(t, u, v, ro, rd, tmin, tmax, v0, v1, v2))
+                {
+                    ++occluded; /* any hit settles the ray */
+                    cur = NONE; pend = NONE; sp = 0;
+                }
+            }
+            continue;
+        }
+        if (has_inner)
+        {
+            const float4* g = bvh.rec + WIDE_STRIDE * (size_t)cur;
+            const float4 q0 = g[0], q1f = g[1], q2f = g[2];
+            const uint32_t e = as_uint(q0.w);
+            const uint32_t base = as_uint(q1f.x), meta = as_uint(q1f.y);
+            const uint32_t lx = as_uint(q1f.z), ly = as_uint(q1f.w), lz = as_uint(q2f.x);
+            const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
+            const uint32_t nx = px ? lx : hx, ny = py ? ly : hy, nz = pz ? lz : hz;
+            const uint32_t fx = px ? hx : lx, fy = py ? hy : ly, fz = pz ? hz : lz;
+            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
+                        sz = as_float(((e >> 16) & 0xffu) << 23);
+            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
+            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            bool h[4];
+            uint32_t ce[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+            {
+                const uint32_t m = (meta >> (8 * k)) & 0xffu;
+                float tn = fmaxf(fmaxf(__builtin_fmaf(wide_byte(nx, k), Bx, Ax), __builtin_fmaf(wide_byte(ny, k), By, Ay)),
+                                 __builtin_fmaf(wide_byte(nz, k), Bz, Az));
+                float tf = fminf(fminf(__builtin_fmaf(wide_byte(fx, k), Bx, Ax), __builtin_fmaf(wide_byte(fy, k), By, Ay)),
+                                 __builtin_fmaf(wide_byte(fz, k), Bz, Az));
+                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
+                tn = fmaxf(tn, tmin);
+                tf = fminf(tf, tmax) * WIDE_SLAB_PAD;
+                h[k] = (m != 0u) && (tn <= tf);
+                ce[k] = (base + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
+            }
+            if (h[0] || h[1] || h[2] || h[3])
+            {
+                const bool deep = __ballot(sp + 3 > WIDE_LDS_STACK) != 0ull;
+                cur = h[0] ? ce[0] : (h[1] ? ce[1] : (h[2] ? ce[2] : ce[3]));
+                if (__builtin_expect(deep, 0))
+                {
+                    if (h[1] && h[0]) push(ce[1]);
+                    if (h[2] && (h[0] || h[1])) push(ce[2]);
+                    if (h[3] && (h[0] || h[1] || h[2])) push(ce[3]);
+                }
+                else
+                {
+                    if (h[3] && (h[0] || h[1] || h[2])) { lds_stack[sp * STRIDE + lane_slot] = ce[3]; ++sp; }
+                    if (h[2] && (h[0] || h[1])) { lds_stack[sp * STRIDE + lane_slot] = ce[2]; ++sp; }
+                    if (h[1] && h[0]) { lds_stack[sp * STRIDE + lane_slot] = ce[1]; ++sp; }
+                }
+            }
+            else cur = sp ? pop() : NONE;
+        }
+    }
+    return occluded;
+}
+
 /* The same with work sharing (r02, as occluded_ws): a lane whose batch is exhausted takes the bottom half of the stack
  * of a lane that is still walking, with that lane's ray; hits go to a per-owner bit mask in LDS (bit k = ray k is
  * occluded), so an owner may move on to its next ray while pieces of the previous one are still being walked by

@@ -2784,6 +2784,107 @@ __global__ __launch_bounds__(TRACE_BLOCK, EXAMPLE == 7 ? 1 : (EXAMPLE == 8 ? 6 :
     count_rays(nrays, &counters[0]);
 }
 
+/* ---------------------------------------- config #1 on the GPU: 04_ao / 06_ao_hiprt */
+/* kernelMain of examples/04_ao/04_ao.cu:31-88 (06_ao_hiprt.cu:35-91 is the same kernel over HIPRT: under the closest-hit
+ * definition with the index tie-break the two give the same image). One pixel per lane; the primary ray takes the closest
+ * hit, the 64 occlusion rays only ask whether anything lies in [0, FLT_MAX] — the any-hit walk answers that exactly as the
+ * reference's closest-hit loop does. The pixel is written straight into the RGBA8 buffer, as the reference kernel does.
+ * LAYOUT (rt_tuning key 27; results never depend on it):
+ *   0  pixel-major: a lane walks its own pixel's 64 rays back to back, drawing each ray when it starts it
+ *      (bvh.h occluded_count_refill): the wavefront is busy for the sum of its rays' lengths, not 64 x the longest.
+ *   1  ray-major: the wavefront walks the 64 rays of one hit pixel at a time, lane i ray i (draws 3i .. 3i + 2 through the
+ *      PCG jump-ahead); all rays leave one origin, so they share the top of the tree. n_visible = 64 - popcount(ballot).
+ * rays: one atomic per wavefront, W * rows primary rays + 64 per hit pixel (the reference's raytrace() calls). */
+constexpr int AO_RAYS = 64; /* N_Rays, 04_ao.cu:63 */
+__constant__ const PcgJumpTable<AO_RAYS, 3> k_ao_jump{};
+#ifndef RT_AO_WAVES
+#define RT_AO_WAVES 1
+#endif
+#ifndef RT_AO_REFILL
+#define RT_AO_REFILL 8 /* pixel-major layout: lanes waiting for their next ray that trigger the refill pass (1 / 4 / 8 / 16 / 32: 17.76 / 15.41 / 14.72 / 14.80 / 15.92 ms, docs/MEASUREMENT_LOG_r07.md) */
+#endif
+RT_DEV f3 ao_direction(PCG& rng, f3 t0, f3 t1, f3 n)
+{
+    /* three draws in argument order (04_ao.cu:66-67), common/core.hpp:76-89 */
+    const float r0 = rng.uniformf();
+    const float r1 = rng.uniformf();
+    const float r2 = rng.uniformf();
+    const f3 s = sample_hemisphere(r0, r1, r2);
+    return t0 * s.x + t1 * s.z + n * s.y;
+}
+template <int LAYOUT>
+__global__ __launch_bounds__(TRACE_BLOCK, RT_AO_WAVES) void k_ao(SceneView S, FrameParams P, uint32_t* __restrict__ pixels,
+                                                                 unsigned long long* __restrict__ rays)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_stack[WIDE_LDS_STACK * TRACE_BLOCK];
+    int x, row;
+    const bool ok = tile_pixel<TRACE_BLOCK>(P, x, row);
+    const int yi = P.H - 1 - row;
+    bool hit = false;
+    f3 ao_ro = P.rg_origin, n = F3(0.0f, 1.0f, 0.0f), t0 = F3(1.0f, 0.0f, 0.0f), t1 = F3(0.0f, 0.0f, 1.0f);
+    PCG rng;
+    rng.state = 0u; rng.inc = 1u;
+    if (ok)
+    {
+        const f3 rd = primary_direction(P, x, yi);
+        Hit h;
+        h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.prim = -1;
+        hit = trace_wide<false, false, TRACE_BLOCK>(S.wide, s_stack, P.rg_origin, rd, 0.0f, kFltMax, h, nullptr, RT_BARY_TV(S));
+        if (hit)
+        {
+            f3 v0, v1, v2;
+            load_tri(S.bvh.tv, h.prim, v0, v1, v2);
+            n = tri_normal(v0, v1, v2); /* normal_of, common/core.hpp:50-55 */
+            if (0.0f < dot(n, rd)) n = -n;
+            t0 = normalize(v1 - v0); /* a_tangent_of, common/core.hpp:45-48 */
+            t1 = cross(t0, n);
+            const f3 p_hit = P.rg_origin + rd * h.t;
+            ao_ro = p_hit + n * 0.0001f;
+            rng = pcg_init(0u, hashPCG3((uint32_t)x, (uint32_t)yi, 42u)); /* seed 0, sequence = the hash (04_ao.cu:42) */
+        }
+    }
+    int occluded = 0;
+    if (LAYOUT == 0)
+    {
+        occluded = occluded_count_refill<TRACE_BLOCK, RT_AO_REFILL>(S.wide, s_stack, ao_ro, hit ? AO_RAYS : 0, 0.0f, kFltMax,
+                                                      [&]() { return ao_direction(rng, t0, t1, n); });
+    }
+    else
+    {
+        const int lane = (int)(threadIdx.x & 63);
+        const PcgJump jmp = k_ao_jump.e[lane];
+        for (unsigned long long todo = __ballot(hit); todo != 0ull; todo &= todo - 1ull)
+        {
+            const int k = __ffsll((long long)todo) - 1;
+            const f3 o = F3(__shfl(ao_ro.x, k), __shfl(ao_ro.y, k), __shfl(ao_ro.z, k));
+            const f3 nk = F3(__shfl(n.x, k), __shfl(n.y, k), __shfl(n.z, k));
+            const f3 ak = F3(__shfl(t0.x, k), __shfl(t0.y, k), __shfl(t0.z, k));
+            const f3 bk = F3(__shfl(t1.x, k), __shfl(t1.y, k), __shfl(t1.z, k));
+            PCG r;
+            r.state = (uint64_t)(uint32_t)__shfl((int)(uint32_t)rng.state, k) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(rng.state >> 32), k) << 32);
+            r.inc = (uint64_t)(uint32_t)__shfl((int)(uint32_t)rng.inc, k) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(rng.inc >> 32), k) << 32);
+            r = pcg_jump(r, jmp);
+            const f3 dir = ao_direction(r, ak, bk, nk);
+            Hit ah;
+            const bool occ = trace_wide<true, false, TRACE_BLOCK>(S.wide, s_stack, o, dir, 0.0f, kFltMax, ah);
+            const int cnt = __popcll(__ballot(occ));
+            if (lane == k) occluded = cnt;
+        }
+    }
+    if (ok)
+    {
+        uint32_t px = 0xff202020u; /* (32, 32, 32, 255) */
+        if (hit)
+        {
+            const float ao = (float)(AO_RAYS - occluded) / (float)AO_RAYS;
+            const uint32_t c = (uint32_t)(int)(pm_powf_pos(ao, 1.0f / 2.2f) * 255.0f);
+            px = c | (c << 8) | (c << 16) | 0xff000000u;
+        }
+        pixels[(size_t)x + (size_t)(row - P.lrow0) * P.W] = px;
+    }
+    count_rays(ok ? (hit ? 1ull + AO_RAYS : 1ull) : 0ull, rays);
+}
+
 /* --------------------------------------------------------- clear / tone_mapping */
 /* common/kernels/common.cu:4-17 */
 __global__ __launch_bounds__(BLOCK) void k_clear(FrameParams P, float4* __restrict__ accum)

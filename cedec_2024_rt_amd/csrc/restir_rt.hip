@@ -201,6 +201,7 @@ struct rt_ctx
     float4* d_paths[2] = {nullptr, nullptr}; /* wavefront path tracer: live-path lists (64 B per path) */
     unsigned long long* d_pt_counters = nullptr;
     int pt_wavefront = 2; /* rt_tuning key 6: 0 one launch per frame, 1 wavefront, 2 auto (wavefront for 09_ris) */
+    int tune_ao_layout = 0; /* rt_tuning key 27: ambient occlusion (rt_path_trace 4 / 6) 0 pixel-major, 1 ray-major (frame_kernels.h k_ao) */
     void* d_stage = nullptr;
     size_t stage_bytes = 0;
 
@@ -1839,13 +1840,29 @@ int rt_tone_mapping(rt_ctx* c)
     return launch_tone_mapping(c);
 }
 
-/* `path_trace` of examples/07_pt/07_pt.cu (example 7), examples/08_nee/08_nee.cu (8) or examples/09_ris/09_ris.cu (9) */
+/* kernelMain of examples/04_ao/04_ao.cu:31-88 = 06_ao_hiprt.cu:35-91 (frame_kernels.h k_ao): RGBA8 straight into the pixel
+ * buffer over the context's own rows; the accumulation buffer, the frame number and the options play no part */
+static int launch_ao(rt_ctx* c)
+{
+    const SceneView S = make_scene(c);
+    const FrameParams P = make_params(c, 0, 0, K_RAYCAST); /* the tracing kernels' tile order: interleaved over the XCDs */
+    const int g = trace_grid(c);
+    RT_HIP(c, hipMemsetAsync(c->d_counter, 0, 8, c->stream));
+    if (c->tune_ao_layout == 1) k_ao<1><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_pixels, c->d_counter);
+    else k_ao<0><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_pixels, c->d_counter);
+    RT_HIP(c, hipGetLastError());
+    return RT_OK;
+}
+
+/* `path_trace` of examples/07_pt/07_pt.cu (example 7), examples/08_nee/08_nee.cu (8) or examples/09_ris/09_ris.cu (9);
+ * example 4 / 6: the ambient occlusion of examples/04_ao/04_ao.cu / examples/06_ao_hiprt/06_ao_hiprt.cu (launch_ao) */
 int rt_path_trace(rt_ctx* c, int example, int frame)
 {
     RT_CHECK_CTX(c);
     JOIN_TAIL(c);
     NEED_SCENE(c);
-    if (example != 7 && example != 8 && example != 9) RT_FAIL(c, RT_ERR_ARG, "example must be 7 (07_pt), 8 (08_nee) or 9 (09_ris)");
+    if (example == 4 || example == 6) return launch_ao(c);
+    if (example != 7 && example != 8 && example != 9) RT_FAIL(c, RT_ERR_ARG, "example must be 4 (04_ao), 6 (06_ao_hiprt), 7 (07_pt), 8 (08_nee) or 9 (09_ris)");
     if (example != 7 && c->n_lights == 0) RT_FAIL(c, RT_ERR_STATE, "08_nee / 09_ris need at least one emissive triangle");
     const SceneView S = make_scene(c);
     FrameParams P = make_params(c, frame, 0, K_RAYCAST);
@@ -3063,6 +3080,7 @@ int rt_tuning(rt_ctx* c, int key, int value)
     else if (key == 24 && (value == 0 || value == 1)) c->tune_half_raycast = value;
     else if (key == 25 && value >= -1 && value <= 1) c->tune_fuse_raycast = value;
     else if (key == 26 && (value == 0 || value == 1)) c->tune_mark_split = value;
+    else if (key == 27 && (value == 0 || value == 1)) c->tune_ao_layout = value;
     else if (key == 22 && value >= -1 && value <= 1) { c->tune_spec_free = value; c->spec_valid = false; c->spec_gen_valid = false; }
     else RT_FAIL(c, RT_ERR_ARG, "bad tuning key/value %d/%d", key, value);
     return RT_OK;
@@ -3097,6 +3115,7 @@ int rt_tuning_get(rt_ctx* c, int key, int* value)
         case 24: *value = c->tune_half_raycast; break;
         case 25: *value = c->tune_fuse_raycast; break;
         case 26: *value = c->tune_mark_split; break;
+        case 27: *value = c->tune_ao_layout; break;
         default: RT_FAIL(c, RT_ERR_ARG, "bad tuning key %d", key);
     }
     return RT_OK;

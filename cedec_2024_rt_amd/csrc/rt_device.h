@@ -102,6 +102,37 @@ RT_HD PCG pcg_init(uint64_t seed, uint64_t sequence)
     r.uniform();
     return r;
 }
+/* Exact jump-ahead of the LCG under PCG: k steps of state' = A state + inc give state_k = A^k state + C_k inc (mod 2^64) with
+ * C_k = A^(k-1) + ... + A + 1. pcg_jump(r, pcg_jump_of(k)) is r after k draws (the ray-major AO layout starts lane i at draw 3i). */
+struct PcgJump
+{
+    uint64_t mul, add;
+};
+constexpr PcgJump pcg_jump_of(int k)
+{
+    uint64_t m = 1u, a = 0u;
+    for (int j = 0; j < k; ++j)
+    {
+        a = a * 6364136223846793005ULL + 1u;
+        m = m * 6364136223846793005ULL;
+    }
+    return PcgJump{m, a};
+}
+/* entry i = the jump over STEP * i draws */
+template <int N, int STEP>
+struct PcgJumpTable
+{
+    PcgJump e[N];
+    constexpr PcgJumpTable() : e()
+    {
+        for (int i = 0; i < N; ++i) e[i] = pcg_jump_of(STEP * i);
+    }
+};
+RT_HD PCG pcg_jump(PCG r, PcgJump j)
+{
+    r.state = r.state * j.mul + j.add * r.inc;
+    return r;
+}
 RT_HD uint32_t hashPCG(uint32_t v)
 {
     const uint32_t state = v * 747796405u + 2891336453u;

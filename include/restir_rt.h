@@ -142,7 +142,11 @@ int rt_tone_mapping(rt_ctx* ctx);                            /* tone_mapping    
  * examples/07_pt/07_pt.cu:11-90 (example = 7), examples/08_nee/08_nee.cu:11-140 (example = 8) and
  * examples/09_ris/09_ris.cu:11-166 (example = 9); camera, Options (max_depth,
  * sky_color, ris_sample_count, accumulate, use_shadowed_target_function) and the accumulation
- * buffer as for 10_restir_di; follow with rt_tone_mapping as 07_pt.cpp:222 does. ---- */
+ * buffer as for 10_restir_di; follow with rt_tone_mapping as 07_pt.cpp:222 does.
+ * example = 6 / 4: BASELINE config #1 on the GPU, the `kernelMain` of examples/06_ao_hiprt/06_ao_hiprt.cu:35-91 /
+ * examples/04_ao/04_ao.cu:31-88 (same image): ambient occlusion with 64 rays per hit pixel, RGBA8 written straight into
+ * RT_BUF_PIXELS over the context's own rows; frame, the options and the accumulation buffer play no part, and no emissive
+ * triangle is needed. ---- */
 int rt_path_trace(rt_ctx* ctx, int example, int frame);
 
 /* ---- one frame = 10_restir_di.cpp:257-379 (clear_first = camera.is_updated()) ----

@@ -269,7 +269,11 @@ int rt_trace_time(rt_ctx* ctx, float* ms);
  *  26    (r06) rt_halo_mark as one workgroup per (tile, pass) instead of one per tile that replays the passes in series: 0
  *        (default = r02-r05), 1. A strip's mark launch is half a generation of wavefronts and lasts as long as one thread's
  *        chain of 3 x 5 neighbour replays - but it is not on the frame's critical chain and its total work stays the same:
- *        measured +-1 % (profiles/r06_mark_split_ab.txt). */
+ *        measured +-1 % (profiles/r06_mark_split_ab.txt).
+ * Ambient occlusion (rt_path_trace example 4 / 6)
+ *  27    (r07) layout of the 64 occlusion rays per pixel: 0 (default) pixel-major, a lane walks its own pixel's rays back to back
+ *        and draws each when it starts it; 1 ray-major, the wavefront walks one pixel's 64 rays at a time (lane i from draw 3i
+ *        through the PCG jump-ahead). Same image either way (ambient occlusion). */
 int rt_tuning(rt_ctx* ctx, int key, int value);
 /* the value a key holds now (measurement records name the builder / variants that were really used) */
 int rt_tuning_get(rt_ctx* ctx, int key, int* value);

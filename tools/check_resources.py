@@ -28,6 +28,8 @@ BUDGET = [
     (r"^k_spatial<true, true>", 80, 7),
     (r"^k_tone_mapping", 0, 8),
     (r"^k_halo_mark<", 0, 8),
+    (r"^k_ao<0>", 0, 7),   # r07 ambient occlusion, pixel-major (default): 8 wavefronts per SIMD (RT_AO_WAVES=8) measured no faster
+    (r"^k_ao<1>", 0, 6),   # ray-major (rt_tuning 27 = 1)
 ]
 
 
