@@ -10,12 +10,16 @@
  *              [--shadowed 0|1] [--visreuse 0|1] [--accumulate 0|1] [--by-kernel]
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
+ *              [--move-lights dx dy dz]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
  * image rows (cedec_2024_rt_amd/csrc/host_path.h: brute-force closest hit, 64 ambient-occlusion rays per pixel,
  * host libm), on --threads host threads (default: all). No GPU call is made: it runs on a machine without one.
  * Defaults then follow 04_ao.cpp (256x256 is the BASELINE size; camera (8,8,8) -> (0,0,0), common/misc.hpp:217-218);
  * --rgba writes the W*H RGBA8 bytes in the reference's storage order (what its pixel buffer holds).
+ * --move-lights dx dy dz (--example 10, also with --ranks): before every frame from the second on, the emissive triangles move
+ * by (dx, dy, dz) and rt_scene_update refits the scene (the span from the lowest to the highest emissive index); the call's wall
+ * time is printed per frame, and with --accumulate 1 the frame starts a new accumulation.
  * --example 6: the same ambient occlusion ON THE GPU through rt_path_trace (examples/06_ao_hiprt/06_ao_hiprt.cu:35-91, the
  * same image as 04_ao's kernel). Defaults follow 06_ao_hiprt.cpp:79-80: 1920x1080, camera (8,8,8) -> (0,0,0), fovy pi/4.
  * --frames K times K launches after one warm-up (host clock around rt_sync) and prints ms per launch and Mray/s in the
@@ -232,6 +236,43 @@ static std::vector<rt_triangle> load_tris(const std::string& path)
     return t;
 }
 
+/* ---- --move-lights dx dy dz (--example 10): before frame f >= 2 every emissive triangle moves by (dx, dy, dz) from where it
+ * was (one float add per coordinate, as scenes.move_triangles) and rt_scene_update refits the scene over the span from the
+ * lowest to the highest emissive index; with --accumulate 1 that frame clears the accumulation (as after a camera move) ---- */
+struct LightMove
+{
+    bool on = false;
+    float d[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t first = 0, count = 0;
+};
+static void light_span(const std::vector<rt_triangle>& tris, LightMove& mv)
+{
+    uint32_t lo = 0xffffffffu, hi = 0u;
+    for (size_t i = 0; i < tris.size(); ++i)
+        if (tris[i].emissive[0] > 0.0f || tris[i].emissive[1] > 0.0f || tris[i].emissive[2] > 0.0f)
+        {
+            lo = lo < (uint32_t)i ? lo : (uint32_t)i;
+            hi = (uint32_t)i;
+        }
+    mv.first = lo == 0xffffffffu ? 0u : lo;
+    mv.count = lo == 0xffffffffu ? 0u : hi - lo + 1u;
+}
+/* moves the lights of the span and updates the context; returns the call's wall time in ms */
+static double move_lights(rt_ctx* ctx, std::vector<rt_triangle>& tris, const LightMove& mv)
+{
+    for (uint32_t i = mv.first; i < mv.first + mv.count; ++i)
+    {
+        rt_triangle& t = tris[i];
+        if (!(t.emissive[0] > 0.0f || t.emissive[1] > 0.0f || t.emissive[2] > 0.0f)) continue;
+        for (int k = 0; k < 3; ++k)
+            for (int a = 0; a < 3; ++a) t.v[k][a] = t.v[k][a] + mv.d[a];
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = rt_scene_update(ctx, tris.data() + mv.first, mv.first, mv.count);
+    if (rc != RT_OK) die(ctx, "rt_scene_update", rc);
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 /* ---- --ranks N: one process per GPU over the native strip driver ---- */
 struct Shared /* anonymous shared mapping made by the parent before fork */
 {
@@ -253,8 +294,9 @@ static void shared_barrier(Shared* sh, int which, int ranks)
 }
 static int rank_main(int rank, int ranks, bool mirror, bool shm, bool equal_strips, const std::vector<int>& given_bounds, Shared* sh,
                      const std::vector<rt_triangle>& triangles, int W, int H, int frames, const float* eye, const float* lookat, const rt_options& opt,
-                     const std::string& pfm)
+                     const std::string& pfm, const LightMove& mv)
 {
+    std::vector<rt_triangle> moving = mv.on ? triangles : std::vector<rt_triangle>();
     const float up[3] = {0, 1, 0};
     const int halo = 87, device = (mirror || shm) ? 0 : rank;
     if (rank == 0 && shm) snprintf(sh->uid, sizeof(sh->uid), "rtmg_app_%d_%llx", (int)getppid(),
@@ -312,7 +354,14 @@ static int rank_main(int rank, int ranks, bool mirror, bool shm, bool equal_stri
     for (int frame = 1; frame <= frames; ++frame)
     {
         if (frame == warm + 1) { CK(rt_sync(ctx)); shared_barrier(sh, 1, ranks); clock_gettime(CLOCK_MONOTONIC, &t0); }
-        rc = rt_mg_frame(mg, frame, 0);
+        int clear = 0;
+        if (mv.on && frame >= 2 && mv.count > 0)
+        {
+            const double ms = move_lights(ctx, moving, mv);
+            if (rank == 0) printf("frame %d scene update: %.3f ms (%u triangles)\n", frame, ms, mv.count);
+            clear = opt.accumulate ? 1 : 0;
+        }
+        rc = rt_mg_frame(mg, frame, clear);
         if (rc != RT_OK) { fprintf(stderr, "rank %d frame %d: %s\n", rank, frame, rt_mg_last_error(mg)); return 1; }
     }
     CK(rt_sync(ctx));
@@ -370,6 +419,7 @@ int main(int argc, char** argv)
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0;
+    LightMove mv;
     rt_options opt;
     memset(&opt, 0, sizeof(opt));
     opt.max_depth = 6; opt.ris_sample_count = 32; opt.rejection_heuristics_threshold = 0.2f;
@@ -410,6 +460,7 @@ int main(int argc, char** argv)
         else if (a == "--pfm") pfm = argv[++i];
         else if (a == "--rgba") rgba = argv[++i];
         else if (a == "--threads") threads = atoi(argv[++i]);
+        else if (a == "--move-lights") { mv.d[0] = f(1); mv.d[1] = f(2); mv.d[2] = f(3); i += 3; mv.on = true; }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     std::vector<rt_triangle> triangles = !obj.empty() ? load_obj(obj) : load_tris(tris_path);
@@ -469,6 +520,8 @@ int main(int argc, char** argv)
         return write_ao_image(px, W, H, rgba, ppm, png);
     }
     if (example != 10 && example != 7 && example != 8 && example != 9) { fprintf(stderr, "--example 10, 7, 8, 9, 6 or 4\n"); return 2; }
+    if (mv.on && example != 10) { fprintf(stderr, "--move-lights applies to --example 10\n"); return 2; }
+    if (mv.on) light_span(triangles, mv);
 
     if (ranks > 1)
     {
@@ -492,7 +545,7 @@ int main(int argc, char** argv)
             const pid_t pid = fork();
             if (pid == 0)
             {
-                const int code = rank_main(r, ranks, mirror, shm, equal_strips, given_bounds, sh, triangles, W, H, frames, eye, lookat, opt, pfm);
+                const int code = rank_main(r, ranks, mirror, shm, equal_strips, given_bounds, sh, triangles, W, H, frames, eye, lookat, opt, pfm, mv);
                 fflush(stdout);
                 fflush(stderr);
                 _exit(code); /* no atexit handlers of the parent's image in a forked child */
@@ -524,15 +577,23 @@ int main(int argc, char** argv)
 
     for (int frame = 1; frame <= frames; ++frame) /* frame++ before the first launch, :233-234 */
     {
+        int clear = 0;
+        if (mv.on && frame >= 2 && mv.count > 0)
+        {
+            const double ms = move_lights(ctx, triangles, mv);
+            printf("frame %d scene update: %.3f ms (%u triangles)\n", frame, ms, mv.count);
+            clear = opt.accumulate ? 1 : 0;
+        }
         if (example != 10)
         {
             /* examples/07_pt/07_pt.cpp:206-222: path_trace, then tone_mapping */
             CK(rt_path_trace(ctx, example, frame));
             CK(rt_tone_mapping(ctx));
         }
-        else if (!by_kernel) { CK(rt_frame(ctx, frame, 0, nullptr)); }
+        else if (!by_kernel) { CK(rt_frame(ctx, frame, clear, nullptr)); }
         else
         {
+            if (clear) CK(rt_clear(ctx));
             /* the launch sequence of 10_restir_di.cpp:270-379, one C-ABI call per kernel */
             CK(rt_raycast(ctx));
             CK(rt_generate_candidate(ctx, frame, RT_RES_0));
@@ -568,6 +629,15 @@ int main(int argc, char** argv)
         printf("rays in the last frame: %llu\n", (unsigned long long)rays);
     }
 
+    if (!rgba.empty())
+    {
+        std::vector<uint8_t> px((size_t)W * H * 4);
+        CK(rt_download(ctx, RT_BUF_PIXELS, px.data(), px.size()));
+        FILE* f = fopen(rgba.c_str(), "wb");
+        if (!f) { fprintf(stderr, "cannot write %s\n", rgba.c_str()); return 1; }
+        fwrite(px.data(), 1, px.size(), f);
+        fclose(f);
+    }
     if (!ppm.empty())
     {
         std::vector<uint8_t> px((size_t)W * H * 4);

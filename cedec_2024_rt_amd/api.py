@@ -30,7 +30,7 @@ PUBLIC_EXPORTS = [
 ]
 # include/restir_rt_internal.h: what the strip driver, the measurement tools and the parity tests use beyond it
 INTERNAL_EXPORTS = [
-    "rt_set_stream_own", "rt_camera_pose", "rt_path_trace_rays", "rt_frame_stage", "rt_frame_stage_input",
+    "rt_set_stream_own", "rt_camera_pose", "rt_path_trace_rays", "rt_scene_update", "rt_frame_stage", "rt_frame_stage_input",
     "rt_frame_stage_begin", "rt_frame_stage_run", "rt_frame_stage_run_part", "rt_frame_stage_fork", "rt_frame_stage_run_async",
     "rt_frame_stage_run_ranges", "rt_frame_stage_end", "rt_frame_stage_output", "rt_halo_bytes", "rt_halo_pack",
     "rt_halo_unpack", "rt_halo_bitmap_words", "rt_halo_flags_bytes", "rt_halo_flags_pack", "rt_halo_flags_unpack",
@@ -92,6 +92,7 @@ def load_library(exp=False, path=None):
     L.rt_sync.argtypes = [vp]
     L.rt_scene_set.argtypes = [vp, vp, C.c_uint32]
     L.rt_scene_info.argtypes = [vp, vp, vp, vp]
+    L.rt_scene_update.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
     L.rt_camera_lookat.argtypes = [vp, vp, vp, vp, cf]
     L.rt_camera_set.argtypes = [vp, vp, vp]
     L.rt_camera_get.argtypes = [vp, vp]
@@ -388,6 +389,14 @@ class Renderer:
     def set_scene(self, triangles):
         t = np.ascontiguousarray(triangles, dtype=TRIANGLE)
         self._ck(self.L.rt_scene_set(self.h, _p(t), len(t)))
+
+    def update_scene(self, triangles, first=0):
+        """Replace triangles [first, first + len(triangles)) of the current scene (rt_scene_update: same count, same order;
+        the tree is refitted, not rebuilt). Results equal set_scene on the whole new array."""
+        t = np.ascontiguousarray(triangles, dtype=TRIANGLE)
+        if int(first) < 0:
+            raise RtError(f"update_scene: first = {first} < 0")
+        self._ck(self.L.rt_scene_update(self.h, _p(t), int(first), len(t)))
 
     def scene_info(self):
         a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()

@@ -231,6 +231,42 @@ constexpr int WIDE_LDS_ROWS = WIDE_LDS_STACK + 2;
 
 RT_DEV float wide_byte(uint32_t w, int k) { return (float)((w >> (8 * k)) & 0xffu); }
 
+/* Quantisation of one inner record, shared by every writer of the records (bvh_build_host.h::collapse_wide,
+ * bvh_build_device.h::k_collapse_level, bvh_refit.h::k_refit_level). wide_quant_scale: per axis the power-of-two step
+ * whose 255 steps cover the node box [lo, hi], exponent clamped to the normal range; returns ex | ey << 8 | ez << 16.
+ * wide_quant_child: child k's byte bounds in q (q[a] = lo bytes, q[3 + a] = hi bytes), rounded outward so that the
+ * box the traversal decodes in binary32, lo + q * scale, contains the child box. */
+RT_HD uint32_t wide_quant_scale(const float lo[3], const float hi[3], float scale[3])
+{
+    uint32_t ebits = 0;
+    for (int a = 0; a < 3; ++a)
+    {
+        const float ext = fmaxf(hi[a] - lo[a], 1e-30f);
+        int e;
+        frexpf(ext / 255.0f, &e); /* ext/255 = m * 2^e, m in [0.5,1) => 2^e >= ext/255 */
+        int biased = e + 127;
+        if (biased < 1) biased = 1;
+        if (biased > 254) biased = 254;
+        ebits |= (uint32_t)biased << (8 * a);
+        scale[a] = ldexpf(1.0f, biased - 127);
+    }
+    return ebits;
+}
+RT_HD void wide_quant_child(const float lo[3], const float scale[3], const float clo[3], const float chi[3], int k, uint32_t q[6])
+{
+    for (int a = 0; a < 3; ++a)
+    {
+        int ql = (int)floorf((clo[a] - lo[a]) / scale[a]);
+        int qh = (int)ceilf((chi[a] - lo[a]) / scale[a]);
+        while (ql > 0 && lo[a] + (float)ql * scale[a] > clo[a]) --ql;
+        while (qh < 255 && lo[a] + (float)qh * scale[a] < chi[a]) ++qh;
+        ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
+        qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
+        q[a] |= (uint32_t)ql << (8 * k);
+        q[3 + a] |= (uint32_t)qh << (8 * k);
+    }
+}
+
 /* Leaf tests are DEFERRED: a lane that reaches a leaf parks it (two slots) and keeps walking inner
  * records; the wave runs the triangle test only when the parked leaves number at least
  * RT_LEAF_NUM/RT_LEAF_DEN of its live lanes (or no lane has inner work left). With a leaf test per ~5

@@ -876,19 +876,8 @@ __global__ void k_collapse_level(const BvhNode* __restrict__ bin, const float* _
     for (int k = 0; k < n; ++k)
         for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], ch[k].lo[a]); hi[a] = fmaxf(hi[a], ch[k].hi[a]); }
     const unsigned int base = atomicAdd(&st->n_rec, (unsigned int)n);
-    uint32_t ebits[3];
     float scale[3];
-    for (int a = 0; a < 3; ++a)
-    {
-        const float ext = fmaxf(hi[a] - lo[a], 1e-30f);
-        int e;
-        frexpf(ext / 255.0f, &e);
-        int biased = e + 127;
-        if (biased < 1) biased = 1;
-        if (biased > 254) biased = 254;
-        ebits[a] = (uint32_t)biased;
-        scale[a] = ldexpf(1.0f, biased - 127);
-    }
+    const uint32_t ebits = wide_quant_scale(lo, hi, scale);
     uint32_t q[6] = {0, 0, 0, 0, 0, 0}, meta = 0;
     int n_inner = 0;
     for (int k = 0; k < n; ++k)
@@ -897,18 +886,7 @@ __global__ void k_collapse_level(const BvhNode* __restrict__ bin, const float* _
     int qi = 0;
     for (int k = 0; k < n; ++k)
     {
-        for (int a = 0; a < 3; ++a)
-        {
-            int ql = (int)floorf((ch[k].lo[a] - lo[a]) / scale[a]);
-            int qh = (int)ceilf((ch[k].hi[a] - lo[a]) / scale[a]);
-            /* the traversal decodes lo + q*scale in binary32: the decoded box must contain the child box */
-            while (ql > 0 && lo[a] + (float)ql * scale[a] > ch[k].lo[a]) --ql;
-            while (qh < 255 && lo[a] + (float)qh * scale[a] < ch[k].hi[a]) ++qh;
-            ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
-            qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
-            q[a] |= (uint32_t)ql << (8 * k);
-            q[3 + a] |= (uint32_t)qh << (8 * k);
-        }
+        wide_quant_child(lo, scale, ch[k].lo, ch[k].hi, k, q);
         if (ch[k].bin >= 0)
         {
             meta |= 1u << (8 * k);
@@ -929,7 +907,7 @@ __global__ void k_collapse_level(const BvhNode* __restrict__ bin, const float* _
     }
     uint32_t* R = recs + 4 * WIDE_STRIDE * (size_t)wk.out;
     R[0] = __float_as_uint(lo[0]); R[1] = __float_as_uint(lo[1]); R[2] = __float_as_uint(lo[2]);
-    R[3] = ebits[0] | (ebits[1] << 8) | (ebits[2] << 16);
+    R[3] = ebits;
     R[4] = base; R[5] = meta; R[6] = q[0]; R[7] = q[1];
     R[8] = q[2]; R[9] = q[3]; R[10] = q[4]; R[11] = q[5];
 }

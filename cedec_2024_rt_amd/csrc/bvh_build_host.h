@@ -185,35 +185,13 @@ static int collapse_wide(const std::vector<BvhNode>& bin, const rt_triangle* tri
             for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], ch[k].lo[a]); hi[a] = fmaxf(hi[a], ch[k].hi[a]); }
         const uint32_t base = (uint32_t)recs.size();
         recs.resize(recs.size() + (size_t)n);
-        /* per-axis power-of-two scale with 255 steps covering the node box */
-        uint32_t ebits[3];
+        /* per-axis power-of-two scale with 255 steps covering the node box (bvh.h, shared with the device collapse and the refit) */
         float scale[3];
-        for (int a = 0; a < 3; ++a)
-        {
-            const float ext = fmaxf(hi[a] - lo[a], 1e-30f);
-            int e;
-            frexpf(ext / 255.0f, &e); /* ext/255 = m * 2^e, m in [0.5,1) => 2^e >= ext/255 */
-            int biased = e + 127;
-            if (biased < 1) biased = 1;
-            if (biased > 254) biased = 254;
-            ebits[a] = (uint32_t)biased;
-            scale[a] = ldexpf(1.0f, biased - 127);
-        }
+        const uint32_t ebits = wide_quant_scale(lo, hi, scale);
         uint32_t q[6] = {0, 0, 0, 0, 0, 0}, meta = 0;
         for (int k = 0; k < n; ++k)
         {
-            for (int a = 0; a < 3; ++a)
-            {
-                int ql = (int)floorf((ch[k].lo[a] - lo[a]) / scale[a]);
-                int qh = (int)ceilf((ch[k].hi[a] - lo[a]) / scale[a]);
-                /* the device decodes lo + q*scale in binary32: make sure the decoded box contains the child box */
-                while (ql > 0 && lo[a] + (float)ql * scale[a] > ch[k].lo[a]) --ql;
-                while (qh < 255 && lo[a] + (float)qh * scale[a] < ch[k].hi[a]) ++qh;
-                ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
-                qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
-                q[a] |= (uint32_t)ql << (8 * k);
-                q[3 + a] |= (uint32_t)qh << (8 * k);
-            }
+            wide_quant_child(lo, scale, ch[k].lo, ch[k].hi, k, q);
             if (ch[k].bin >= 0)
             {
                 meta |= 1u << (8 * k);
@@ -233,7 +211,7 @@ static int collapse_wide(const std::vector<BvhNode>& bin, const rt_triangle* tri
         }
         WideRec& R = recs[wk.out];
         R.w[0] = f2u(lo[0]); R.w[1] = f2u(lo[1]); R.w[2] = f2u(lo[2]);
-        R.w[3] = ebits[0] | (ebits[1] << 8) | (ebits[2] << 16);
+        R.w[3] = ebits;
         R.w[4] = base; R.w[5] = meta; R.w[6] = q[0]; R.w[7] = q[1];
         R.w[8] = q[2]; R.w[9] = q[3]; R.w[10] = q[4]; R.w[11] = q[5];
     }

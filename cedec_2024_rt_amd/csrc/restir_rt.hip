@@ -39,6 +39,7 @@ static_assert(sizeof(BvhNode) == 64, "BVH node");
 #include "host_path.h"
 #include "bvh_build_host.h"
 #include "bvh_build_device.h"
+#include "bvh_refit.h"
 
 /* ======================================================================= host */
 
@@ -130,6 +131,15 @@ struct rt_ctx
     float4* d_trimat = nullptr;
     float4* d_lights = nullptr;
     float4* d_light_ke = nullptr;
+    /* rt_scene_update: the light list in index order (host), its device copy, the refit's level lists (built at the first
+     * update of a scene: refit_off[l] .. refit_off[l + 1] = inner records of level l), its box scratch and the scene bounds */
+    std::vector<uint32_t> h_lights;
+    uint32_t* d_light_ids = nullptr;
+    uint32_t* d_refit_list = nullptr;
+    float* d_refit_box = nullptr;
+    unsigned int* d_refit_bounds = nullptr;
+    std::vector<uint32_t> refit_off;
+    bool bin_stale = false; /* the binary tree (d_nodes, trace mode 1 of the experiments library) predates an update */
 
     float4 *d_vis = nullptr, *d_g0 = nullptr, *d_g1 = nullptr, *d_accum = nullptr;
     uint32_t* d_pixels = nullptr;
@@ -392,6 +402,10 @@ int rt_create(int device, int width, int height, int row_begin, int row_end, int
 static void free_scene(rt_ctx* c)
 {
     hipFree(c->d_tris); hipFree(c->d_tv); hipFree(c->d_nodes); hipFree(c->d_trimat); hipFree(c->d_lights); hipFree(c->d_light_ke); hipFree(c->d_wide);
+    hipFree(c->d_light_ids); hipFree(c->d_refit_list); hipFree(c->d_refit_box); hipFree(c->d_refit_bounds);
+    c->d_light_ids = nullptr; c->d_refit_list = nullptr; c->d_refit_box = nullptr; c->d_refit_bounds = nullptr;
+    c->h_lights.clear(); c->refit_off.clear();
+    c->bin_stale = false;
     c->d_light_ke = nullptr;
     c->d_wide = nullptr;
     c->d_tris = nullptr; c->d_tv = nullptr; c->d_nodes = nullptr; c->d_trimat = nullptr; c->d_lights = nullptr;
@@ -1045,7 +1059,126 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     if (rc != RT_OK) return rc;
     RT_HIP(c, hipStreamSynchronize(c->stream));
     c->build_ms = (float)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_build0).count() * 1e-3f;
+    c->h_lights.swap(lights);
     c->has_scene = true;
+    return RT_OK;
+}
+
+/* Level lists of the wide tree's inner records, top-down from the root (bvh_refit.h); once per scene. */
+static int refit_topology(rt_ctx* c)
+{
+    hipStream_t st = c->stream;
+    const int levels = c->wide_height;
+    if (levels < 1 || levels > REFIT_MAX_LEVELS) RT_FAIL(c, RT_ERR_STATE, "internal: wide tree height %d", levels);
+    const uint32_t cap = (uint32_t)c->n_wide;
+    hipFree(c->d_refit_list); hipFree(c->d_refit_box); hipFree(c->d_refit_bounds); /* a failed earlier attempt */
+    c->d_refit_list = nullptr; c->d_refit_box = nullptr; c->d_refit_bounds = nullptr;
+    RT_HIP(c, hipMalloc(&c->d_refit_list, (size_t)cap * 4));
+    RT_HIP(c, hipMalloc(&c->d_refit_box, (size_t)cap * 24));
+    RT_HIP(c, hipMalloc(&c->d_refit_bounds, 24));
+    uint32_t* d_off = nullptr;
+    RT_HIP(c, hipMalloc(&d_off, (size_t)(levels + 2) * 4));
+    std::vector<uint32_t> off((size_t)levels + 2, 0u);
+    off[1] = 1u; /* level 0 = the root, record 0 */
+    const uint32_t root = 0u;
+    int rc = RT_OK;
+    auto ck = [&](hipError_t e) { if (e != hipSuccess && rc == RT_OK) { c->err = std::string("refit topology: ") + hipGetErrorString(e); rc = RT_ERR_HIP; } };
+    ck(hipMemcpyAsync(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+    ck(hipMemcpyAsync(c->d_refit_list, &root, 4, hipMemcpyHostToDevice, st));
+    /* the scene bounds of the leaves' pad start from the whole scene; updates only grow them */
+    ck(hipMemsetAsync(c->d_refit_bounds, 0xff, 12, st));
+    ck(hipMemsetAsync(c->d_refit_bounds + 3, 0, 12, st));
+    k_refit_bounds<<<(c->n_tris + 255) / 256, 256, 0, st>>>(c->d_tris, c->n_tris, c->d_refit_bounds);
+    for (int level = 0; level < levels && rc == RT_OK; ++level)
+    {
+        /* level l holds at most 4^l records */
+        const uint64_t bound = std::min<uint64_t>((uint64_t)1 << std::min(2 * level, 40), cap);
+        k_refit_topo_next<<<1, 1, 0, st>>>(level, d_off);
+        k_refit_topo<<<(unsigned)((bound + 255) / 256), 256, 0, st>>>(level, d_off, c->d_refit_list, cap, (const uint32_t*)c->d_wide);
+        ck(hipGetLastError());
+    }
+    ck(hipMemcpyAsync(off.data(), d_off, off.size() * 4, hipMemcpyDeviceToHost, st));
+    ck(hipStreamSynchronize(st));
+    hipFree(d_off);
+    if (rc != RT_OK) return rc;
+    /* every level non-empty, nothing below the last one, no more inner records than records */
+    for (int level = 0; level < levels; ++level)
+        if (off[(size_t)level + 1] <= off[(size_t)level]) RT_FAIL(c, RT_ERR_STATE, "internal: wide tree level %d is empty", level);
+    if (off[(size_t)levels + 1] != off[(size_t)levels] || off[(size_t)levels] > cap)
+        RT_FAIL(c, RT_ERR_STATE, "internal: wide tree deeper than its height %d (or %u inner records of %u)", levels, off[(size_t)levels], cap);
+    off.pop_back();
+    c->refit_off.swap(off);
+    return RT_OK;
+}
+
+int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uint32_t count)
+{
+    RT_CHECK_CTX(c);
+    if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "rt_scene_update before rt_scene_set");
+    if ((uint64_t)first + count > (uint64_t)c->n_tris)
+        RT_FAIL(c, RT_ERR_ARG, "triangles [%u, %llu) outside the scene's %d", first, (unsigned long long)first + count, c->n_tris);
+    if (!triangles && count) RT_FAIL(c, RT_ERR_ARG, "null triangles");
+    if (count == 0) return RT_OK;
+    RT_HIP(c, hipSetDevice(c->device));
+    /* every stream that may still read the old scene, as rt_scene_set */
+    { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
+    if (c->own_stream && c->own_stream != c->stream) RT_HIP(c, hipStreamSynchronize(c->own_stream));
+    if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+    c->spec_valid = false;
+    c->spec_gen_valid = false;
+    ++c->epoch;
+    c->bin_stale = true;
+    hipStream_t st = c->stream;
+    /* light list: the ids below and above the span stay, the span's are taken from the new triangles (index order) */
+    std::vector<uint32_t> lights;
+    {
+        const auto lo = std::lower_bound(c->h_lights.begin(), c->h_lights.end(), first);
+        const auto hi = std::lower_bound(lo, c->h_lights.end(), first + count); /* <= n_tris: no wrap */
+        lights.reserve(c->h_lights.size());
+        lights.insert(lights.end(), c->h_lights.begin(), lo);
+        for (uint32_t i = 0; i < count; ++i)
+            if (triangles[i].emissive[0] > 0.0f || triangles[i].emissive[1] > 0.0f || triangles[i].emissive[2] > 0.0f)
+                lights.push_back(first + i);
+        lights.insert(lights.end(), hi, c->h_lights.end());
+    }
+    if (lights.size() > ((size_t)1 << 26)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "more than 2^26 emissive triangles (the light table is addressed by 32-bit byte offsets)");
+    if (c->refit_off.empty()) { const int rc = refit_topology(c); if (rc != RT_OK) return rc; }
+    /* per-triangle arrays of the span */
+    RT_HIP(c, hipMemcpyAsync(c->d_tris + 15 * (size_t)first, triangles, (size_t)count * 60, hipMemcpyHostToDevice, st));
+    const int gs = (int)((count + 255) / 256);
+    k_trimat<<<gs, 256, 0, st>>>((int)count, c->d_tris + 15 * (size_t)first, c->d_trimat + 2 * (size_t)first);
+    k_bvh_tv<<<gs, 256, 0, st>>>(c->d_tris + 15 * (size_t)first, (int)count, c->d_tv + 3 * (size_t)first);
+    RT_HIP(c, hipGetLastError());
+    /* light table: records hold positions and 1 / n_lights, so all of it is rebuilt (k_light_table, as rt_scene_set) */
+    if (lights.size() != c->h_lights.size())
+    {
+        hipFree(c->d_lights); hipFree(c->d_light_ke); hipFree(c->d_light_ids);
+        c->d_lights = nullptr; c->d_light_ke = nullptr; c->d_light_ids = nullptr;
+        if (!lights.empty())
+        {
+            RT_HIP(c, hipMalloc(&c->d_lights, lights.size() * 16 * RT_LIGHT_STRIDE));
+            RT_HIP(c, hipMalloc(&c->d_light_ke, lights.size() * 16));
+        }
+    }
+    if (!lights.empty())
+    {
+        bool upload = lights != c->h_lights;
+        if (!c->d_light_ids) { RT_HIP(c, hipMalloc(&c->d_light_ids, lights.size() * 4)); upload = true; }
+        if (upload) RT_HIP(c, hipMemcpyAsync(c->d_light_ids, lights.data(), lights.size() * 4, hipMemcpyHostToDevice, st));
+        k_light_table<<<((int)lights.size() + 255) / 256, 256, 0, st>>>((int)lights.size(), c->d_light_ids, c->d_tris, c->d_lights, c->d_light_ke);
+        RT_HIP(c, hipGetLastError());
+    }
+    c->n_lights = (int)lights.size();
+    /* refit: the pad's bounds grown by the span, then the inner records level by level, deepest first */
+    k_refit_bounds<<<gs, 256, 0, st>>>(c->d_tris + 15 * (size_t)first, (int)count, c->d_refit_bounds);
+    for (int level = (int)c->refit_off.size() - 2; level >= 0; --level)
+    {
+        const uint32_t b = c->refit_off[(size_t)level], m = c->refit_off[(size_t)level + 1] - b;
+        k_refit_level<<<(m + 255) / 256, 256, 0, st>>>(c->d_refit_list + b, m, c->d_tris, c->d_refit_bounds, c->d_refit_box, (uint32_t*)c->d_wide);
+    }
+    RT_HIP(c, hipGetLastError());
+    RT_HIP(c, hipStreamSynchronize(st)); /* the caller's triangles and the light list are host memory */
+    c->h_lights.swap(lights);
     return RT_OK;
 }
 
@@ -2946,10 +3079,14 @@ int rt_spatial_bytes(rt_ctx* c, int frame, int pass, int in, uint64_t* bytes, ui
     return RT_OK;
 }
 
+/* the binary tree is built by rt_scene_set only: after an rt_scene_update the walks of it refuse */
+#define RT_CHECK_BINARY_TREE(c, binary)                                                                                   \
+    do { if ((binary) && (c)->bin_stale) RT_FAIL(c, RT_ERR_STATE, "trace mode %d walks the binary tree, which rt_scene_update does not refit", (c)->trace_mode); } while (0)
 int rt_trace_closest(rt_ctx* c, const float* rays, uint32_t n, float* hits)
 {
     RT_CHECK_CTX(c);
     if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "no scene");
+    RT_CHECK_BINARY_TREE(c, c->trace_mode == 1);
     if (n == 0) return RT_OK;
     float *d_r = nullptr, *d_h = nullptr;
     RT_HIP(c, hipMalloc(&d_r, (size_t)n * 32));
@@ -3000,6 +3137,7 @@ int rt_trace_stats(rt_ctx* c, const float* rays, uint32_t n, uint32_t* stats)
 {
     RT_CHECK_CTX(c);
     if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "no scene");
+    RT_CHECK_BINARY_TREE(c, c->trace_mode != 0 && c->trace_mode != 4 && c->trace_mode != 5);
     if (n == 0) return RT_OK;
     float* d_r = nullptr;
     uint32_t* d_s = nullptr;

@@ -147,6 +147,16 @@ def light_indices(triangles):
     return np.nonzero((e[:, 0] > 0) | (e[:, 1] > 0) | (e[:, 2] > 0))[0].astype(np.uint32)
 
 
+def move_triangles(tris, mask, offset):
+    """A copy of `tris` with the masked triangles' vertices translated by `offset`: one float32 add per coordinate
+    (v + offset), the same IEEE operation restir_app's --move-lights performs, so both agree bit for bit."""
+    out = np.array(tris, dtype=tris.dtype, copy=True)
+    m = np.asarray(mask)
+    off = np.asarray(offset, dtype=np.float32).reshape(3)
+    out["v"][m] = (out["v"][m] + off[None, None, :]).astype(np.float32)
+    return out
+
+
 def scene_sha256(triangles):
     return hashlib.sha256(np.ascontiguousarray(triangles).tobytes()).hexdigest()
 

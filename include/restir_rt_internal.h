@@ -28,6 +28,17 @@ int rt_camera_pose(rt_ctx* ctx, float eye[3], float lookat[3]); /* the pose the 
 
 int rt_path_trace_rays(rt_ctx* ctx, uint64_t* rays); /* raytrace() calls of the last launch */
 
+/* ---- scene update: the counterpart of HIPRT's hiprtBuildGeometry with hiprtBuildOperationUpdate (a refit) ---- */
+/* Replace triangles [first, first + count) of the current scene (same total count, same index order).
+ * Afterwards every result equals what rt_scene_set on the full new array would give. The tree keeps its topology
+ * (rt_bvh_info does not change) and gets new boxes (a refit on the device); the per-triangle tables, the light table
+ * and rt_scene_info's light count follow the new triangles. Any frame enqueued after the call sees the new scene: the
+ * state epoch changes and the speculative next-frame work is dropped; accumulation is left alone (pass clear_first).
+ * Synchronises the context's streams as rt_scene_set does. No scene: RT_ERR_STATE; a span beyond the scene or a NULL
+ * pointer with count > 0: RT_ERR_ARG; count == 0: nothing changes. The experiments library's binary-tree walks refuse
+ * (RT_ERR_STATE) after an update until the next rt_scene_set. */
+int rt_scene_update(rt_ctx* ctx, const rt_triangle* triangles, uint32_t first, uint32_t count);
+
 /* ---- rt_frame in stages ---- */
 /* The same frame cut into stages for strip contexts (multi-GPU): stage 0 = [clear,] raycast,
  * generate_candidate(+temporal); stage k in 1..passes = spatial pass k-1; stage passes+1 = resolve,
