@@ -10,13 +10,15 @@
  *              [--shadowed 0|1] [--visreuse 0|1] [--accumulate 0|1] [--by-kernel]
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
- *              [--move-lights dx dy dz]
+ *              [--move-lights dx dy dz] [--denoise N]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
  * image rows (cedec_2024_rt_amd/csrc/host_path.h: brute-force closest hit, 64 ambient-occlusion rays per pixel,
  * host libm), on --threads host threads (default: all). No GPU call is made: it runs on a machine without one.
  * Defaults then follow 04_ao.cpp (256x256 is the BASELINE size; camera (8,8,8) -> (0,0,0), common/misc.hpp:217-218);
  * --rgba writes the W*H RGBA8 bytes in the reference's storage order (what its pixel buffer holds).
+ * --denoise N (--example 10, 7, 8, 9; one GPU): after every frame rt_denoise with N a-trous iterations (0..8) and the default
+ * parameters; --ppm / --png / --rgba then write its tone-mapped image and --pfm its HDR image (RT_BUF_DENOISED).
  * --move-lights dx dy dz (--example 10, also with --ranks): before every frame from the second on, the emissive triangles move
  * by (dx, dy, dz) and rt_scene_update refits the scene (the span from the lowest to the highest emissive index); the call's wall
  * time is printed per frame, and with --accumulate 1 the frame starts a new accumulation.
@@ -418,7 +420,7 @@ int main(int argc, char** argv)
     std::string obj, tris_path, ppm, png, pfm, dump, rgba;
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
-    int example = 10, ranks = 1, threads = 0;
+    int example = 10, ranks = 1, threads = 0, denoise = -1;
     LightMove mv;
     rt_options opt;
     memset(&opt, 0, sizeof(opt));
@@ -460,9 +462,13 @@ int main(int argc, char** argv)
         else if (a == "--pfm") pfm = argv[++i];
         else if (a == "--rgba") rgba = argv[++i];
         else if (a == "--threads") threads = atoi(argv[++i]);
+        else if (a == "--denoise") denoise = atoi(argv[++i]);
         else if (a == "--move-lights") { mv.d[0] = f(1); mv.d[1] = f(2); mv.d[2] = f(3); i += 3; mv.on = true; }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
+    if (denoise >= 0 && (example == 4 || example == 6)) { fprintf(stderr, "--denoise applies to --example 10, 7, 8 and 9\n"); return 2; }
+    if (denoise >= 0 && ranks > 1) { fprintf(stderr, "--denoise runs on one GPU (whole-frame contexts), not with --ranks\n"); return 2; }
+    if (denoise > 8) { fprintf(stderr, "--denoise: 0..8 iterations\n"); return 2; }
     std::vector<rt_triangle> triangles = !obj.empty() ? load_obj(obj) : load_tris(tris_path);
     if (triangles.empty()) { fprintf(stderr, "no triangles (use --obj or --tris)\n"); return 2; }
     if (!dump.empty())
@@ -608,6 +614,11 @@ int main(int argc, char** argv)
             CK(rt_resolve(ctx, out));
             CK(rt_tone_mapping(ctx));
         }
+        if (denoise >= 0)
+        {
+            rt_denoise_params dp = {denoise, 4.0f, 1.0f, 7, 3};
+            CK(rt_denoise(ctx, &dp));
+        }
         CK(rt_sync(ctx));
         if (!by_kernel && example == 10)
         {
@@ -615,6 +626,12 @@ int main(int argc, char** argv)
             CK(rt_timing(ctx, ms));
             printf("frame %d kernel: %.3f ms (raycast %.3f, candidates %.3f, spatial %.3f+%.3f+%.3f, resolve %.3f)\n", frame,
                    ms[8], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6]); /* cf. the overlay of :410 */
+        }
+        if (denoise >= 0)
+        {
+            float dms[5];
+            CK(rt_denoise_timing(ctx, dms));
+            printf("frame %d denoise: %.3f ms (guide %.3f, prep %.3f, %d iterations %.3f)\n", frame, dms[4], dms[0], dms[1], denoise, dms[2] + dms[3]);
         }
     }
     uint64_t rays = 0, shaded = 0;
@@ -660,7 +677,7 @@ int main(int argc, char** argv)
     if (!pfm.empty())
     {
         std::vector<float> acc((size_t)W * H * 4);
-        CK(rt_download(ctx, RT_BUF_ACCUMULATION, acc.data(), acc.size() * 4));
+        CK(rt_download(ctx, denoise >= 0 ? (int)RT_BUF_DENOISED : (int)RT_BUF_ACCUMULATION, acc.data(), acc.size() * 4));
         FILE* f = fopen(pfm.c_str(), "wb");
         fprintf(f, "PF\n%d %d\n-1.0\n", W, H);
         for (size_t i = 0; i < (size_t)W * H; ++i)

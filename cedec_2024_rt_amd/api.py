@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(HERE, "librestir_rt.so")
 RT_RES_0, RT_RES_1, RT_RES_TEMPORAL = 0, 1, 2
 RT_RES_PHYS = 16
 RT_BUF_VISIBILITY, RT_BUF_RES_0, RT_BUF_RES_1, RT_BUF_RES_TEMPORAL, RT_BUF_ACCUMULATION, RT_BUF_PIXELS = range(6)
+RT_BUF_DENOISED, RT_BUF_DENOISE_GUIDE = 6, 7  # include/restir_rt_internal.h: written by rt_denoise, download only
 
 # include/restir_rt.h: the reference-facing boundary (what the stub of INTEGRATION.md section 2 binds)
 PUBLIC_EXPORTS = [
@@ -30,7 +31,7 @@ PUBLIC_EXPORTS = [
 ]
 # include/restir_rt_internal.h: what the strip driver, the measurement tools and the parity tests use beyond it
 INTERNAL_EXPORTS = [
-    "rt_set_stream_own", "rt_camera_pose", "rt_path_trace_rays", "rt_scene_update", "rt_frame_stage", "rt_frame_stage_input",
+    "rt_set_stream_own", "rt_camera_pose", "rt_path_trace_rays", "rt_scene_update", "rt_denoise", "rt_denoise_timing", "rt_frame_stage", "rt_frame_stage_input",
     "rt_frame_stage_begin", "rt_frame_stage_run", "rt_frame_stage_run_part", "rt_frame_stage_fork", "rt_frame_stage_run_async",
     "rt_frame_stage_run_ranges", "rt_frame_stage_end", "rt_frame_stage_output", "rt_halo_bytes", "rt_halo_pack",
     "rt_halo_unpack", "rt_halo_bitmap_words", "rt_halo_flags_bytes", "rt_halo_flags_pack", "rt_halo_flags_unpack",
@@ -93,6 +94,8 @@ def load_library(exp=False, path=None):
     L.rt_scene_set.argtypes = [vp, vp, C.c_uint32]
     L.rt_scene_info.argtypes = [vp, vp, vp, vp]
     L.rt_scene_update.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.rt_denoise.argtypes = [vp, vp]
+    L.rt_denoise_timing.argtypes = [vp, vp]
     L.rt_camera_lookat.argtypes = [vp, vp, vp, vp, cf]
     L.rt_camera_set.argtypes = [vp, vp, vp]
     L.rt_camera_get.argtypes = [vp, vp]
@@ -342,7 +345,11 @@ def _p(a):
 _BUF_DTYPE = {
     RT_BUF_VISIBILITY: VISIBILITY, RT_BUF_RES_0: RESERVOIR, RT_BUF_RES_1: RESERVOIR,
     RT_BUF_RES_TEMPORAL: RESERVOIR, RT_BUF_ACCUMULATION: np.dtype(("<f4", 4)), RT_BUF_PIXELS: np.dtype(("u1", 4)),
+    RT_BUF_DENOISED: np.dtype(("<f4", 4)), RT_BUF_DENOISE_GUIDE: VISIBILITY,
 }
+# rt_denoise_params (include/restir_rt_internal.h)
+DENOISE_PARAMS = np.dtype([("iterations", "<i4"), ("sigma_luminance", "<f4"), ("sigma_plane", "<f4"), ("normal_power_log2", "<i4"),
+                           ("variance_radius", "<i4")])
 
 
 class Renderer:
@@ -513,6 +520,25 @@ class Renderer:
         px = self.download(RT_BUF_PIXELS).view(np.uint8).reshape(self.local_rows, self.W, 4)
         r0 = self.rows[0] - self.local_row0
         return px[r0:r0 + self.rows[1] - self.rows[0]].copy()
+
+    def denoise(self, iterations=5, sigma_luminance=4.0, sigma_plane=1.0, normal_power_log2=7, variance_radius=3, hdr=False):
+        """rt_denoise: the a-trous filter of csrc/denoise_math.h over the accumulation buffer as it stands, guided by the primary hits
+        of the current camera (whole-frame contexts). Returns the tone-mapped image as (H, W, 4) uint8 in storage order (what
+        rt_denoise wrote into RT_BUF_PIXELS), or with hdr=True the denoised HDR buffer as (H, W, 4) float32 (RT_BUF_DENOISED)."""
+        p = np.zeros(1, dtype=DENOISE_PARAMS)
+        p["iterations"], p["sigma_luminance"], p["sigma_plane"] = int(iterations), float(sigma_luminance), float(sigma_plane)
+        p["normal_power_log2"], p["variance_radius"] = int(normal_power_log2), int(variance_radius)
+        self._ck(self.L.rt_denoise(self.h, _p(p)))
+        if hdr:
+            return self.download(RT_BUF_DENOISED).reshape(self.local_rows, self.W, 4)
+        return self.download(RT_BUF_PIXELS).view(np.uint8).reshape(self.local_rows, self.W, 4)
+
+    def denoise_timing(self):
+        """device ms of the last rt_denoise run with timing_enable(True): guide, prep (demodulation + variance), the levels before
+        the last, the last level (fused output), whole call"""
+        ms = np.zeros(5, dtype=np.float32)
+        self._ck(self.L.rt_denoise_timing(self.h, _p(ms)))
+        return dict(zip(["guide", "prep", "levels", "last_level", "total"], [float(v) for v in ms]))
 
     def path_trace_rays(self):
         a = C.c_uint64()

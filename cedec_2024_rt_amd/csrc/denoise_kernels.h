@@ -1,0 +1,270 @@
+/*
+ * denoise_kernels.h — the gfx950 kernels of rt_denoise (included once, by restir_rt.hip, after frame_kernels.h).
+ *
+ * Whole-frame contexts only (lrow0 = 0): buffer index = row * W + x. All arithmetic is denoise_math.h's; the loops below are
+ * what tests/denoise_ref.py restates on the CPU (tap order dy outer, dx inner).
+ *
+ *   k_denoise_guide   one primary ray per pixel (k_raycast's ray and closest-hit walk, tile order of rt_tuning key 0):
+ *                     gx = {x_p, f_p}, gn = {n_p, guide word}, and the rt_visibility record of the hit
+ *   k_denoise_demod   col = {e, 0} for participating pixels, {0, 0, 0, -1} for the others
+ *   k_denoise_var     col' = {e, var}: moments over the (2R+1)^2 window at step 1
+ *   k_denoise_iter    one a-trous level at step s (rt_tuning key 28 = 0: per-lane gathers, tiles in XCD bands as the spatial pass)
+ *   k_denoise_iter_lds the same level over 16 x 16 blocks of one residue lattice {p = r mod s} staged in LDS with a 2-point apron
+ *                     (key 28 = 1: 20 x 20 records of 48 B whatever the step)
+ *   FINAL forms of the level (and k_denoise_output for 0 iterations): HDR value + RGBA8 (tone_map_rgba8)
+ */
+#pragma once
+#include "denoise_math.h"
+
+/* rt_tuning key 28 default: the residue lattice in LDS (1), 1.13 against 1.19 ms of filter at 5 iterations, 1080p */
+#ifndef DN_LAYOUT_DEFAULT
+#define DN_LAYOUT_DEFAULT 1
+#endif
+
+struct DnParams
+{
+    int iterations;
+    float sigma_l, sigma_x;
+    int normal_power_log2, variance_radius;
+};
+
+/* ------------------------------------------------------------------ guide */
+template <bool WS>
+__global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_RAYCAST_WS_WAVES : RT_RAYCAST_WAVES) void k_denoise_guide(SceneView S, FrameParams P, float4* __restrict__ vis,
+                                                                                                         float4* __restrict__ gx, float4* __restrict__ gn)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_stack[(WS ? WIDE_LDS_ROWS_CLOSEST : WIDE_LDS_STACK) * TRACE_BLOCK];
+    int x, row;
+    if (!tile_pixel<TRACE_BLOCK>(P, x, row)) return;
+    const int yi = P.H - 1 - row;
+    const size_t li = (size_t)x + (size_t)row * P.W;
+    const f3 rd = primary_direction(P, x, yi);
+    Hit h;
+    h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.prim = -1;
+    if (WS) closest_ws<TRACE_BLOCK>(S.wide, S.bvh.tv, s_stack, P.rg_origin, rd, 0.0f, kFltMax, h);
+    else trace_wide<false, false, TRACE_BLOCK>(S.wide, s_stack, P.rg_origin, rd, 0.0f, kFltMax, h, nullptr, RT_BARY_TV(S));
+    vis[li] = make_float4(h.u, h.v, as_float(h.prim), as_float(0));
+    if (h.prim < 0)
+    {
+        gx[li] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        gn[li] = make_float4(0.0f, 0.0f, 0.0f, as_float(dn_guide_word(-1, false)));
+        return;
+    }
+    f3 v0, v1, v2, p, n;
+    load_tri(S.bvh.tv, h.prim, v0, v1, v2);
+    dn_surface(v0, v1, v2, h.u, h.v, P.eye, p, n);
+    const bool emissive = as_uint(S.trimat[2 * (size_t)h.prim].w) != 0u;
+    gx[li] = make_float4(p.x, p.y, p.z, dn_pixel_size(p, P.eye, P.rg_up, P.H));
+    gn[li] = make_float4(n.x, n.y, n.z, as_float(dn_guide_word(h.prim, emissive)));
+}
+
+RT_DEV f3 dn_albedo(const float4* __restrict__ trimat, uint32_t word)
+{
+    const float4 k = trimat[2 * (size_t)dn_tri(word)];
+    return F3(k.x, k.y, k.z);
+}
+
+/* ------------------------------------------------------------------ prep */
+__global__ __launch_bounds__(BLOCK) void k_denoise_demod(FrameParams P, const float4* __restrict__ trimat, const float4* __restrict__ accum,
+                                                         const float4* __restrict__ gn, float4* __restrict__ col)
+{
+    int x, row;
+    if (!tile_pixel(P, x, row)) return;
+    const size_t li = (size_t)x + (size_t)row * P.W;
+    const uint32_t word = as_uint(gn[li].w);
+    const float4 A = accum[li];
+    if (dn_kind(word) != DN_KIND_SURFACE || A.w == 0.0f)
+    {
+        col[li] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        return;
+    }
+    const f3 e = dn_demodulate(A, dn_albedo(trimat, word));
+    col[li] = make_float4(e.x, e.y, e.z, 0.0f);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_denoise_var(FrameParams P, DnParams D, const float4* __restrict__ gx, const float4* __restrict__ gn,
+                                                       const float4* __restrict__ cin, float4* __restrict__ cout)
+{
+    int x, row;
+    if (!tile_pixel(P, x, row)) return;
+    const size_t li = (size_t)x + (size_t)row * P.W;
+    const float4 cp = cin[li];
+    if (cp.w < 0.0f)
+    {
+        cout[li] = cp;
+        return;
+    }
+    const float4 xp4 = gx[li], np4 = gn[li];
+    const f3 xp = F3(xp4.x, xp4.y, xp4.z), np = F3(np4.x, np4.y, np4.z);
+    const int R = D.variance_radius;
+    DnMoments m = dn_moments_init();
+    for (int dy = -R; dy <= R; ++dy)
+    {
+        const int qr = row + dy;
+        if (qr < 0 || qr >= P.H) continue;
+        for (int dx = -R; dx <= R; ++dx)
+        {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= P.W) continue;
+            const size_t qi = (size_t)qx + (size_t)qr * P.W;
+            const float4 cq = cin[qi];
+            if (cq.w < 0.0f) continue;
+            const float4 xq4 = gx[qi], nq4 = gn[qi];
+            const float wn = dn_normal_weight(np, F3(nq4.x, nq4.y, nq4.z), D.normal_power_log2);
+            const float dxp = dn_plane_distance(np, xp, F3(xq4.x, xq4.y, xq4.z), D.sigma_x, 1.0f, xp4.w);
+            dn_moments_add(m, dn_variance_weight(wn, dxp), dn_luminance(cq));
+        }
+    }
+    cout[li] = make_float4(cp.x, cp.y, cp.z, dn_moments_variance(m));
+}
+
+/* ------------------------------------------------------------------ one a-trous level */
+/* TAP(dx, dy, cq, xq, nq) loads tap (dx, dy) of the 5 x 5 at the level's step and returns false if it is outside the image or
+ * does not participate; p = TAP(0, 0) participates (the caller checked) */
+template <typename Tap>
+RT_DEV float4 dn_level(const DnParams& D, float step, const float4& cp, const float4& xp4, const float4& np4, Tap tap)
+{
+    const f3 xp = F3(xp4.x, xp4.y, xp4.z), np = F3(np4.x, np4.y, np4.z);
+    DnPrefilter g = dn_prefilter_init();
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx)
+        {
+            float4 cq, xq, nq;
+            if (tap(dx, dy, cq, xq, nq)) dn_prefilter_add(g, dn_k1(dx) * dn_k1(dy), cq.w);
+        }
+    const float gvar = dn_prefilter_result(g);
+    const float lp = dn_luminance(cp);
+    DnFilter f = dn_filter_init();
+    for (int dy = -2; dy <= 2; ++dy)
+        for (int dx = -2; dx <= 2; ++dx)
+        {
+            float4 cq, xq, nq;
+            if (!tap(dx, dy, cq, xq, nq)) continue;
+            const float h = dn_h1(dx) * dn_h1(dy);
+            const float wn = dn_normal_weight(np, F3(nq.x, nq.y, nq.z), D.normal_power_log2);
+            const float dl = dn_luminance_distance(lp, dn_luminance(cq), D.sigma_l, gvar);
+            const float dxp = dn_plane_distance(np, xp, F3(xq.x, xq.y, xq.z), D.sigma_x, step, xp4.w);
+            dn_filter_add(f, dn_tap_weight(h, wn, dl, dxp), cq);
+        }
+    return dn_filter_result(f);
+}
+/* a non-participating pixel's output: its accumulation value as it is */
+template <bool FINAL>
+RT_DEV void dn_store(size_t li, const float4& out, bool part, uint32_t word, const float4* __restrict__ trimat, const float4* __restrict__ accum,
+                     float4* __restrict__ cout, float4* __restrict__ hdr, uint32_t* __restrict__ pixels)
+{
+    if (!FINAL)
+    {
+        cout[li] = out;
+        return;
+    }
+    float4 v;
+    if (part)
+    {
+        const float4 r = dn_remodulate(out, dn_albedo(trimat, word));
+        v = make_float4(r.x, r.y, r.z, r.w);
+    }
+    else v = accum[li];
+    hdr[li] = v;
+    pixels[li] = tone_map_rgba8(v);
+}
+
+template <bool FINAL>
+__global__ __launch_bounds__(BLOCK) void k_denoise_iter(FrameParams P, DnParams D, int step, const float4* __restrict__ trimat,
+                                                        const float4* __restrict__ accum, const float4* __restrict__ gx, const float4* __restrict__ gn,
+                                                        const float4* __restrict__ cin, float4* __restrict__ cout, float4* __restrict__ hdr,
+                                                        uint32_t* __restrict__ pixels)
+{
+    int x, row;
+    if (!tile_pixel(P, x, row)) return;
+    const size_t li = (size_t)x + (size_t)row * P.W;
+    const float4 cp = cin[li];
+    const float4 np4 = gn[li];
+    const bool part = cp.w >= 0.0f;
+    float4 out = cp;
+    if (part)
+    {
+        const int W = P.W, H = P.H;
+        auto tap = [&](int dx, int dy, float4& cq, float4& xq, float4& nq) -> bool {
+            const int qx = x + dx * step, qr = row + dy * step;
+            if (qx < 0 || qx >= W || qr < 0 || qr >= H) return false;
+            const size_t qi = (size_t)qx + (size_t)qr * W;
+            cq = cin[qi];
+            if (cq.w < 0.0f) return false;
+            xq = gx[qi];
+            nq = gn[qi];
+            return true;
+        };
+        out = dn_level(D, (float)step, cp, gx[li], np4, tap);
+    }
+    dn_store<FINAL>(li, out, part, as_uint(np4.w), trimat, accum, cout, hdr, pixels);
+}
+
+/* key 28 = 1. Workgroup b: residue r = (rx, ry) of the step's lattice, block (bx, by) of 16 x 16 lattice points; lattice point
+ * (i, j) of residue r = pixel (rx + s i, ry + s j). Every tap of a lattice point is a lattice point of the same residue, so a
+ * 20 x 20 apron of the lattice holds all of them (and the 3 x 3 of the prefilter) for any step. */
+constexpr int DN_LDS_BLOCK = 16, DN_LDS_APRON = DN_LDS_BLOCK + 4;
+template <bool FINAL>
+__global__ __launch_bounds__(DN_LDS_BLOCK * DN_LDS_BLOCK) void k_denoise_iter_lds(FrameParams P, DnParams D, int step, int nbx, int nby,
+                                                        const float4* __restrict__ trimat, const float4* __restrict__ accum,
+                                                        const float4* __restrict__ gx, const float4* __restrict__ gn,
+                                                        const float4* __restrict__ cin, float4* __restrict__ cout, float4* __restrict__ hdr,
+                                                        uint32_t* __restrict__ pixels)
+{
+    constexpr int A = DN_LDS_APRON, N = A * A;
+    __shared__ float4 s_c[N], s_x[N], s_n[N];
+    const int b = (int)blockIdx.x, per_res = nbx * nby;
+    const int res = b / per_res, rem = b - res * per_res;
+    const int ry = res / step, rx = res - ry * step;
+    const int by = rem / nbx, bx = rem - by * nbx;
+    const int i0 = bx * DN_LDS_BLOCK - 2, j0 = by * DN_LDS_BLOCK - 2; /* lattice coordinates of apron entry (0, 0) */
+    const int W = P.W, H = P.H;
+    for (int k = (int)threadIdx.x; k < N; k += DN_LDS_BLOCK * DN_LDS_BLOCK)
+    {
+        const int jj = k / A, ii = k - jj * A;
+        const int qx = rx + step * (i0 + ii), qr = ry + step * (j0 + jj);
+        if (qx >= 0 && qx < W && qr >= 0 && qr < H)
+        {
+            const size_t qi = (size_t)qx + (size_t)qr * W;
+            s_c[k] = cin[qi];
+            s_x[k] = gx[qi];
+            s_n[k] = gn[qi];
+        }
+        else s_c[k] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    }
+    __syncthreads();
+    const int ti = (int)threadIdx.x % DN_LDS_BLOCK, tj = (int)threadIdx.x / DN_LDS_BLOCK;
+    const int x = rx + step * (i0 + 2 + ti), row = ry + step * (j0 + 2 + tj);
+    if (x >= W || row >= H) return;
+    const size_t li = (size_t)x + (size_t)row * W;
+    const int c0 = (tj + 2) * A + (ti + 2);
+    const float4 cp = s_c[c0];
+    const float4 np4 = s_n[c0];
+    const bool part = cp.w >= 0.0f;
+    float4 out = cp;
+    if (part)
+    {
+        auto tap = [&](int dx, int dy, float4& cq, float4& xq, float4& nq) -> bool {
+            const int k = c0 + dy * A + dx;
+            cq = s_c[k];
+            if (cq.w < 0.0f) return false;
+            xq = s_x[k];
+            nq = s_n[k];
+            return true;
+        };
+        out = dn_level(D, (float)step, cp, s_x[c0], np4, tap);
+    }
+    dn_store<FINAL>(li, out, part, as_uint(np4.w), trimat, accum, cout, hdr, pixels);
+}
+
+/* 0 iterations: the demodulated value remodulated as it is */
+__global__ __launch_bounds__(BLOCK) void k_denoise_output(FrameParams P, const float4* __restrict__ trimat, const float4* __restrict__ accum,
+                                                          const float4* __restrict__ gn, const float4* __restrict__ col, float4* __restrict__ hdr,
+                                                          uint32_t* __restrict__ pixels)
+{
+    int x, row;
+    if (!tile_pixel(P, x, row)) return;
+    const size_t li = (size_t)x + (size_t)row * P.W;
+    const float4 cp = col[li];
+    dn_store<true>(li, cp, cp.w >= 0.0f, as_uint(gn[li].w), trimat, accum, nullptr, hdr, pixels);
+}

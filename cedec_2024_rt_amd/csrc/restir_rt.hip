@@ -40,6 +40,7 @@ static_assert(sizeof(BvhNode) == 64, "BVH node");
 #include "bvh_build_host.h"
 #include "bvh_build_device.h"
 #include "bvh_refit.h"
+#include "denoise_kernels.h"
 
 /* ======================================================================= host */
 
@@ -212,6 +213,12 @@ struct rt_ctx
     unsigned long long* d_pt_counters = nullptr;
     int pt_wavefront = 2; /* rt_tuning key 6: 0 one launch per frame, 1 wavefront, 2 auto (wavefront for 09_ris) */
     int tune_ao_layout = 0; /* rt_tuning key 27: ambient occlusion (rt_path_trace 4 / 6) 0 pixel-major, 1 ray-major (frame_kernels.h k_ao) */
+    /* rt_denoise (denoise_kernels.h), allocated at the first call: the guide (rt_visibility records, {x, f}, {n, word}), the colour
+     * records {e, var} of the two ping-pong sides, the HDR output; per-kernel events while rt_timing_enable is on */
+    float4 *d_dn_vis = nullptr, *d_dn_gx = nullptr, *d_dn_gn = nullptr, *d_dn_col[2] = {nullptr, nullptr}, *d_dn_hdr = nullptr;
+    bool dn_valid = false, dn_timed = false;
+    int tune_dn_layout = DN_LAYOUT_DEFAULT; /* rt_tuning key 28: a-trous levels 0 = per-lane gathers, 1 = residue lattice in LDS */
+    hipEvent_t dn_ev[5] = {};
     void* d_stage = nullptr;
     size_t stage_bytes = 0;
 
@@ -441,6 +448,8 @@ int rt_destroy(rt_ctx* c)
     if (c->h_visq_count) hipHostFree(c->h_visq_count);
     hipFree(c->d_walk); hipFree(c->d_wire); hipFree(c->d_wave_clock);
     for (auto& p : c->d_tile_perm) hipFree(p);
+    hipFree(c->d_dn_vis); hipFree(c->d_dn_gx); hipFree(c->d_dn_gn); hipFree(c->d_dn_col[0]); hipFree(c->d_dn_col[1]); hipFree(c->d_dn_hdr);
+    for (auto& e : c->dn_ev) if (e) hipEventDestroy(e);
     hipFree(c->d_counter); hipFree(c->d_stage); hipFree(c->d_paths[0]); hipFree(c->d_paths[1]); hipFree(c->d_pt_counters);
     if (c->ev_created) for (auto& e : c->ev) hipEventDestroy(e);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -2055,6 +2064,94 @@ int rt_path_trace_rays(rt_ctx* c, uint64_t* rays)
     return RT_OK;
 }
 
+/* ---- rt_denoise (denoise_kernels.h): guide, demodulation, variance, the a-trous levels; asynchronous on the context's stream ---- */
+int rt_denoise(rt_ctx* c, const rt_denoise_params* params)
+{
+    RT_CHECK_CTX(c);
+    if (c->row_begin != 0 || c->row_end != c->H)
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_denoise is for whole-frame contexts (rows [%d,%d) of %d)", c->row_begin, c->row_end, c->H);
+    NEED_SCENE(c);
+    rt_denoise_params d = {5, 4.0f, 1.0f, 7, 3};
+    if (params) d = *params;
+    if (d.iterations < 0 || d.iterations > 8) RT_FAIL(c, RT_ERR_ARG, "iterations %d outside 0..8", d.iterations);
+    if (!(d.sigma_luminance > 0.0f) || !(d.sigma_luminance < INFINITY)) RT_FAIL(c, RT_ERR_ARG, "sigma_luminance must be finite and > 0");
+    if (!(d.sigma_plane > 0.0f) || !(d.sigma_plane < INFINITY)) RT_FAIL(c, RT_ERR_ARG, "sigma_plane must be finite and > 0");
+    if (d.normal_power_log2 < 0 || d.normal_power_log2 > 10) RT_FAIL(c, RT_ERR_ARG, "normal_power_log2 %d outside 0..10", d.normal_power_log2);
+    if (d.variance_radius < 0 || d.variance_radius > 3) RT_FAIL(c, RT_ERR_ARG, "variance_radius %d outside 0..3", d.variance_radius);
+    if (c->n_tris > (1 << 30)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "the guide word holds triangle indices below 2^30");
+    RT_HIP(c, hipSetDevice(c->device));
+    const size_t n = local_pixels(c);
+    if (!c->d_dn_hdr)
+    {
+        float4** bufs[6] = {&c->d_dn_vis, &c->d_dn_gx, &c->d_dn_gn, &c->d_dn_col[0], &c->d_dn_col[1], &c->d_dn_hdr};
+        for (float4** b : bufs)
+            if (!*b) RT_HIP(c, hipMalloc(b, n * 16));
+    }
+    /* what may still write the accumulation buffer (or the pixels): the previous frame's resolve + tone mapping on the tail stream,
+     * the look-ahead stage 0 (waited for, not dropped: its results stay valid for the next frame). What comes after on this stream
+     * is ordered behind the launches below; the next staged frame's tail forks from this stream behind them. */
+    JOIN_TAIL(c);
+    JOIN_SPEC(c);
+    hipStream_t st = c->stream;
+    const bool timed = c->timing;
+    if (timed && !c->dn_ev[0])
+        for (auto& e : c->dn_ev) RT_HIP(c, hipEventCreate(&e));
+    if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[0], st));
+    const SceneView S = make_scene(c);
+    {
+        const FrameParams PG = make_params(c, 0, 0, K_RAYCAST);
+        if (use_ws_primary(c, trace_grid(c))) k_denoise_guide<true><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, c->d_dn_gx, c->d_dn_gn);
+        else k_denoise_guide<false><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, c->d_dn_gx, c->d_dn_gn);
+        RT_HIP(c, hipGetLastError());
+    }
+    if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[1], st));
+    const FrameParams P = make_params(c, 0, 0, K_SPATIAL);
+    const DnParams D = {d.iterations, d.sigma_luminance, d.sigma_plane, d.normal_power_log2, d.variance_radius};
+    const int g = launch_grid(c);
+    k_denoise_demod<<<g, BLOCK, 0, st>>>(P, c->d_trimat, c->d_accum, c->d_dn_gn, c->d_dn_col[1]);
+    k_denoise_var<<<g, BLOCK, 0, st>>>(P, D, c->d_dn_gx, c->d_dn_gn, c->d_dn_col[1], c->d_dn_col[0]);
+    RT_HIP(c, hipGetLastError());
+    if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[2], st));
+    if (d.iterations == 0)
+    {
+        if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[3], st));
+        k_denoise_output<<<g, BLOCK, 0, st>>>(P, c->d_trimat, c->d_accum, c->d_dn_gn, c->d_dn_col[0], c->d_dn_hdr, c->d_pixels);
+    }
+    for (int i = 0; i < d.iterations; ++i)
+    {
+        const bool last = i + 1 == d.iterations;
+        if (timed && last) RT_HIP(c, hipEventRecord(c->dn_ev[3], st));
+        const int step = 1 << i;
+        const float4* cin = c->d_dn_col[i & 1];
+        float4* cout = c->d_dn_col[(i + 1) & 1];
+        if (c->tune_dn_layout == 1)
+        {
+            const int nbx = ((c->W + step - 1) / step + DN_LDS_BLOCK - 1) / DN_LDS_BLOCK, nby = ((c->H + step - 1) / step + DN_LDS_BLOCK - 1) / DN_LDS_BLOCK;
+            const int gl = step * step * nbx * nby;
+            if (last) k_denoise_iter_lds<true><<<gl, DN_LDS_BLOCK * DN_LDS_BLOCK, 0, st>>>(P, D, step, nbx, nby, c->d_trimat, c->d_accum, c->d_dn_gx, c->d_dn_gn, cin, nullptr, c->d_dn_hdr, c->d_pixels);
+            else k_denoise_iter_lds<false><<<gl, DN_LDS_BLOCK * DN_LDS_BLOCK, 0, st>>>(P, D, step, nbx, nby, c->d_trimat, c->d_accum, c->d_dn_gx, c->d_dn_gn, cin, cout, nullptr, nullptr);
+        }
+        else if (last) k_denoise_iter<true><<<g, BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, c->d_dn_gx, c->d_dn_gn, cin, nullptr, c->d_dn_hdr, c->d_pixels);
+        else k_denoise_iter<false><<<g, BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, c->d_dn_gx, c->d_dn_gn, cin, cout, nullptr, nullptr);
+        RT_HIP(c, hipGetLastError());
+    }
+    RT_HIP(c, hipGetLastError());
+    if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[4], st));
+    c->dn_timed = timed;
+    c->dn_valid = true;
+    return RT_OK;
+}
+int rt_denoise_timing(rt_ctx* c, float ms[5])
+{
+    RT_CHECK_CTX(c);
+    if (!ms) return RT_ERR_ARG;
+    if (!c->dn_timed) RT_FAIL(c, RT_ERR_STATE, "no timed rt_denoise (rt_timing_enable + rt_denoise first)");
+    RT_HIP(c, hipEventSynchronize(c->dn_ev[4]));
+    for (int k = 0; k < 4; ++k) RT_HIP(c, hipEventElapsedTime(&ms[k], c->dn_ev[k], c->dn_ev[k + 1]));
+    RT_HIP(c, hipEventElapsedTime(&ms[4], c->dn_ev[0], c->dn_ev[4]));
+    return RT_OK;
+}
+
 int rt_timing_enable(rt_ctx* c, int on)
 {
     RT_CHECK_CTX(c);
@@ -2426,6 +2523,12 @@ int rt_download(rt_ctx* c, int buf, void* dst, size_t bytes)
         case RT_BUF_PIXELS:
             if (bytes != n * 4) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 4);
             RT_HIP(c, hipMemcpyAsync(dst, c->d_pixels, bytes, hipMemcpyDeviceToHost, c->stream));
+            break;
+        case RT_BUF_DENOISED:
+        case RT_BUF_DENOISE_GUIDE:
+            if (!c->dn_valid) RT_FAIL(c, RT_ERR_STATE, "buffer %d is written by rt_denoise, which has not run on this context", buf);
+            if (bytes != n * 16) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 16);
+            RT_HIP(c, hipMemcpyAsync(dst, buf == RT_BUF_DENOISED ? c->d_dn_hdr : c->d_dn_vis, bytes, hipMemcpyDeviceToHost, c->stream));
             break;
         case RT_BUF_RES_0:
         case RT_BUF_RES_1:
@@ -3219,6 +3322,7 @@ int rt_tuning(rt_ctx* c, int key, int value)
     else if (key == 25 && value >= -1 && value <= 1) c->tune_fuse_raycast = value;
     else if (key == 26 && (value == 0 || value == 1)) c->tune_mark_split = value;
     else if (key == 27 && (value == 0 || value == 1)) c->tune_ao_layout = value;
+    else if (key == 28 && (value == 0 || value == 1)) c->tune_dn_layout = value;
     else if (key == 22 && value >= -1 && value <= 1) { c->tune_spec_free = value; c->spec_valid = false; c->spec_gen_valid = false; }
     else RT_FAIL(c, RT_ERR_ARG, "bad tuning key/value %d/%d", key, value);
     return RT_OK;
@@ -3254,6 +3358,7 @@ int rt_tuning_get(rt_ctx* c, int key, int* value)
         case 25: *value = c->tune_fuse_raycast; break;
         case 26: *value = c->tune_mark_split; break;
         case 27: *value = c->tune_ao_layout; break;
+        case 28: *value = c->tune_dn_layout; break;
         default: RT_FAIL(c, RT_ERR_ARG, "bad tuning key %d", key);
     }
     return RT_OK;

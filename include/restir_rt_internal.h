@@ -39,6 +39,34 @@ int rt_path_trace_rays(rt_ctx* ctx, uint64_t* rays); /* raytrace() calls of the 
  * (RT_ERR_STATE) after an update until the next rt_scene_set. */
 int rt_scene_update(rt_ctx* ctx, const rt_triangle* triangles, uint32_t first, uint32_t count);
 
+/* ---- denoiser: a spatial edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with the variance-guided luminance weight of
+ * SVGF (Schied et al. 2017) over the accumulation buffer of a whole-frame context (csrc/denoise_math.h pins the arithmetic) ---- */
+typedef struct
+{
+    int32_t iterations;        /* 0..8, default 5 (steps 1, 2, 4, 8, 16) */
+    float sigma_luminance;     /* > 0, default 4 */
+    float sigma_plane;         /* > 0, default 1 */
+    int32_t normal_power_log2; /* 0..10, default 7 (n.n' ^ 128) */
+    int32_t variance_radius;   /* 0..3, default 3 (7 x 7) */
+} rt_denoise_params;
+enum
+{
+    RT_BUF_DENOISED = 6,      /* float4[W*H], accumulation layout: the denoised HDR image; download only */
+    RT_BUF_DENOISE_GUIDE = 7  /* rt_visibility[W*H] of the guide's primary hits; download only */
+};
+/* Filters the accumulation buffer as it stands (after the frames enqueued before the call) with guides from one primary ray per
+ * pixel of the current camera, writes RT_BUF_DENOISED and its tone-mapped image into RT_BUF_PIXELS. Pixels that are sky,
+ * emissive or have accumulation w == 0 keep their accumulation value. Asynchronous on the context's stream: it waits for the
+ * streams that may still write the accumulation buffer and whatever is enqueued after it is ordered behind it; it changes neither
+ * the accumulation buffer, the reservoirs, the state epoch nor the look-ahead work. params NULL = defaults. No scene or camera,
+ * or a download of the two buffers before the first call: RT_ERR_STATE; strip contexts: RT_ERR_UNSUPPORTED; a parameter out of
+ * range: RT_ERR_ARG. rt_tuning key 28 picks the layout of the a-trous levels (0 per-lane gathers, 1 residue lattice in LDS): the
+ * same results. */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params);
+/* device time of the last rt_denoise run while rt_timing_enable was on: ms[0] guide, [1] demodulation + variance, [2] the levels
+ * before the last, [3] the last level (fused output), [4] the whole call */
+int rt_denoise_timing(rt_ctx* ctx, float ms[5]);
+
 /* ---- rt_frame in stages ---- */
 /* The same frame cut into stages for strip contexts (multi-GPU): stage 0 = [clear,] raycast,
  * generate_candidate(+temporal); stage k in 1..passes = spatial pass k-1; stage passes+1 = resolve,

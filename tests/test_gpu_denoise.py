@@ -1,0 +1,270 @@
+"""rt_denoise (include/restir_rt_internal.h, csrc/denoise_kernels.h) on the GPU.
+
+* the guide's primary hits (RT_BUF_DENOISE_GUIDE) == rt_raycast's RT_BUF_VISIBILITY, 1920 x 1080 and 333 x 187;
+* RT_BUF_DENOISED == the CPU restatement (tests/denoise_ref.py) bit for bit: the bench stand-in at 1920 x 1080, 333 x 187 (partial
+  tiles) and 64 x 36; 0, 1, 5 and 8 iterations; default and other parameters; both layouts of rt_tuning key 28; input from rt_frame,
+  rt_path_trace 7 and 9, and an uploaded accumulation with w = 0 pixels;
+* rt_tone_mapping of the uploaded RT_BUF_DENOISED == the pixels rt_denoise wrote;
+* no side effects: six frames with rt_denoise after each and no rt_sync in between leave the accumulation, the three reservoir
+  buffers and the state epoch as the same frames without it, and the last denoised image equals a fully synchronised run;
+* error codes; restir_app --denoise == the Renderer, and its refusals.
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import denoise_ref
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+APP = os.path.join(ROOT, "app", "restir_app")
+RT_OK, RT_ERR_ARG, RT_ERR_STATE, RT_ERR_UNSUPPORTED = 0, 1, 3, 5
+ROOM_EYE, ROOM_AT = (0.5, 2.5, 6.0), (0.0, 1.5, -1.0)
+OTHER = dict(sigma_luminance=2.5, sigma_plane=0.5, normal_power_log2=3, variance_radius=1)
+
+
+@pytest.fixture(scope="module")
+def api():
+    from cedec_2024_rt_amd import api as _api
+    return _api
+
+
+@pytest.fixture(scope="module")
+def blocks():
+    from cedec_2024_rt_amd import scenes
+    return scenes.make_blocks_restir(), scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT
+
+
+@pytest.fixture(scope="module")
+def room():
+    from cedec_2024_rt_amd import scenes
+    return scenes.make_quad_room(), ROOM_EYE, ROOM_AT
+
+
+def _eq_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+def _ndiff(a, b):
+    a, b = np.ascontiguousarray(a).reshape(-1, 4).view(np.uint32), np.ascontiguousarray(b).reshape(-1, 4).view(np.uint32)
+    return int((a != b).any(axis=1).sum())
+
+
+def _renderer(api, scene, W, H, **opt):
+    from cedec_2024_rt_amd.types import bench_options
+
+    tris, eye, at = scene
+    r = api.Renderer(W, H)
+    r.set_scene(tris)
+    r.lookat(eye, at)
+    r.set_options(bench_options(**opt))
+    return r
+
+
+def _check(api, r, scene, params, layouts=(0, 1)):
+    """rt_denoise of the accumulation as it stands == the CPU restatement, for each layout; the pixels == rt_tone_mapping of it"""
+    tris, eye, _ = scene
+    r.sync()
+    acc = r.download(api.RT_BUF_ACCUMULATION)
+    rg_up = r.raygen()["up"][0]
+    ref = None
+    for lay in layouts:
+        r.tuning(28, lay)
+        hdr = r.denoise(hdr=True, **params).reshape(-1, 4)
+        if ref is None:
+            ref = denoise_ref.denoise(r.W, r.H, tris, r.download(api.RT_BUF_DENOISE_GUIDE), eye, rg_up, acc, **params)
+        assert _eq_bits(hdr, ref), f"layout {lay} {params}: {_ndiff(hdr, ref)} pixels differ from the CPU restatement"
+        assert _eq_bits(r.download(api.RT_BUF_ACCUMULATION), acc), "rt_denoise changed the accumulation buffer"
+    return acc, ref
+
+
+def _tone_map_check(api, r, acc, hdr):
+    px = r.download(api.RT_BUF_PIXELS)
+    r.upload(api.RT_BUF_ACCUMULATION, hdr)
+    r.tone_mapping()
+    assert _eq_bits(r.download(api.RT_BUF_PIXELS), px), "rt_tone_mapping(RT_BUF_DENOISED) != rt_denoise's pixels"
+    r.upload(api.RT_BUF_ACCUMULATION, acc)
+
+
+@pytest.mark.parametrize("W,H", [(1920, 1080), (333, 187)])
+def test_guide_hits_equal_raycast(api, blocks, W, H):
+    r = _renderer(api, blocks, W, H)
+    r.raycast()
+    vis = r.download(api.RT_BUF_VISIBILITY)
+    r.clear()
+    r.denoise(iterations=1)
+    guide = r.download(api.RT_BUF_DENOISE_GUIDE)
+    assert _eq_bits(guide, vis), f"{int((guide.view(np.uint32).reshape(-1, 4) != vis.view(np.uint32).reshape(-1, 4)).any(axis=1).sum())} hits differ"
+    r.close()
+
+
+def test_restir_1080p_equals_cpu(api, blocks):
+    r = _renderer(api, blocks, 1920, 1080, accumulate=1)
+    for f in range(1, 4):
+        r.frame(f)
+    acc, hdr = _check(api, r, blocks, {})
+    _tone_map_check(api, r, acc, hdr)
+    r.close()
+
+
+def test_restir_partial_tiles_equals_cpu(api, blocks):
+    r = _renderer(api, blocks, 333, 187, accumulate=1)
+    for f in range(1, 3):
+        r.frame(f)
+    for it in (0, 1, 5, 8):
+        acc, hdr = _check(api, r, blocks, dict(iterations=it))
+        acc, hdr = _check(api, r, blocks, dict(iterations=it, **OTHER))
+    _tone_map_check(api, r, acc, hdr)
+    r.close()
+
+
+@pytest.mark.parametrize("example", [7, 9])
+def test_path_trace_input_equals_cpu(api, room, example):
+    r = _renderer(api, room, 64, 36, accumulate=1)
+    r.clear()
+    for f in range(1, 3):
+        r.path_trace(example, f)
+    for it in (0, 1, 5, 8):
+        _check(api, r, room, dict(iterations=it))
+    _check(api, r, room, dict(iterations=5, **OTHER))
+    r.close()
+
+
+def test_uploaded_accumulation_with_empty_pixels(api, blocks):
+    W, H = 333, 187
+    r = _renderer(api, blocks, W, H)
+    rng = np.random.default_rng(9)
+    acc = rng.exponential(1.0, size=(W * H, 4)).astype(np.float32)
+    acc[:, 3] = rng.integers(1, 5, size=W * H).astype(np.float32)
+    acc[rng.random(W * H) < 0.2] = 0.0  # w == 0 (and 0 / 0 in the tone mapping): passed through, never a tap
+    r.upload(api.RT_BUF_ACCUMULATION, acc)
+    _, hdr = _check(api, r, blocks, {})
+    empty = acc[:, 3] == 0
+    assert _eq_bits(hdr[empty], acc[empty])
+    assert np.isfinite(hdr[~empty]).all()
+    r.close()
+
+
+def _epoch(r):
+    e = C.c_uint64()
+    assert r.L.rt_state_epoch(r.h, C.byref(e)) == RT_OK
+    return e.value
+
+
+def _state(api, r):
+    r.sync()
+    return [r.download(b) for b in (api.RT_BUF_ACCUMULATION, api.RT_BUF_RES_0, api.RT_BUF_RES_1, api.RT_BUF_RES_TEMPORAL)] + [_epoch(r)]
+
+
+def test_no_side_effects_on_the_frame_sequence(api, blocks):
+    """rt_denoise between rt_frame calls, nothing synchronised: the frames' own state is what it is without the denoiser (the
+    resolve on the tail stream and the look-ahead stage 0 keep running as usual), and the denoised image is a synchronised run's."""
+    W, H, frames = 333, 187, 6
+    plain = _renderer(api, blocks, W, H, accumulate=1)
+    for f in range(1, frames + 1):
+        plain.frame(f)
+    want = _state(api, plain)
+    plain.close()
+
+    r = _renderer(api, blocks, W, H, accumulate=1)
+    for f in range(1, frames + 1):
+        r.frame(f)
+        assert r.L.rt_denoise(r.h, None) == RT_OK, r.L.rt_last_error(r.h)
+    got = _state(api, r)
+    hdr = r.download(api.RT_BUF_DENOISED)
+    px = r.download(api.RT_BUF_PIXELS)
+    r.close()
+    for name, a, b in zip(("accumulation", "RES_0", "RES_1", "RES_TEMPORAL", "epoch"), got, want):
+        assert (a == b) if name == "epoch" else _eq_bits(a, b), name
+
+    s = _renderer(api, blocks, W, H, accumulate=1)
+    for f in range(1, frames + 1):
+        s.frame(f)
+        s.sync()
+        h = s.denoise(hdr=True)
+        s.sync()
+    assert _eq_bits(h.reshape(-1, 4), hdr)
+    assert _eq_bits(s.download(api.RT_BUF_PIXELS), px)
+    s.close()
+
+
+def test_error_codes(api, blocks, room):
+    W, H = 64, 36
+    r = api.Renderer(W, H)
+    buf = np.zeros(W * H * 4, np.float32)
+    assert r.L.rt_download(r.h, api.RT_BUF_DENOISED, buf.ctypes.data, buf.nbytes) == RT_ERR_STATE
+    assert r.L.rt_download(r.h, api.RT_BUF_DENOISE_GUIDE, buf.ctypes.data, buf.nbytes) == RT_ERR_STATE
+    assert r.L.rt_denoise(r.h, None) == RT_ERR_STATE  # no scene
+    r.set_scene(room[0])
+    assert r.L.rt_denoise(r.h, None) == RT_ERR_STATE  # no camera
+    r.lookat(room[1], room[2])
+    bad = [dict(iterations=9), dict(iterations=-1), dict(sigma_luminance=0.0), dict(sigma_luminance=float("nan")),
+           dict(sigma_plane=-1.0), dict(sigma_plane=float("inf")), dict(normal_power_log2=11), dict(normal_power_log2=-1),
+           dict(variance_radius=4), dict(variance_radius=-1)]
+    for b in bad:
+        p = np.zeros(1, dtype=api.DENOISE_PARAMS)
+        p[0] = (5, 4.0, 1.0, 7, 3)
+        for k, v in b.items():
+            p[k] = v
+        assert r.L.rt_denoise(r.h, p.ctypes.data) == RT_ERR_ARG, b
+    assert r.L.rt_download(r.h, api.RT_BUF_DENOISED, buf.ctypes.data, buf.nbytes) == RT_ERR_STATE
+    assert r.L.rt_denoise(r.h, None) == RT_OK
+    assert r.L.rt_download(r.h, api.RT_BUF_DENOISED, buf.ctypes.data, buf.nbytes) == RT_OK
+    assert r.L.rt_download(r.h, api.RT_BUF_DENOISED, buf.ctypes.data, buf.nbytes - 16) == RT_ERR_ARG
+    assert r.L.rt_upload(r.h, api.RT_BUF_DENOISED, buf.ctypes.data, buf.nbytes) == RT_ERR_ARG  # download only
+    assert r.L.rt_tuning(r.h, 28, 2) == RT_ERR_ARG
+    r.close()
+    s = api.Renderer(W, H, rows=(0, H // 2), halo=8)
+    s.set_scene(room[0])
+    s.lookat(room[1], room[2])
+    assert s.L.rt_denoise(s.h, None) == RT_ERR_UNSUPPORTED
+    s.close()
+
+
+@pytest.mark.parametrize("example", [10, 7])
+def test_restir_app_denoise_equals_the_renderer(tmp_path, api, room, example):
+    from cedec_2024_rt_amd.types import bench_options
+
+    tris, eye, at = room
+    path = os.path.join(str(tmp_path), "room.tris")
+    tris.tofile(path)
+    out, pfm = os.path.join(str(tmp_path), "out.raw"), os.path.join(str(tmp_path), "out.pfm")
+    W, H = 96, 64
+    cmd = [APP, "--example", str(example), "--tris", path, "--size", str(W), str(H), "--eye", *map(str, eye), "--lookat", *map(str, at),
+           "--accumulate", "1", "--frames", "3", "--denoise", "3", "--rgba", out, "--pfm", pfm]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert p.stdout.count("denoise:") == 3, p.stdout
+    app_px = np.fromfile(out, np.uint8).reshape(H, W, 4)
+
+    r = api.Renderer(W, H)
+    r.set_scene(tris)
+    r.lookat(eye, at)
+    r.set_options(bench_options(accumulate=1))
+    r.clear()
+    for f in range(1, 4):
+        if example == 10:
+            r.frame(f)
+        else:
+            r.path_trace(example, f)
+            r.tone_mapping()
+        px = r.denoise(iterations=3)
+        hdr = r.download(api.RT_BUF_DENOISED)
+    r.close()
+    assert np.array_equal(app_px, px), f"{int((app_px != px).any(axis=2).sum())} pixels differ"
+    with open(pfm, "rb") as f:
+        body = f.read().split(b"\n", 3)[3]
+    want = (hdr[:, :3] / hdr[:, 3:4]).astype(np.float32)
+    assert _eq_bits(np.frombuffer(body, np.float32).reshape(-1, 3), want)
+
+
+def test_restir_app_denoise_refusals(tmp_path, room):
+    path = os.path.join(str(tmp_path), "room.tris")
+    room[0].tofile(path)
+    for extra in (["--example", "6"], ["--example", "4"], ["--ranks", "2"]):
+        p = subprocess.run([APP, "--tris", path, "--size", "64", "36", "--denoise", "2", *extra], capture_output=True, text=True, timeout=120)
+        assert p.returncode == 2 and "--denoise" in p.stderr, (extra, p.stdout + p.stderr)

@@ -30,6 +30,13 @@ BUDGET = [
     (r"^k_halo_mark<", 0, 8),
     (r"^k_ao<0>", 0, 7),   # r07 ambient occlusion, pixel-major (default): 8 wavefronts per SIMD (RT_AO_WAVES=8) measured no faster
     (r"^k_ao<1>", 0, 6),   # ray-major (rt_tuning 27 = 1)
+    (r"^k_denoise_guide<false>", 0, 8),  # r09 rt_denoise: primary rays of the guide (k_raycast's walk)
+    (r"^k_denoise_guide<true>", 0, 6),
+    (r"^k_denoise_demod", 0, 8),
+    (r"^k_denoise_var", 0, 8),
+    (r"^k_denoise_iter<", 0, 8),         # a-trous level, per-lane gathers (rt_tuning 28 = 0)
+    (r"^k_denoise_iter_lds<", 0, 8),     # residue lattice in LDS (rt_tuning 28 = 1), 19 200 B per workgroup
+    (r"^k_denoise_output", 0, 8),
 ]
 
 
