@@ -10,7 +10,7 @@
  *              [--shadowed 0|1] [--visreuse 0|1] [--accumulate 0|1] [--by-kernel]
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
- *              [--move-lights dx dy dz] [--denoise N]
+ *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
  * image rows (cedec_2024_rt_amd/csrc/host_path.h: brute-force closest hit, 64 ambient-occlusion rays per pixel,
@@ -19,6 +19,9 @@
  * --rgba writes the W*H RGBA8 bytes in the reference's storage order (what its pixel buffer holds).
  * --denoise N (--example 10, 7, 8, 9; one GPU): after every frame rt_denoise with N a-trous iterations (0..8) and the default
  * parameters; --ppm / --png / --rgba then write its tone-mapped image and --pfm its HDR image (RT_BUF_DENOISED).
+ * --denoise-temporal (with --denoise N): rt_denoise_temporal (default alphas) in place of rt_denoise, one call per frame.
+ * --orbit dx dy (one GPU): before every frame from the second on, rt_camera_orbit(dx, dy) (a left-button drag); with
+ * --accumulate 1 that frame starts a new accumulation, as the example clears on a camera update.
  * --move-lights dx dy dz (--example 10, also with --ranks): before every frame from the second on, the emissive triangles move
  * by (dx, dy, dz) and rt_scene_update refits the scene (the span from the lowest to the highest emissive index); the call's wall
  * time is printed per frame, and with --accumulate 1 the frame starts a new accumulation.
@@ -421,6 +424,8 @@ int main(int argc, char** argv)
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
+    bool denoise_temporal = false, orbit = false;
+    float orbit_d[2] = {0.0f, 0.0f};
     LightMove mv;
     rt_options opt;
     memset(&opt, 0, sizeof(opt));
@@ -463,12 +468,16 @@ int main(int argc, char** argv)
         else if (a == "--rgba") rgba = argv[++i];
         else if (a == "--threads") threads = atoi(argv[++i]);
         else if (a == "--denoise") denoise = atoi(argv[++i]);
+        else if (a == "--denoise-temporal") denoise_temporal = true;
+        else if (a == "--orbit") { orbit_d[0] = f(1); orbit_d[1] = f(2); i += 2; orbit = true; }
         else if (a == "--move-lights") { mv.d[0] = f(1); mv.d[1] = f(2); mv.d[2] = f(3); i += 3; mv.on = true; }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     if (denoise >= 0 && (example == 4 || example == 6)) { fprintf(stderr, "--denoise applies to --example 10, 7, 8 and 9\n"); return 2; }
     if (denoise >= 0 && ranks > 1) { fprintf(stderr, "--denoise runs on one GPU (whole-frame contexts), not with --ranks\n"); return 2; }
     if (denoise > 8) { fprintf(stderr, "--denoise: 0..8 iterations\n"); return 2; }
+    if (denoise_temporal && denoise < 0) { fprintf(stderr, "--denoise-temporal needs --denoise N\n"); return 2; }
+    if (orbit && (ranks > 1 || example == 4 || example == 6)) { fprintf(stderr, "--orbit applies to one GPU and --example 10, 7, 8 and 9\n"); return 2; }
     std::vector<rt_triangle> triangles = !obj.empty() ? load_obj(obj) : load_tris(tris_path);
     if (triangles.empty()) { fprintf(stderr, "no triangles (use --obj or --tris)\n"); return 2; }
     if (!dump.empty())
@@ -590,9 +599,17 @@ int main(int argc, char** argv)
             printf("frame %d scene update: %.3f ms (%u triangles)\n", frame, ms, mv.count);
             clear = opt.accumulate ? 1 : 0;
         }
+        if (orbit && frame >= 2)
+        {
+            int updated = 0;
+            CK(rt_camera_orbit(ctx, orbit_d[0], orbit_d[1]));
+            CK(rt_camera_updated(ctx, &updated));
+            if (updated && opt.accumulate) clear = 1; /* 10_restir_di.cpp:257-267 */
+        }
         if (example != 10)
         {
             /* examples/07_pt/07_pt.cpp:206-222: path_trace, then tone_mapping */
+            if (clear) CK(rt_clear(ctx));
             CK(rt_path_trace(ctx, example, frame));
             CK(rt_tone_mapping(ctx));
         }
@@ -617,7 +634,8 @@ int main(int argc, char** argv)
         if (denoise >= 0)
         {
             rt_denoise_params dp = {denoise, 4.0f, 1.0f, 7, 3};
-            CK(rt_denoise(ctx, &dp));
+            if (denoise_temporal) CK(rt_denoise_temporal(ctx, &dp, nullptr));
+            else CK(rt_denoise(ctx, &dp));
         }
         CK(rt_sync(ctx));
         if (!by_kernel && example == 10)
@@ -627,7 +645,14 @@ int main(int argc, char** argv)
             printf("frame %d kernel: %.3f ms (raycast %.3f, candidates %.3f, spatial %.3f+%.3f+%.3f, resolve %.3f)\n", frame,
                    ms[8], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6]); /* cf. the overlay of :410 */
         }
-        if (denoise >= 0)
+        if (denoise_temporal)
+        {
+            float tms[6];
+            CK(rt_denoise_temporal_timing(ctx, tms));
+            printf("frame %d denoise: %.3f ms (guide %.3f, reprojection %.3f, variance %.3f, %d iterations %.3f)\n", frame, tms[5], tms[0], tms[1],
+                   tms[2], denoise, tms[3] + tms[4]);
+        }
+        else if (denoise >= 0)
         {
             float dms[5];
             CK(rt_denoise_timing(ctx, dms));

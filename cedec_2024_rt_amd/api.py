@@ -19,6 +19,7 @@ RT_RES_0, RT_RES_1, RT_RES_TEMPORAL = 0, 1, 2
 RT_RES_PHYS = 16
 RT_BUF_VISIBILITY, RT_BUF_RES_0, RT_BUF_RES_1, RT_BUF_RES_TEMPORAL, RT_BUF_ACCUMULATION, RT_BUF_PIXELS = range(6)
 RT_BUF_DENOISED, RT_BUF_DENOISE_GUIDE = 6, 7  # include/restir_rt_internal.h: written by rt_denoise, download only
+RT_BUF_DENOISE_HISTORY = 8  # written by rt_denoise_temporal: {mu1, mu2, history length, 0} per pixel, download only
 
 # include/restir_rt.h: the reference-facing boundary (what the stub of INTEGRATION.md section 2 binds)
 PUBLIC_EXPORTS = [
@@ -31,7 +32,8 @@ PUBLIC_EXPORTS = [
 ]
 # include/restir_rt_internal.h: what the strip driver, the measurement tools and the parity tests use beyond it
 INTERNAL_EXPORTS = [
-    "rt_set_stream_own", "rt_camera_pose", "rt_path_trace_rays", "rt_scene_update", "rt_denoise", "rt_denoise_timing", "rt_frame_stage", "rt_frame_stage_input",
+    "rt_set_stream_own", "rt_camera_pose", "rt_path_trace_rays", "rt_scene_update", "rt_denoise", "rt_denoise_timing", "rt_denoise_temporal",
+    "rt_denoise_temporal_reset", "rt_denoise_temporal_timing", "rt_frame_stage", "rt_frame_stage_input",
     "rt_frame_stage_begin", "rt_frame_stage_run", "rt_frame_stage_run_part", "rt_frame_stage_fork", "rt_frame_stage_run_async",
     "rt_frame_stage_run_ranges", "rt_frame_stage_end", "rt_frame_stage_output", "rt_halo_bytes", "rt_halo_pack",
     "rt_halo_unpack", "rt_halo_bitmap_words", "rt_halo_flags_bytes", "rt_halo_flags_pack", "rt_halo_flags_unpack",
@@ -96,6 +98,9 @@ def load_library(exp=False, path=None):
     L.rt_scene_update.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
     L.rt_denoise.argtypes = [vp, vp]
     L.rt_denoise_timing.argtypes = [vp, vp]
+    L.rt_denoise_temporal.argtypes = [vp, vp, vp]
+    L.rt_denoise_temporal_reset.argtypes = [vp]
+    L.rt_denoise_temporal_timing.argtypes = [vp, vp]
     L.rt_camera_lookat.argtypes = [vp, vp, vp, vp, cf]
     L.rt_camera_set.argtypes = [vp, vp, vp]
     L.rt_camera_get.argtypes = [vp, vp]
@@ -345,11 +350,13 @@ def _p(a):
 _BUF_DTYPE = {
     RT_BUF_VISIBILITY: VISIBILITY, RT_BUF_RES_0: RESERVOIR, RT_BUF_RES_1: RESERVOIR,
     RT_BUF_RES_TEMPORAL: RESERVOIR, RT_BUF_ACCUMULATION: np.dtype(("<f4", 4)), RT_BUF_PIXELS: np.dtype(("u1", 4)),
-    RT_BUF_DENOISED: np.dtype(("<f4", 4)), RT_BUF_DENOISE_GUIDE: VISIBILITY,
+    RT_BUF_DENOISED: np.dtype(("<f4", 4)), RT_BUF_DENOISE_GUIDE: VISIBILITY, RT_BUF_DENOISE_HISTORY: np.dtype(("<f4", 4)),
 }
 # rt_denoise_params (include/restir_rt_internal.h)
 DENOISE_PARAMS = np.dtype([("iterations", "<i4"), ("sigma_luminance", "<f4"), ("sigma_plane", "<f4"), ("normal_power_log2", "<i4"),
                            ("variance_radius", "<i4")])
+# rt_denoise_temporal_params
+DENOISE_TEMPORAL_PARAMS = np.dtype([("alpha_color", "<f4"), ("alpha_moments", "<f4")])
 
 
 class Renderer:
@@ -539,6 +546,32 @@ class Renderer:
         ms = np.zeros(5, dtype=np.float32)
         self._ck(self.L.rt_denoise_timing(self.h, _p(ms)))
         return dict(zip(["guide", "prep", "levels", "last_level", "total"], [float(v) for v in ms]))
+
+    def denoise_temporal(self, iterations=5, sigma_luminance=4.0, sigma_plane=1.0, normal_power_log2=7, variance_radius=3,
+                         alpha_color=0.2, alpha_moments=0.2, hdr=False):
+        """rt_denoise_temporal: one frame of a sequence. The accumulation buffer as it stands is blended with the history reprojected
+        from the previous call (SVGF's temporal half, csrc/denoise_math.h), then filtered as denoise() filters. Returns what denoise()
+        returns (RT_BUF_PIXELS, or RT_BUF_DENOISED with hdr=True); RT_BUF_DENOISE_HISTORY holds {mu1, mu2, h, 0} per pixel."""
+        p = np.zeros(1, dtype=DENOISE_PARAMS)
+        p["iterations"], p["sigma_luminance"], p["sigma_plane"] = int(iterations), float(sigma_luminance), float(sigma_plane)
+        p["normal_power_log2"], p["variance_radius"] = int(normal_power_log2), int(variance_radius)
+        t = np.zeros(1, dtype=DENOISE_TEMPORAL_PARAMS)
+        t["alpha_color"], t["alpha_moments"] = float(alpha_color), float(alpha_moments)
+        self._ck(self.L.rt_denoise_temporal(self.h, _p(p), _p(t)))
+        if hdr:
+            return self.download(RT_BUF_DENOISED).reshape(self.local_rows, self.W, 4)
+        return self.download(RT_BUF_PIXELS).view(np.uint8).reshape(self.local_rows, self.W, 4)
+
+    def denoise_temporal_reset(self):
+        """empty rt_denoise_temporal's history: the next call starts a new sequence (and equals denoise())"""
+        self._ck(self.L.rt_denoise_temporal_reset(self.h))
+
+    def denoise_temporal_timing(self):
+        """device ms of the last rt_denoise_temporal run with timing_enable(True): guide, reprojection (+ integration), variance,
+        the levels before the last, the last level (fused output), whole call"""
+        ms = np.zeros(6, dtype=np.float32)
+        self._ck(self.L.rt_denoise_temporal_timing(self.h, _p(ms)))
+        return dict(zip(["guide", "reprojection", "variance", "levels", "last_level", "total"], [float(v) for v in ms]))
 
     def path_trace_rays(self):
         a = C.c_uint64()

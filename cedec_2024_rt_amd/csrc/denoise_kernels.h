@@ -12,6 +12,11 @@
  *   k_denoise_iter_lds the same level over 16 x 16 blocks of one residue lattice {p = r mod s} staged in LDS with a 2-point apron
  *                     (key 28 = 1: 20 x 20 records of 48 B whatever the step)
  *   FINAL forms of the level (and k_denoise_output for 0 iterations): HDR value + RGBA8 (tone_map_rgba8)
+ *
+ * rt_denoise_temporal puts two kernels in place of demodulation and variance and reuses the others:
+ *   k_denoise_temporal  reprojection into the previous camera, demodulation and integration: col = {c, 0} (or {0, 0, 0, -1}) and
+ *                       the moments record {mu1, mu2, h, 0}
+ *   k_denoise_var_hist  col' = {c, var}: the temporal variance where h >= 4, k_denoise_var's window elsewhere
  */
 #pragma once
 #include "denoise_math.h"
@@ -82,18 +87,10 @@ __global__ __launch_bounds__(BLOCK) void k_denoise_demod(FrameParams P, const fl
     col[li] = make_float4(e.x, e.y, e.z, 0.0f);
 }
 
-__global__ __launch_bounds__(BLOCK) void k_denoise_var(FrameParams P, DnParams D, const float4* __restrict__ gx, const float4* __restrict__ gn,
-                                                       const float4* __restrict__ cin, float4* __restrict__ cout)
+/* the luminance variance of participating pixel (x, row) over the (2R+1)^2 window at step 1 */
+RT_DEV float dn_window_variance(const FrameParams& P, const DnParams& D, int x, int row, size_t li, const float4* __restrict__ gx,
+                                const float4* __restrict__ gn, const float4* __restrict__ cin)
 {
-    int x, row;
-    if (!tile_pixel(P, x, row)) return;
-    const size_t li = (size_t)x + (size_t)row * P.W;
-    const float4 cp = cin[li];
-    if (cp.w < 0.0f)
-    {
-        cout[li] = cp;
-        return;
-    }
     const float4 xp4 = gx[li], np4 = gn[li];
     const f3 xp = F3(xp4.x, xp4.y, xp4.z), np = F3(np4.x, np4.y, np4.z);
     const int R = D.variance_radius;
@@ -115,7 +112,90 @@ __global__ __launch_bounds__(BLOCK) void k_denoise_var(FrameParams P, DnParams D
             dn_moments_add(m, dn_variance_weight(wn, dxp), dn_luminance(cq));
         }
     }
-    cout[li] = make_float4(cp.x, cp.y, cp.z, dn_moments_variance(m));
+    return dn_moments_variance(m);
+}
+__global__ __launch_bounds__(BLOCK) void k_denoise_var(FrameParams P, DnParams D, const float4* __restrict__ gx, const float4* __restrict__ gn,
+                                                       const float4* __restrict__ cin, float4* __restrict__ cout)
+{
+    int x, row;
+    if (!tile_pixel(P, x, row)) return;
+    const size_t li = (size_t)x + (size_t)row * P.W;
+    const float4 cp = cin[li];
+    if (cp.w < 0.0f)
+    {
+        cout[li] = cp;
+        return;
+    }
+    cout[li] = make_float4(cp.x, cp.y, cp.z, dn_window_variance(P, D, x, row, li, gx, gn, cin));
+}
+
+/* ------------------------------------------------------------------ temporal prep (rt_denoise_temporal) */
+struct DnTemporal
+{
+    f3 rg_origin, rg_right, rg_up; /* the previous call's RayGenerator */
+    float alpha_c, alpha_m;
+    int has_history; /* 0: the first call after a reset (the previous buffers are not read) */
+};
+/* one pass per pixel: 2 guide records, the accumulation, the albedo, and per valid tap 4 records of the previous frame */
+__global__ __launch_bounds__(BLOCK) void k_denoise_temporal(FrameParams P, DnTemporal T, const float4* __restrict__ trimat,
+                                                            const float4* __restrict__ accum, const float4* __restrict__ gx,
+                                                            const float4* __restrict__ gn, const float4* __restrict__ pgx,
+                                                            const float4* __restrict__ pgn, const float4* __restrict__ hcol,
+                                                            const float4* __restrict__ hmom, float4* __restrict__ col, float4* __restrict__ mom)
+{
+    int x, row;
+    if (!tile_pixel(P, x, row)) return;
+    const size_t li = (size_t)x + (size_t)row * P.W;
+    const float4 np4 = gn[li];
+    const uint32_t word = as_uint(np4.w);
+    const float4 A = accum[li];
+    if (dn_kind(word) != DN_KIND_SURFACE || A.w == 0.0f)
+    {
+        col[li] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        mom[li] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const f3 e = dn_demodulate(A, dn_albedo(trimat, word));
+    const float4 xp4 = gx[li];
+    const f3 xp = F3(xp4.x, xp4.y, xp4.z), np = F3(np4.x, np4.y, np4.z);
+    DnHistory s = dn_history_init();
+    float px, pr;
+    if (T.has_history && dn_reproject(xp, T.rg_origin, T.rg_right, T.rg_up, P.W, P.H, px, pr))
+    {
+        int x0, r0;
+        float w[4];
+        dn_bilinear(px, pr, x0, r0, w);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+        {
+            const int qx = x0 + (k & 1), qr = r0 + (k >> 1);
+            if (qx < 0 || qx >= P.W || qr < 0 || qr >= P.H) continue;
+            const size_t qi = (size_t)qx + (size_t)qr * P.W;
+            const float4 mq = hmom[qi], nq4 = pgn[qi], xq4 = pgx[qi];
+            if (!dn_temporal_tap_valid(np, xp, xp4.w, as_uint(nq4.w), mq.z, F3(nq4.x, nq4.y, nq4.z), F3(xq4.x, xq4.y, xq4.z))) continue;
+            dn_history_add(s, w[k], hcol[qi], mq);
+        }
+    }
+    float4 c, m;
+    dn_temporal_integrate(s, e, T.alpha_c, T.alpha_m, c, m);
+    col[li] = c;
+    mom[li] = m;
+}
+__global__ __launch_bounds__(BLOCK) void k_denoise_var_hist(FrameParams P, DnParams D, const float4* __restrict__ gx, const float4* __restrict__ gn,
+                                                            const float4* __restrict__ mom, const float4* __restrict__ cin, float4* __restrict__ cout)
+{
+    int x, row;
+    if (!tile_pixel(P, x, row)) return;
+    const size_t li = (size_t)x + (size_t)row * P.W;
+    const float4 cp = cin[li];
+    if (cp.w < 0.0f)
+    {
+        cout[li] = cp;
+        return;
+    }
+    const float4 m = mom[li];
+    const float var = m.z >= DN_HISTORY_VARIANCE_MIN ? dn_temporal_variance(m) : dn_window_variance(P, D, x, row, li, gx, gn, cin);
+    cout[li] = make_float4(cp.x, cp.y, cp.z, var);
 }
 
 /* ------------------------------------------------------------------ one a-trous level */
@@ -153,11 +233,8 @@ template <bool FINAL>
 RT_DEV void dn_store(size_t li, const float4& out, bool part, uint32_t word, const float4* __restrict__ trimat, const float4* __restrict__ accum,
                      float4* __restrict__ cout, float4* __restrict__ hdr, uint32_t* __restrict__ pixels)
 {
-    if (!FINAL)
-    {
-        cout[li] = out;
-        return;
-    }
+    if (!FINAL || cout) cout[li] = out; /* FINAL with cout: the level that also feeds rt_denoise_temporal's history (1 iteration) */
+    if (!FINAL) return;
     float4 v;
     if (part)
     {

@@ -1,8 +1,8 @@
 /*
  * denoise_math.h — per-pixel and per-tap arithmetic of rt_denoise (include/restir_rt_internal.h): a spatial edge-avoiding
  * a-trous wavelet filter (Dammertz et al. 2010, "Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination
- * Filtering") with the variance-guided luminance weight of SVGF (Schied et al. 2017). Spatial half only: no reprojection,
- * no history.
+ * Filtering") with the variance-guided luminance weight of SVGF (Schied et al. 2017); and the temporal half of SVGF that
+ * rt_denoise_temporal adds in front of it (reprojection into the previous camera, colour and moment history; the last section).
  *
  * Every formula the kernels (denoise_kernels.h) evaluate is here, as RT_HD functions over IEEE +, -, *, / and the two
  * portable transcendentals (pm_expf; sqrt_guarded, correctly rounded on both sides, rt_device.h). Compiled by hipcc and by
@@ -144,6 +144,105 @@ RT_HD float4 dn_remodulate(float4 e, f3 a)
     o.z = e.z * a.z;
     o.w = 1.0f;
     return o;
+}
+
+/* ---- temporal half (rt_denoise_temporal): SVGF's reprojection, history and temporal variance (Schied et al. 2017, 4.1 and 4.2).
+ * The context keeps the previous call's guide, RayGenerator, colour history (its level 1 output, step 1: SVGF's feedback) and the
+ * moments record {mu1, mu2, h, 0}. Per participating pixel p: x_p projected into the previous camera gives storage coordinates
+ * (px, pr); its 2 x 2 bilinear taps (order r0x0, r0x1, r1x0, r1x1) that pass dn_temporal_tap_valid form the history; then
+ * dn_temporal_integrate. Pixels that do not participate get h = 0 (never a tap of the next call). ---- */
+constexpr float DN_TEMPORAL_NORMAL_MIN = 0.9f;  /* a tap needs n_p . n_q >= this */
+constexpr float DN_TEMPORAL_PLANE_MAX = 2.0f;   /* ... and |n_p . (x_q - x_p)| <= this * f_p */
+constexpr float DN_TEMPORAL_WEIGHT_MIN = 0.01f; /* history exists if the valid taps' bilinear weights sum to >= this */
+constexpr float DN_HISTORY_MAX = 32.0f;         /* cap of the history length h */
+constexpr float DN_HISTORY_VARIANCE_MIN = 4.0f; /* h >= this: the temporal variance; below: the spatial window (k_denoise_var's) */
+
+/* inverse of primary_direction (frame_kernels.h: pixel x has u = x / W, storage row = H - 1 - yi with v = yi / H) for the
+ * RayGenerator {o, R, U} (R, U and forward = normalize(U x R) orthogonal, as raygen_lookat makes them): continuous storage
+ * coordinates of x. false behind the camera, or where no bilinear tap can be inside the image (NaN included) */
+RT_HD bool dn_reproject(f3 x, f3 o, f3 R, f3 U, int W, int H, float& px, float& pr)
+{
+    const f3 fwd = normalize(cross(U, R));
+    const f3 d = x - o;
+    const float t = dot(d, fwd);
+    if (!(t > 0.0f)) return false;
+    const float a = dot(d, R) / (t * dot(R, R)), b = dot(d, U) / (t * dot(U, U));
+    px = ((a + 1.0f) * 0.5f) * (float)W;
+    pr = (float)(H - 1) - ((1.0f - b) * 0.5f) * (float)H;
+    return px >= -1.0f && px < (float)W && pr >= -1.0f && pr < (float)H;
+}
+/* the 2 x 2 taps from (x0, r0), weights in tap order r0x0, r0x1, r1x0, r1x1 */
+RT_HD void dn_bilinear(float px, float pr, int& x0, int& r0, float w[4])
+{
+    const float fx0 = floorf(px), fr0 = floorf(pr);
+    const float fx = px - fx0, fr = pr - fr0;
+    x0 = (int)fx0;
+    r0 = (int)fr0;
+    w[0] = (1.0f - fx) * (1.0f - fr);
+    w[1] = fx * (1.0f - fr);
+    w[2] = (1.0f - fx) * fr;
+    w[3] = fx * fr;
+}
+/* a tap of the previous frame that is inside the image: SURFACE, history length > 0, the same orientation and the same plane */
+RT_HD bool dn_temporal_tap_valid(f3 np, f3 xp, float fp, uint32_t word_q, float hq, f3 nq, f3 xq)
+{
+    return dn_kind(word_q) == DN_KIND_SURFACE && hq > 0.0f && dot(np, nq) >= DN_TEMPORAL_NORMAL_MIN &&
+           fabsf(dot(np, xq - xp)) <= DN_TEMPORAL_PLANE_MAX * fp;
+}
+
+/* weighted sums over the valid taps in tap order; h of the valid tap with the largest weight (the first on ties) */
+struct DnHistory
+{
+    float sw, r, g, b, m1, m2, wmax, h;
+};
+RT_HD DnHistory dn_history_init() { return DnHistory{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}; }
+RT_HD void dn_history_add(DnHistory& s, float w, float4 c, float4 m)
+{
+    s.sw = s.sw + w;
+    s.r = s.r + w * c.x;
+    s.g = s.g + w * c.y;
+    s.b = s.b + w * c.z;
+    s.m1 = s.m1 + w * m.x;
+    s.m2 = s.m2 + w * m.y;
+    if (w > s.wmax)
+    {
+        s.wmax = w;
+        s.h = m.z;
+    }
+}
+RT_HD float dn_blend(float prev, float cur, float a) { return (1.0f - a) * prev + a * cur; }
+/* the integrated colour {c, 0} and moments {mu1, mu2, h, 0} of a participating pixel with demodulated value e */
+RT_HD void dn_temporal_integrate(const DnHistory& s, f3 e, float alpha_c, float alpha_m, float4& col, float4& mom)
+{
+    const float l = dn_luminance(e);
+    col.w = 0.0f;
+    mom.w = 0.0f;
+    if (!(s.sw >= DN_TEMPORAL_WEIGHT_MIN))
+    {
+        col.x = e.x;
+        col.y = e.y;
+        col.z = e.z;
+        mom.x = l;
+        mom.y = l * l;
+        mom.z = 1.0f;
+        return;
+    }
+    const float hn = s.h + 1.0f;
+    const float h = hn < DN_HISTORY_MAX ? hn : DN_HISTORY_MAX;
+    const float inv = 1.0f / h;
+    const float ac = alpha_c > inv ? alpha_c : inv, am = alpha_m > inv ? alpha_m : inv;
+    col.x = dn_blend(s.r / s.sw, e.x, ac);
+    col.y = dn_blend(s.g / s.sw, e.y, ac);
+    col.z = dn_blend(s.b / s.sw, e.z, ac);
+    mom.x = dn_blend(s.m1 / s.sw, l, am);
+    mom.y = dn_blend(s.m2 / s.sw, l * l, am);
+    mom.z = h;
+}
+/* h >= DN_HISTORY_VARIANCE_MIN: max(0, mu2 - mu1^2) */
+RT_HD float dn_temporal_variance(float4 mom)
+{
+    const float v = mom.y - mom.x * mom.x;
+    return v > 0.0f ? v : 0.0f;
 }
 
 }  // namespace rt

@@ -219,6 +219,14 @@ struct rt_ctx
     bool dn_valid = false, dn_timed = false;
     int tune_dn_layout = DN_LAYOUT_DEFAULT; /* rt_tuning key 28: a-trous levels 0 = per-lane gathers, 1 = residue lattice in LDS */
     hipEvent_t dn_ev[5] = {};
+    /* rt_denoise_temporal's history, allocated at the first call: guides {x, f} / {n, word} and moments {mu1, mu2, h, 0} of the
+     * current [dt_cur] and the previous [1 - dt_cur] call, the colour history (level 1's output), the previous RayGenerator;
+     * dt_valid: a history exists (rt_scene_set and rt_denoise_temporal_reset clear it). It scratches d_dn_col / d_dn_vis / d_dn_hdr. */
+    float4 *d_dt_gx[2] = {nullptr, nullptr}, *d_dt_gn[2] = {nullptr, nullptr}, *d_dt_mom[2] = {nullptr, nullptr}, *d_dt_col = nullptr;
+    rt_raygen dt_rg;
+    int dt_cur = 0;
+    bool dt_valid = false, dt_timed = false;
+    hipEvent_t dt_ev[6] = {};
     void* d_stage = nullptr;
     size_t stage_bytes = 0;
 
@@ -450,6 +458,9 @@ int rt_destroy(rt_ctx* c)
     for (auto& p : c->d_tile_perm) hipFree(p);
     hipFree(c->d_dn_vis); hipFree(c->d_dn_gx); hipFree(c->d_dn_gn); hipFree(c->d_dn_col[0]); hipFree(c->d_dn_col[1]); hipFree(c->d_dn_hdr);
     for (auto& e : c->dn_ev) if (e) hipEventDestroy(e);
+    for (int k = 0; k < 2; ++k) { hipFree(c->d_dt_gx[k]); hipFree(c->d_dt_gn[k]); hipFree(c->d_dt_mom[k]); }
+    hipFree(c->d_dt_col);
+    for (auto& e : c->dt_ev) if (e) hipEventDestroy(e);
     hipFree(c->d_counter); hipFree(c->d_stage); hipFree(c->d_paths[0]); hipFree(c->d_paths[1]); hipFree(c->d_pt_counters);
     if (c->ev_created) for (auto& e : c->ev) hipEventDestroy(e);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -1033,6 +1044,7 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     if (c->own_stream && c->own_stream != c->stream) RT_HIP(c, hipStreamSynchronize(c->own_stream));
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
     c->spec_valid = false;
+    c->dt_valid = false; /* rt_denoise_temporal's history belongs to the old scene */
     const auto t_build0 = std::chrono::steady_clock::now();
     free_scene(c);
     ++c->epoch;
@@ -2065,13 +2077,13 @@ int rt_path_trace_rays(rt_ctx* c, uint64_t* rays)
 }
 
 /* ---- rt_denoise (denoise_kernels.h): guide, demodulation, variance, the a-trous levels; asynchronous on the context's stream ---- */
-int rt_denoise(rt_ctx* c, const rt_denoise_params* params)
+/* what rt_denoise and rt_denoise_temporal share: the checks, the buffers, the guide pass and one a-trous level */
+static int denoise_begin(rt_ctx* c, const rt_denoise_params* params, rt_denoise_params& d, const char* name)
 {
-    RT_CHECK_CTX(c);
     if (c->row_begin != 0 || c->row_end != c->H)
-        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_denoise is for whole-frame contexts (rows [%d,%d) of %d)", c->row_begin, c->row_end, c->H);
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "%s is for whole-frame contexts (rows [%d,%d) of %d)", name, c->row_begin, c->row_end, c->H);
     NEED_SCENE(c);
-    rt_denoise_params d = {5, 4.0f, 1.0f, 7, 3};
+    d = rt_denoise_params{5, 4.0f, 1.0f, 7, 3};
     if (params) d = *params;
     if (d.iterations < 0 || d.iterations > 8) RT_FAIL(c, RT_ERR_ARG, "iterations %d outside 0..8", d.iterations);
     if (!(d.sigma_luminance > 0.0f) || !(d.sigma_luminance < INFINITY)) RT_FAIL(c, RT_ERR_ARG, "sigma_luminance must be finite and > 0");
@@ -2079,6 +2091,10 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* params)
     if (d.normal_power_log2 < 0 || d.normal_power_log2 > 10) RT_FAIL(c, RT_ERR_ARG, "normal_power_log2 %d outside 0..10", d.normal_power_log2);
     if (d.variance_radius < 0 || d.variance_radius > 3) RT_FAIL(c, RT_ERR_ARG, "variance_radius %d outside 0..3", d.variance_radius);
     if (c->n_tris > (1 << 30)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "the guide word holds triangle indices below 2^30");
+    return RT_OK;
+}
+static int denoise_alloc(rt_ctx* c)
+{
     RT_HIP(c, hipSetDevice(c->device));
     const size_t n = local_pixels(c);
     if (!c->d_dn_hdr)
@@ -2087,6 +2103,40 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* params)
         for (float4** b : bufs)
             if (!*b) RT_HIP(c, hipMalloc(b, n * 16));
     }
+    return RT_OK;
+}
+static int denoise_guide(rt_ctx* c, const SceneView& S, hipStream_t st, float4* gx, float4* gn)
+{
+    const FrameParams PG = make_params(c, 0, 0, K_RAYCAST);
+    if (use_ws_primary(c, trace_grid(c))) k_denoise_guide<true><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, gx, gn);
+    else k_denoise_guide<false><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, gx, gn);
+    RT_HIP(c, hipGetLastError());
+    return RT_OK;
+}
+/* a-trous level at `step` from cin into cout; the last level writes the HDR output and the pixels (and cout unless it is null) */
+static int denoise_level(rt_ctx* c, const FrameParams& P, const DnParams& D, hipStream_t st, int step, bool last, const float4* gx,
+                         const float4* gn, const float4* cin, float4* cout)
+{
+    if (c->tune_dn_layout == 1)
+    {
+        const int nbx = ((c->W + step - 1) / step + DN_LDS_BLOCK - 1) / DN_LDS_BLOCK, nby = ((c->H + step - 1) / step + DN_LDS_BLOCK - 1) / DN_LDS_BLOCK;
+        const int gl = step * step * nbx * nby;
+        if (last) k_denoise_iter_lds<true><<<gl, DN_LDS_BLOCK * DN_LDS_BLOCK, 0, st>>>(P, D, step, nbx, nby, c->d_trimat, c->d_accum, gx, gn, cin, cout, c->d_dn_hdr, c->d_pixels);
+        else k_denoise_iter_lds<false><<<gl, DN_LDS_BLOCK * DN_LDS_BLOCK, 0, st>>>(P, D, step, nbx, nby, c->d_trimat, c->d_accum, gx, gn, cin, cout, nullptr, nullptr);
+    }
+    else if (last) k_denoise_iter<true><<<launch_grid(c), BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, gx, gn, cin, cout, c->d_dn_hdr, c->d_pixels);
+    else k_denoise_iter<false><<<launch_grid(c), BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, gx, gn, cin, cout, nullptr, nullptr);
+    RT_HIP(c, hipGetLastError());
+    return RT_OK;
+}
+#define DN_CK(x) do { const int _r = (x); if (_r != RT_OK) return _r; } while (0)
+
+int rt_denoise(rt_ctx* c, const rt_denoise_params* params)
+{
+    RT_CHECK_CTX(c);
+    rt_denoise_params d;
+    DN_CK(denoise_begin(c, params, d, "rt_denoise"));
+    DN_CK(denoise_alloc(c));
     /* what may still write the accumulation buffer (or the pixels): the previous frame's resolve + tone mapping on the tail stream,
      * the look-ahead stage 0 (waited for, not dropped: its results stay valid for the next frame). What comes after on this stream
      * is ordered behind the launches below; the next staged frame's tail forks from this stream behind them. */
@@ -2098,12 +2148,7 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* params)
         for (auto& e : c->dn_ev) RT_HIP(c, hipEventCreate(&e));
     if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[0], st));
     const SceneView S = make_scene(c);
-    {
-        const FrameParams PG = make_params(c, 0, 0, K_RAYCAST);
-        if (use_ws_primary(c, trace_grid(c))) k_denoise_guide<true><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, c->d_dn_gx, c->d_dn_gn);
-        else k_denoise_guide<false><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, c->d_dn_gx, c->d_dn_gn);
-        RT_HIP(c, hipGetLastError());
-    }
+    DN_CK(denoise_guide(c, S, st, c->d_dn_gx, c->d_dn_gn));
     if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[1], st));
     const FrameParams P = make_params(c, 0, 0, K_SPATIAL);
     const DnParams D = {d.iterations, d.sigma_luminance, d.sigma_plane, d.normal_power_log2, d.variance_radius};
@@ -2121,19 +2166,7 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* params)
     {
         const bool last = i + 1 == d.iterations;
         if (timed && last) RT_HIP(c, hipEventRecord(c->dn_ev[3], st));
-        const int step = 1 << i;
-        const float4* cin = c->d_dn_col[i & 1];
-        float4* cout = c->d_dn_col[(i + 1) & 1];
-        if (c->tune_dn_layout == 1)
-        {
-            const int nbx = ((c->W + step - 1) / step + DN_LDS_BLOCK - 1) / DN_LDS_BLOCK, nby = ((c->H + step - 1) / step + DN_LDS_BLOCK - 1) / DN_LDS_BLOCK;
-            const int gl = step * step * nbx * nby;
-            if (last) k_denoise_iter_lds<true><<<gl, DN_LDS_BLOCK * DN_LDS_BLOCK, 0, st>>>(P, D, step, nbx, nby, c->d_trimat, c->d_accum, c->d_dn_gx, c->d_dn_gn, cin, nullptr, c->d_dn_hdr, c->d_pixels);
-            else k_denoise_iter_lds<false><<<gl, DN_LDS_BLOCK * DN_LDS_BLOCK, 0, st>>>(P, D, step, nbx, nby, c->d_trimat, c->d_accum, c->d_dn_gx, c->d_dn_gn, cin, cout, nullptr, nullptr);
-        }
-        else if (last) k_denoise_iter<true><<<g, BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, c->d_dn_gx, c->d_dn_gn, cin, nullptr, c->d_dn_hdr, c->d_pixels);
-        else k_denoise_iter<false><<<g, BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, c->d_dn_gx, c->d_dn_gn, cin, cout, nullptr, nullptr);
-        RT_HIP(c, hipGetLastError());
+        DN_CK(denoise_level(c, P, D, st, 1 << i, last, c->d_dn_gx, c->d_dn_gn, c->d_dn_col[i & 1], last ? nullptr : c->d_dn_col[(i + 1) & 1]));
     }
     RT_HIP(c, hipGetLastError());
     if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[4], st));
@@ -2149,6 +2182,96 @@ int rt_denoise_timing(rt_ctx* c, float ms[5])
     RT_HIP(c, hipEventSynchronize(c->dn_ev[4]));
     for (int k = 0; k < 4; ++k) RT_HIP(c, hipEventElapsedTime(&ms[k], c->dn_ev[k], c->dn_ev[k + 1]));
     RT_HIP(c, hipEventElapsedTime(&ms[4], c->dn_ev[0], c->dn_ev[4]));
+    return RT_OK;
+}
+
+/* ---- rt_denoise_temporal (denoise_kernels.h): guide, reprojection + integration, variance with history, rt_denoise's levels.
+ * Buffers: k_denoise_temporal reads the previous guide / moments [1 - cur] and the colour history, writes the integrated colour
+ * into d_dn_col[1] and the moments [cur]; k_denoise_var_hist -> d_dn_col[0] (0 iterations: d_dt_col, the history itself);
+ * level 1 -> d_dt_col (it has been read already), level i >= 2 -> d_dn_col[i & 1]. ---- */
+int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_denoise_temporal_params* temporal)
+{
+    RT_CHECK_CTX(c);
+    rt_denoise_params d;
+    DN_CK(denoise_begin(c, spatial, d, "rt_denoise_temporal"));
+    rt_denoise_temporal_params t = {0.2f, 0.2f};
+    if (temporal) t = *temporal;
+    if (!(t.alpha_color > 0.0f && t.alpha_color <= 1.0f)) RT_FAIL(c, RT_ERR_ARG, "alpha_color must be in (0, 1]");
+    if (!(t.alpha_moments > 0.0f && t.alpha_moments <= 1.0f)) RT_FAIL(c, RT_ERR_ARG, "alpha_moments must be in (0, 1]");
+    DN_CK(denoise_alloc(c));
+    const size_t n = local_pixels(c);
+    if (!c->d_dt_col)
+    {
+        float4** bufs[7] = {&c->d_dt_gx[0], &c->d_dt_gx[1], &c->d_dt_gn[0], &c->d_dt_gn[1], &c->d_dt_mom[0], &c->d_dt_mom[1], &c->d_dt_col};
+        for (float4** b : bufs)
+            if (!*b) RT_HIP(c, hipMalloc(b, n * 16));
+    }
+    JOIN_TAIL(c); /* as rt_denoise */
+    JOIN_SPEC(c);
+    hipStream_t st = c->stream;
+    const bool timed = c->timing;
+    if (timed && !c->dt_ev[0])
+        for (auto& e : c->dt_ev) RT_HIP(c, hipEventCreate(&e));
+    const int cur = c->dt_valid ? 1 - c->dt_cur : c->dt_cur, prev = 1 - cur;
+    if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[0], st));
+    const SceneView S = make_scene(c);
+    DN_CK(denoise_guide(c, S, st, c->d_dt_gx[cur], c->d_dt_gn[cur]));
+    if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[1], st));
+    const FrameParams P = make_params(c, 0, 0, K_SPATIAL);
+    const DnParams D = {d.iterations, d.sigma_luminance, d.sigma_plane, d.normal_power_log2, d.variance_radius};
+    DnTemporal T;
+    T.rg_origin = F3(c->dt_rg.origin[0], c->dt_rg.origin[1], c->dt_rg.origin[2]);
+    T.rg_right = F3(c->dt_rg.right[0], c->dt_rg.right[1], c->dt_rg.right[2]);
+    T.rg_up = F3(c->dt_rg.up[0], c->dt_rg.up[1], c->dt_rg.up[2]);
+    T.alpha_c = t.alpha_color;
+    T.alpha_m = t.alpha_moments;
+    T.has_history = c->dt_valid ? 1 : 0;
+    const int g = launch_grid(c);
+    float4 *gx = c->d_dt_gx[cur], *gn = c->d_dt_gn[cur], *mom = c->d_dt_mom[cur];
+    k_denoise_temporal<<<g, BLOCK, 0, st>>>(P, T, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
+                                            c->d_dt_mom[prev], c->d_dn_col[1], mom);
+    RT_HIP(c, hipGetLastError());
+    if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[2], st));
+    float4* var_out = d.iterations == 0 ? c->d_dt_col : c->d_dn_col[0];
+    k_denoise_var_hist<<<g, BLOCK, 0, st>>>(P, D, gx, gn, mom, c->d_dn_col[1], var_out);
+    RT_HIP(c, hipGetLastError());
+    if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[3], st));
+    if (d.iterations == 0)
+    {
+        if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[4], st));
+        k_denoise_output<<<g, BLOCK, 0, st>>>(P, c->d_trimat, c->d_accum, gn, var_out, c->d_dn_hdr, c->d_pixels);
+        RT_HIP(c, hipGetLastError());
+    }
+    for (int i = 0; i < d.iterations; ++i)
+    {
+        const bool last = i + 1 == d.iterations;
+        if (timed && last) RT_HIP(c, hipEventRecord(c->dt_ev[4], st));
+        const float4* cin = i == 0 ? c->d_dn_col[0] : i == 1 ? c->d_dt_col : c->d_dn_col[(i - 1) & 1];
+        float4* cout = i == 0 ? c->d_dt_col : last ? nullptr : c->d_dn_col[i & 1];
+        DN_CK(denoise_level(c, P, D, st, 1 << i, last, gx, gn, cin, cout));
+    }
+    if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[5], st));
+    c->dt_rg = c->rg;
+    c->dt_cur = cur;
+    c->dt_valid = true;
+    c->dt_timed = timed;
+    c->dn_valid = true;
+    return RT_OK;
+}
+int rt_denoise_temporal_reset(rt_ctx* c)
+{
+    RT_CHECK_CTX(c);
+    c->dt_valid = false; /* the next call reads none of the previous buffers */
+    return RT_OK;
+}
+int rt_denoise_temporal_timing(rt_ctx* c, float ms[6])
+{
+    RT_CHECK_CTX(c);
+    if (!ms) return RT_ERR_ARG;
+    if (!c->dt_timed) RT_FAIL(c, RT_ERR_STATE, "no timed rt_denoise_temporal (rt_timing_enable + rt_denoise_temporal first)");
+    RT_HIP(c, hipEventSynchronize(c->dt_ev[5]));
+    for (int k = 0; k < 5; ++k) RT_HIP(c, hipEventElapsedTime(&ms[k], c->dt_ev[k], c->dt_ev[k + 1]));
+    RT_HIP(c, hipEventElapsedTime(&ms[5], c->dt_ev[0], c->dt_ev[5]));
     return RT_OK;
 }
 
@@ -2529,6 +2652,11 @@ int rt_download(rt_ctx* c, int buf, void* dst, size_t bytes)
             if (!c->dn_valid) RT_FAIL(c, RT_ERR_STATE, "buffer %d is written by rt_denoise, which has not run on this context", buf);
             if (bytes != n * 16) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 16);
             RT_HIP(c, hipMemcpyAsync(dst, buf == RT_BUF_DENOISED ? c->d_dn_hdr : c->d_dn_vis, bytes, hipMemcpyDeviceToHost, c->stream));
+            break;
+        case RT_BUF_DENOISE_HISTORY:
+            if (!c->dt_valid) RT_FAIL(c, RT_ERR_STATE, "no rt_denoise_temporal history (none since the context, the scene or the last reset)");
+            if (bytes != n * 16) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 16);
+            RT_HIP(c, hipMemcpyAsync(dst, c->d_dt_mom[c->dt_cur], bytes, hipMemcpyDeviceToHost, c->stream));
             break;
         case RT_BUF_RES_0:
         case RT_BUF_RES_1:

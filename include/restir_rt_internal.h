@@ -67,6 +67,30 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params);
  * before the last, [3] the last level (fused output), [4] the whole call */
 int rt_denoise_timing(rt_ctx* ctx, float ms[5]);
 
+/* ---- temporal denoiser: SVGF's reprojection and history (Schied et al. 2017) in front of rt_denoise's filter ---- */
+typedef struct
+{
+    float alpha_color;   /* (0, 1], default 0.2 */
+    float alpha_moments; /* (0, 1], default 0.2 */
+} rt_denoise_temporal_params;
+enum
+{
+    RT_BUF_DENOISE_HISTORY = 8 /* float4[W*H] {mu1, mu2, history length, 0} of the last rt_denoise_temporal call; download only */
+};
+/* rt_denoise's contract, for one frame of a sequence: the accumulation buffer as it stands is the new frame (call it once per
+ * frame). Per pixel the demodulated value is blended with its history, reprojected from the previous call's guide and camera
+ * (csrc/denoise_math.h pins the arithmetic); the variance is the history's where it is 4 frames or longer; rt_denoise's levels
+ * follow and the first level's output is the next call's colour history. Writes RT_BUF_DENOISED, RT_BUF_PIXELS,
+ * RT_BUF_DENOISE_GUIDE and RT_BUF_DENOISE_HISTORY. The history is the context's, allocated at the first call: rt_scene_set and
+ * rt_denoise_temporal_reset empty it; camera changes, rt_options_set, rt_scene_update and rt_denoise calls keep it. The first call
+ * after a reset equals rt_denoise with the same spatial parameters. Whole-frame contexts only (RT_ERR_UNSUPPORTED); NULL
+ * parameters = defaults; out of range: RT_ERR_ARG; RT_BUF_DENOISE_HISTORY before the first call or after a reset: RT_ERR_STATE. */
+int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* spatial, const rt_denoise_temporal_params* temporal);
+int rt_denoise_temporal_reset(rt_ctx* ctx);
+/* device time of the last rt_denoise_temporal run while rt_timing_enable was on: ms[0] guide, [1] reprojection + integration,
+ * [2] variance, [3] the levels before the last, [4] the last level (fused output), [5] the whole call */
+int rt_denoise_temporal_timing(rt_ctx* ctx, float ms[6]);
+
 /* ---- rt_frame in stages ---- */
 /* The same frame cut into stages for strip contexts (multi-GPU): stage 0 = [clear,] raycast,
  * generate_candidate(+temporal); stage k in 1..passes = spatial pass k-1; stage passes+1 = resolve,

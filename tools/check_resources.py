@@ -37,6 +37,8 @@ BUDGET = [
     (r"^k_denoise_iter<", 0, 8),         # a-trous level, per-lane gathers (rt_tuning 28 = 0)
     (r"^k_denoise_iter_lds<", 0, 8),     # residue lattice in LDS (rt_tuning 28 = 1), 19 200 B per workgroup
     (r"^k_denoise_output", 0, 8),
+    (r"^k_denoise_temporal", 0, 8),      # r10 rt_denoise_temporal: reprojection + integration
+    (r"^k_denoise_var_hist", 0, 8),      # variance with history
 ]
 
 
