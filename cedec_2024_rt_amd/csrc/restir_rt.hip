@@ -71,8 +71,8 @@ struct rt_ctx
     bool spec_outstanding = false; /* work recorded by ev_spec_done that the main stream has not waited for yet */
     uint64_t spec_epoch = 0;
     /* tags of the own-visibility flags (rt_device.h): one number per staged frame and per pipelined stage 0; the launches of
-     * a staged frame carry frame_tag (cur_tag while they are enqueued), the per-kernel entry points carry 0 */
-    uint32_t ownv_serial = 0, frame_tag = 0, cur_tag = 0, spec_gen_tag = 0;
+     * a staged frame carry frame_tag (Launch::tag), the per-kernel entry points carry 0 */
+    uint32_t ownv_serial = 0, frame_tag = 0, spec_gen_tag = 0;
     /* which G-buffer a reservoir buffer's shaded bits belong to (k_refresh_shaded): gbuf_serial counts G-buffer writes */
     uint64_t gbuf_serial = 0, rec_gserial[5] = {0, 0, 0, 0, 0};
     unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters */
@@ -203,8 +203,6 @@ struct rt_ctx
     bool spec_gen_valid = false, gen_taken = false;
     int spec_gen_frame = 0, spec_gen_hist = -1;
     uint64_t res_epoch = 1, spec_res_epoch = 0;
-    int sub0 = -1, sub1 = -1; /* row sub-range of the running rt_frame_stage_run (-1: all owned rows) */
-    int subb0 = 0, subb1 = 0; /* optional second row range of the same launches (rt_frame_stage_run_ranges) */
     int fX = 0, fY = 1, fZ = 2, f_in = 0, f_out = 1, f_stage = 0, f_final = RT_RES_1, f_frame = 0;
     bool f_clear = false;
     uint64_t halo_flags_epoch[2] = {0, 0}; /* epoch at which the neighbour's shaded flags were unpacked (valid while it is the current one) */
@@ -277,15 +275,26 @@ static rt_options default_options()
     return o;
 }
 
+/* Where and over what a launch goes. Built by whoever decides it (an entry point, a stage run, the look-ahead stage 0) and handed
+ * down by reference: the launch helpers take the stream, the rows, the tag and the G-buffer set from here and from nowhere else. */
+struct Launch
+{
+    hipStream_t stream;
+    int row0, row1, rowb0, rowb1; /* storage rows [row0,row1), and an optional second range of the same launches (rowb0 >= rowb1: none) */
+    uint32_t tag;                 /* own-visibility tag (rt_device.h): the staged frame's, 0 for the per-kernel entry points */
+    bool timed;                   /* rt_timing's per-kernel events belong to this lane */
+    float4 *vis, *g0, *g1;        /* G-buffer set */
+};
+/* the context's current stream, all owned rows, the current G-buffer set: what a per-kernel entry point launches */
+static Launch whole_launch(const rt_ctx* c) { return Launch{c->stream, c->row_begin, c->row_end, 0, 0, 0u, c->timing, c->d_vis, c->d_g0, c->d_g1}; }
+
 enum { K_RAYCAST = 0, K_GENERATE = 1, K_SPATIAL = 2, K_RESOLVE = 3, K_OTHER = 4 };
-static FrameParams make_params(const rt_ctx* c, int frame, int pass, int kernel = K_OTHER)
+static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int pass, int kernel = K_OTHER)
 {
     FrameParams P;
     P.W = c->W; P.H = c->H;
-    P.row0 = c->sub0 >= 0 ? c->sub0 : c->row_begin;
-    P.row1 = c->sub0 >= 0 ? c->sub1 : c->row_end;
-    P.rowb0 = c->sub0 >= 0 ? c->subb0 : 0;
-    P.rowb1 = c->sub0 >= 0 ? c->subb1 : 0;
+    P.row0 = L.row0; P.row1 = L.row1;
+    P.rowb0 = L.rowb0; P.rowb1 = L.rowb1;
     P.lrow0 = c->lrow0; P.lrows = c->lrows;
     P.frame = frame; P.pass = pass;
     P.eye = F3(c->eye[0], c->eye[1], c->eye[2]);
@@ -316,12 +325,12 @@ static FrameParams make_params(const rt_ctx* c, int frame, int pass, int kernel 
         const int autom = kernel == K_SPATIAL ? spatial : (kernel == K_OTHER ? 0 : traced);
         P.tile_mode = c->tune_tile_mode[kernel] >= 0 ? c->tune_tile_mode[kernel] : autom;
     }
-    P.ownv_tag = c->cur_tag;
+    P.ownv_tag = L.tag;
     P.stats = c->walk_on ? c->d_walk : nullptr;
 #ifdef RT_EXPERIMENTS
     P.wave_clock = c->d_wave_clock && kernel == c->wave_clock_kernel && (kernel != K_SPATIAL || pass == c->wave_clock_pass) ? c->d_wave_clock : nullptr;
     /* whole launches over the context's own rows only (the grid the permutation was checked against) */
-    const bool own_rows = c->sub0 < 0 || (c->sub0 == c->row_begin && c->sub1 == c->row_end && c->subb1 <= c->subb0);
+    const bool own_rows = L.row0 == c->row_begin && L.row1 == c->row_end && L.rowb1 <= L.rowb0;
     P.tile_perm = (kernel == K_RAYCAST || kernel == K_GENERATE || kernel == K_RESOLVE) && own_rows ? c->d_tile_perm[kernel] : nullptr;
 #endif
     return P;
@@ -1377,10 +1386,7 @@ int rt_options_get(rt_ctx* c, rt_options* o)
 #define NEED_RES(c, id) \
     if ((id) < 0 || (id) > 2) RT_FAIL(c, RT_ERR_ARG, "bad reservoir buffer id %d", (id));
 
-static int launch_grid(const rt_ctx* c)
-{
-    return c->sub0 >= 0 ? tile_grid(c->W, c->sub1 - c->sub0, TILE_W, TILE_H, c->subb1 - c->subb0) : tile_grid(c->W, c->row_end - c->row_begin);
-}
+static int launch_grid(const rt_ctx* c, const Launch& L) { return tile_grid(c->W, L.row1 - L.row0, TILE_W, TILE_H, L.rowb1 - L.rowb0); }
 /* The work-sharing walk evens out the per-wavefront tail (longest lane 8x the mean: profiles/r02_wave_tail.txt). A launch
  * of many rounds of wavefronts hides that tail behind the next wavefronts and only pays the bookkeeping; a launch of
  * about one round (a strip of the multi-GPU frame: 135 rows x 1920 = 4050 wavefronts on 1024 SIMDs x 4-5) ends with
@@ -1403,70 +1409,76 @@ static int stream_priority(const char* env, int dflt)
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return 0;
     return want > 0 ? least : (want < 0 ? greatest : 0);
 }
-static bool use_tail(const rt_ctx* c)
+static bool use_tail(const rt_ctx* c, bool timed)
 {
-    if (c->timing) return false; /* rt_timing brackets the kernels with events on the main stream */
+    if (timed) return false; /* rt_timing brackets the kernels with events on the main stream */
     /* auto = always (r03: strips 0.442 -> 0.373 ms per frame at 1080p in 8 strips; a whole 1080p frame 1.68 -> 1.63 ms) */
     return c->tune_tail != 0;
 }
 /* the stream about to be used waits for the previous frame's resolve + tone_mapping (no-op unless they are in flight) */
-static int join_tail(rt_ctx* c)
+static int join_tail(rt_ctx* c, const Launch& L)
 {
     if (!c->tail_pending_main) return RT_OK;
-    RT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_tail, 0));
+    RT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_tail, 0));
     /* the second lane of a stage waits for itself; the main stream still has to */
-    if (c->stream != c->aux_stream) c->tail_pending_main = false;
+    if (L.stream != c->aux_stream) c->tail_pending_main = false;
     return RT_OK;
 }
-#define JOIN_TAIL(c) do { const int _jt = join_tail(c); if (_jt != RT_OK) return _jt; } while (0)
+/* the entry points outside the staged frame: the context's current stream joins */
+#define JOIN_TAIL(c) do { const int _jt = join_tail(c, whole_launch(c)); if (_jt != RT_OK) return _jt; } while (0)
 /* a kernel of the staged frame that WRITES reservoir buffer `phys` (and reads only what the tail reads too): it waits for the
  * tail only if that is the buffer the tail reads */
-static int join_tail_for(rt_ctx* c, int phys) { return (c->tail_pending_main && phys == c->tail_phys) ? join_tail(c) : RT_OK; }
+static int join_tail_for(rt_ctx* c, const Launch& L, int phys) { return (c->tail_pending_main && phys == c->tail_phys) ? join_tail(c, L) : RT_OK; }
 /* the pipelined stage 0 (spec_stream) may still be running when a call outside the staged frame — or a frame that does not
  * take its results — starts to write what it reads (the history buffer, the other G-buffer set) or reads what it writes: the
  * stream about to be used waits for it first (cheap: that work is behind already). ADVICE r03. */
-static int join_spec(rt_ctx* c)
+static int join_spec(rt_ctx* c, const Launch& L)
 {
     if (!c->spec_outstanding) return RT_OK;
-    RT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_spec_done, 0));
-    if (c->stream != c->aux_stream) c->spec_outstanding = false;
+    RT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_spec_done, 0));
+    if (L.stream != c->aux_stream) c->spec_outstanding = false;
     return RT_OK;
 }
-#define JOIN_SPEC(c) do { const int _js = join_spec(c); if (_js != RT_OK) return _js; } while (0)
-static int trace_grid(const rt_ctx* c)
+#define JOIN_SPEC(c) do { const int _js = join_spec(c, whole_launch(c)); if (_js != RT_OK) return _js; } while (0)
+static int trace_grid(const rt_ctx* c, const Launch& L)
 {
-    const int rows = c->sub0 >= 0 ? c->sub1 - c->sub0 : c->row_end - c->row_begin;
-    return tile_grid(c->W, rows, TileShape<TRACE_BLOCK>::W, TileShape<TRACE_BLOCK>::H, c->sub0 >= 0 ? c->subb1 - c->subb0 : 0);
+    return tile_grid(c->W, L.row1 - L.row0, TileShape<TRACE_BLOCK>::W, TileShape<TRACE_BLOCK>::H, L.rowb1 - L.rowb0);
 }
 
-int rt_clear(rt_ctx* c)
+/* rt_clear over the launch's rows */
+static int clear_rows(rt_ctx* c, const Launch& L)
 {
-    RT_CHECK_CTX(c);
-    JOIN_TAIL(c);
-    k_clear<<<launch_grid(c), BLOCK, 0, c->stream>>>(make_params(c, 0, 0), c->d_accum);
+    { const int rc = join_tail(c, L); if (rc != RT_OK) return rc; }
+    k_clear<<<launch_grid(c, L), BLOCK, 0, L.stream>>>(make_params(c, L, 0, 0), c->d_accum);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
-
-/* the raycast launch of the context's tuning, on `st`, into the given G-buffer set */
-static void launch_raycast(rt_ctx* c, hipStream_t st, float4* vis, float4* g0, float4* g1)
-{
-#ifdef RT_EXPERIMENTS
-    if (c->tune_half_raycast) { k_raycast_half<<<2 * trace_grid(c), TRACE_BLOCK, 0, st>>>(make_scene(c), make_params(c, 0, 0, K_RAYCAST), vis, g0, g1); return; }
-#endif
-#ifdef RT_EXPERIMENTS
-    if (c->tune_ws_primary == 2) { k_raycast_quad<<<4 * trace_grid(c), TRACE_BLOCK, 0, st>>>(make_scene(c), make_params(c, 0, 0, K_RAYCAST), vis, g0, g1); return; }
-#endif
-    if (use_ws_primary(c, trace_grid(c))) k_raycast<true><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(make_scene(c), make_params(c, 0, 0, K_RAYCAST), vis, g0, g1);
-    else k_raycast<false><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(make_scene(c), make_params(c, 0, 0, K_RAYCAST), vis, g0, g1);
-}
-int rt_raycast(rt_ctx* c)
+int rt_clear(rt_ctx* c)
 {
     RT_CHECK_CTX(c);
-    JOIN_TAIL(c);
-    JOIN_SPEC(c);
+    return clear_rows(c, whole_launch(c));
+}
+
+/* the raycast launch of the context's tuning, into the launch's G-buffer set */
+static void launch_raycast(rt_ctx* c, const Launch& L)
+{
+    const int g = trace_grid(c, L);
+    const FrameParams P = make_params(c, L, 0, 0, K_RAYCAST);
+#ifdef RT_EXPERIMENTS
+    if (c->tune_half_raycast) { k_raycast_half<<<2 * g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), P, L.vis, L.g0, L.g1); return; }
+    if (c->tune_ws_primary == 2) { k_raycast_quad<<<4 * g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), P, L.vis, L.g0, L.g1); return; }
+#endif
+    if (use_ws_primary(c, g)) k_raycast<true><<<g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), P, L.vis, L.g0, L.g1);
+    else k_raycast<false><<<g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), P, L.vis, L.g0, L.g1);
+}
+/* rt_raycast over the launch's rows, with everything it does to the context's state */
+static int raycast_rows(rt_ctx* c, const Launch& L)
+{
+    int rc = join_tail(c, L);
+    if (rc == RT_OK) rc = join_spec(c, L);
+    if (rc != RT_OK) return rc;
     NEED_SCENE(c);
-    launch_raycast(c, c->stream, c->d_vis, c->d_g0, c->d_g1);
+    launch_raycast(c, L);
     RT_HIP(c, hipGetLastError());
     c->has_gbuffer = true;
     ++c->gbuf_serial;
@@ -1476,29 +1488,34 @@ int rt_raycast(rt_ctx* c)
      * the scene or the options change (halo_flags_epoch), which is when the neighbours' G-buffers change */
     return RT_OK;
 }
+int rt_raycast(rt_ctx* c)
+{
+    RT_CHECK_CTX(c);
+    return raycast_rows(c, whole_launch(c));
+}
 
 /* A/B r02 (profiles/r02_next_raycast_ab.txt): a strip's frame is a chain of small launches and exchanges with idle
  * slots the raycast fills (-6 % at 1080p in 8 strips, -3 % at 4K); a whole frame gains < 1 % at 1080p (the overlapped
  * spatial pass just waits for the machine) and its per-kernel times stop being comparable, so auto means strips only */
-static bool use_next_raycast(const rt_ctx* c)
+static bool use_next_raycast(const rt_ctx* c, bool timed)
 {
     if (c->tune_spec >= 0) return c->tune_spec != 0;
     /* auto: strips always; whole frames too (r03: with the candidates pipelined as well a 1080p frame gains 3 %), except
      * while rt_timing brackets the kernels of a frame with events — then they run back to back on one stream */
-    return (c->row_begin != 0 || c->row_end != c->H) || !c->timing;
+    return (c->row_begin != 0 || c->row_end != c->H) || !timed;
 }
 /* the next frame's generate_candidate(+temporal) too. Not while per-kernel timing is on (rt_timing attributes events of the
  * main stream to kernels) and not with the deferred-visibility queue (its counters live per lane of the main frame). */
-static bool use_next_generate(const rt_ctx* c)
+static bool use_next_generate(const rt_ctx* c, bool timed)
 {
-    if (!use_next_raycast(c) || c->timing || c->tune_defer_vis) return false;
+    if (!use_next_raycast(c, timed) || timed || c->tune_defer_vis) return false;
     return c->tune_spec < 0 || c->tune_spec == 2;
 }
 /* r05, rt_tuning key 22. auto: strips — their kernels are launches of one to three generations of wavefronts and what fills the GPU
  * is running several of them side by side (rank 4 of 8: 1080p 0.306 -> 0.287 ms, 4K 0.889 -> 0.870, profiles/r05_spec_free_ab.txt);
  * a whole frame's kernels fill the GPU alone and only take slots from each other (pipelined 1080p frame 1.277 -> 1.296 ms) */
 static bool spec_free(const rt_ctx* c) { return c->tune_spec_free < 0 ? (c->row_begin != 0 || c->row_end != c->H) : c->tune_spec_free != 0; }
-static int launch_generate(rt_ctx* c, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis = nullptr);
+static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis = nullptr);
 /* r05, rt_tuning key 25: raycast + generate_candidate (+ temporal merge) of a frame in ONE launch — the candidates need the primary ray
  * of their own pixel only, and two launches on a stream cost the first one's ramp-down (its last wavefront starts at 216 of 257 us).
  * The product's fused candidate kernel only (temporal merge on, unshadowed, work-sharing shadow walk), whole owned rows.
@@ -1514,14 +1531,15 @@ static bool use_fused_stage0(const rt_ctx* c)
 #ifdef RT_EXPERIMENTS
     if (c->tune_half_raycast || c->tune_defer_vis || c->tune_ris_pipe) return false;
 #endif
-    const int g = trace_grid(c);
+    const int g = trace_grid(c, whole_launch(c));
     return c->opt.use_temporal_resampling && !c->opt.use_shadowed_target_function && c->n_lights > 0 && use_ws(c, g) && !use_ws_primary(c, g);
 }
 /* the next frame's primary rays, behind everything enqueued on the main stream so far, on the stream of their own */
 static int launch_next_raycast(rt_ctx* c, int frame)
 {
     c->spec_gen_valid = false;
-    if (!use_next_raycast(c)) { c->spec_valid = false; return RT_OK; }
+    if (!use_next_raycast(c, c->timing)) { c->spec_valid = false; return RT_OK; }
+    const bool next_generate = use_next_generate(c, c->timing);
     const size_t n = local_pixels(c);
     const int o = (c->gcur + 1) % rt_ctx::NGSET;
     bool fresh_set = false;
@@ -1553,19 +1571,18 @@ static int launch_next_raycast(rt_ctx* c, int frame)
      * overwrites is not the one the running frame reads, and the candidates' buffer has no role in the running frame nor is it
      * what the tail in flight reads */
     if (o == c->gcur) RT_FAIL(c, RT_ERR_STATE, "look-ahead stage 0 would overwrite the running frame's G-buffer set %d", o);
-    if (use_next_generate(c) && (c->spare == c->fX || c->spare == c->fY || c->spare == c->fZ || c->spare == c->quarantine ||
+    if (next_generate && (c->spare == c->fX || c->spare == c->fY || c->spare == c->fZ || c->spare == c->quarantine ||
                                  (spec_free(c) && c->tail_pending_main && c->spare == c->tail_phys))) /* r04's dependencies hand the tail's buffer over and wait for the latest resolve above */
         RT_FAIL(c, RT_ERR_STATE, "look-ahead candidates' buffer %d is in use (X %d Y %d Z %d quarantine %d tail %d)", c->spare, c->fX, c->fY, c->fZ, c->quarantine, c->tail_pending_main ? c->tail_phys : -1);
-    const int s0 = c->sub0, s1 = c->sub1, b0 = c->subb0, b1 = c->subb1;
-    c->sub0 = c->sub1 = -1; c->subb0 = c->subb1 = 0; /* all owned rows */
-    if (c->timing) hipEventRecord(c->ev_spec_t[o][0], c->spec_stream);
-    const bool one_launch = use_next_generate(c) && use_fused_stage0(c); /* the candidates' launch below traces the primary rays too */
-    if (!one_launch) launch_raycast(c, c->spec_stream, c->d_gset[o][0], c->d_gset[o][1], c->d_gset[o][2]);
+    Launch spec = whole_launch(c); /* all owned rows, on the stream of its own, into set o */
+    spec.stream = c->spec_stream; spec.vis = c->d_gset[o][0]; spec.g0 = c->d_gset[o][1]; spec.g1 = c->d_gset[o][2];
+    if (c->timing) hipEventRecord(c->ev_spec_t[o][0], spec.stream);
+    const bool one_launch = next_generate && use_fused_stage0(c); /* the candidates' launch below traces the primary rays too */
+    if (!one_launch) launch_raycast(c, spec);
     RT_HIP(c, hipGetLastError());
-    if (c->timing) hipEventRecord(c->ev_spec_t[o][1], c->spec_stream);
+    if (c->timing) hipEventRecord(c->ev_spec_t[o][1], spec.stream);
     c->spec_timed[o] = c->timing;
-    int rc = RT_OK;
-    if (use_next_generate(c) && c->n_lights > 0)
+    if (next_generate && c->n_lights > 0)
     {
         /* candidates (+ temporal merge) of frame + 1: G-buffer = the set just traced, history = the buffer this frame's
          * stage 0 wrote (c->fY), output = the spare buffer; all owned rows, on the same stream behind the raycast */
@@ -1574,46 +1591,37 @@ static int launch_next_raycast(rt_ctx* c, int frame)
         {
             RT_HIP(c, hipMalloc(&c->d_rec[c->spare], npx * 64));
             RT_HIP(c, hipMalloc(&c->d_rad[c->spare], npx * 16));
-            RT_HIP(c, hipMemsetAsync(c->d_rec[c->spare], 0, npx * 64, c->spec_stream));
-            RT_HIP(c, hipMemsetAsync(c->d_rad[c->spare], 0, npx * 16, c->spec_stream));
+            RT_HIP(c, hipMemsetAsync(c->d_rec[c->spare], 0, npx * 64, spec.stream));
+            RT_HIP(c, hipMemsetAsync(c->d_rad[c->spare], 0, npx * 16, spec.stream));
         }
-        hipStream_t ms = c->stream;
-        float4 *g0 = c->d_g0, *g1 = c->d_g1;
-        c->stream = c->spec_stream; c->d_g0 = c->d_gset[o][1]; c->d_g1 = c->d_gset[o][2];
-        const uint32_t tag_now = c->cur_tag;
         c->spec_gen_tag = next_ownv_tag(c); /* the frame that takes these candidates continues under their tag */
-        c->cur_tag = c->spec_gen_tag;
-        rc = launch_generate(c, frame + 1, c->spare, c->fY, c->opt.use_temporal_resampling != 0, one_launch ? c->d_gset[o][0] : nullptr);
-        c->cur_tag = tag_now;
-        c->stream = ms; c->d_g0 = g0; c->d_g1 = g1;
-        if (rc == RT_OK)
-        {
-            c->spec_gen_valid = true;
-            c->spec_gen_frame = frame + 1;
-            c->spec_gen_hist = c->fY;
-            c->spec_res_epoch = c->res_epoch;
-        }
+        spec.tag = c->spec_gen_tag;
+        const int rc = launch_generate(c, spec, frame + 1, c->spare, c->fY, c->opt.use_temporal_resampling != 0, one_launch ? spec.vis : nullptr);
+        if (rc != RT_OK) return rc;
+        c->spec_gen_valid = true;
+        c->spec_gen_frame = frame + 1;
+        c->spec_gen_hist = c->fY;
+        c->spec_res_epoch = c->res_epoch;
     }
-    c->sub0 = s0; c->sub1 = s1; c->subb0 = b0; c->subb1 = b1;
-    if (rc != RT_OK) return rc;
-    RT_HIP(c, hipEventRecord(c->ev_spec_done, c->spec_stream));
+    RT_HIP(c, hipEventRecord(c->ev_spec_done, spec.stream));
     c->spec_outstanding = true;
     c->spec_valid = true;
     c->spec_epoch = c->epoch;
     return RT_OK;
 }
 /* stage 0's raycast over all owned rows: the G-buffer traced beside the previous frame if it is still the right one */
-static int raycast_or_take(rt_ctx* c, bool whole, int frame, bool may_defer = false, bool* deferred = nullptr)
+/* L: the stage's launch; a take moves it to the taken G-buffer set and, with the candidates, to their tag */
+static int raycast_or_take(rt_ctx* c, Launch& L, bool whole, int frame, bool may_defer = false, bool* deferred = nullptr)
 {
     c->timed_spec_set = -1;
     c->gen_taken = false;
-    if (whole && use_next_raycast(c) && c->spec_valid && c->spec_epoch == c->epoch)
+    if (whole && use_next_raycast(c, L.timed) && c->spec_valid && c->spec_epoch == c->epoch)
     {
         c->gcur = (c->gcur + 1) % rt_ctx::NGSET;
-        c->d_vis = c->d_gset[c->gcur][0]; c->d_g0 = c->d_gset[c->gcur][1]; c->d_g1 = c->d_gset[c->gcur][2];
-        RT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_spec_done, 0));
+        L.vis = c->d_vis = c->d_gset[c->gcur][0]; L.g0 = c->d_g0 = c->d_gset[c->gcur][1]; L.g1 = c->d_g1 = c->d_gset[c->gcur][2];
+        RT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_spec_done, 0));
         c->spec_outstanding = false;
-        if (c->spec_gen_valid && use_next_generate(c) && c->spec_gen_frame == frame && c->spec_res_epoch == c->res_epoch &&
+        if (c->spec_gen_valid && use_next_generate(c, L.timed) && c->spec_gen_frame == frame && c->spec_res_epoch == c->res_epoch &&
             c->spec_gen_hist == c->fX)
         {
             /* this frame's candidates are in the spare buffer already: it becomes Y (stage 0's generate is skipped;
@@ -1634,7 +1642,7 @@ static int raycast_or_take(rt_ctx* c, bool whole, int frame, bool may_defer = fa
             c->f_in = c->fY; c->f_out = c->fZ;
             c->gen_taken = true;
             c->frame_tag = c->spec_gen_tag; /* own-visibility flags of the candidates were written under this tag */
-            c->cur_tag = c->frame_tag;
+            L.tag = c->frame_tag;
         }
         c->spec_gen_valid = false;
         c->spec_valid = false;
@@ -1651,8 +1659,9 @@ static int raycast_or_take(rt_ctx* c, bool whole, int frame, bool may_defer = fa
     if (may_defer)
     {
         /* rt_raycast without its launch: the candidates' kernel of this stage traces the primary rays (use_fused_stage0) */
-        JOIN_TAIL(c);
-        JOIN_SPEC(c);
+        int rc = join_tail(c, L);
+        if (rc == RT_OK) rc = join_spec(c, L);
+        if (rc != RT_OK) return rc;
         c->has_gbuffer = true;
         ++c->gbuf_serial;
         c->gbuf_epoch = c->epoch;
@@ -1660,39 +1669,39 @@ static int raycast_or_take(rt_ctx* c, bool whole, int frame, bool may_defer = fa
         *deferred = true;
         return RT_OK;
     }
-    return rt_raycast(c);
+    return raycast_rows(c, L);
 }
 
-static int launch_generate(rt_ctx* c, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis)
+static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis)
 {
     if (c->n_lights == 0 && c->opt.ris_sample_count > 0)
         RT_FAIL(c, RT_ERR_STATE, "scene has no emissive triangle (the reference divides by zero here)");
     const SceneView S = make_scene(c);
-    const FrameParams P = make_params(c, frame, 0, K_GENERATE);
+    const FrameParams P = make_params(c, L, frame, 0, K_GENERATE);
     const bool sh = c->opt.use_shadowed_target_function;
     float4 *orec = c->d_rec[dst_phys], *orad = c->d_rad[dst_phys];
     c->rec_gserial[dst_phys] = c->gbuf_serial;
     const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
-    const int g = trace_grid(c);
+    const int g = trace_grid(c, L);
 #ifdef RT_EXPERIMENTS
     if (fuse && !sh && c->tune_defer_vis)
     {
         /* fused + unshadowed: the visibility-reuse rays that survive the temporal merge go through a queue */
-        const int lane = (c->stream == c->aux_stream) ? 1 : 0;
+        const int lane = (L.stream == c->aux_stream) ? 1 : 0;
         const size_t npx = local_pixels(c);
         if (!c->d_visq[0])
         {
             RT_HIP(c, hipMalloc(&c->d_visq[0], npx * 4));
             RT_HIP(c, hipMalloc(&c->d_visq[1], npx * 4));
             RT_HIP(c, hipMalloc(&c->d_visq_count, 8));
-            RT_HIP(c, hipMemsetAsync(c->d_visq_count, 0, 8, c->stream));
+            RT_HIP(c, hipMemsetAsync(c->d_visq_count, 0, 8, L.stream));
             RT_HIP(c, hipHostMalloc(&c->h_visq_count, 8, hipHostMallocDefault));
             c->h_visq_count[0] = c->h_visq_count[1] = 0xffffffffu;
         }
         if (c->visq_epoch != c->epoch) { c->h_visq_count[0] = c->h_visq_count[1] = 0xffffffffu; c->visq_epoch = c->epoch; }
-        RT_HIP(c, hipMemsetAsync(c->d_visq_count + lane, 0, 4, c->stream));
-        if (c->tune_ris_pipe) k_generate_candidate<true, false, true, true><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
-        else k_generate_candidate<true, false, true><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
+        RT_HIP(c, hipMemsetAsync(c->d_visq_count + lane, 0, 4, L.stream));
+        if (c->tune_ris_pipe) k_generate_candidate<true, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
+        else k_generate_candidate<true, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
         RT_HIP(c, hipGetLastError());
         /* grid of the walk: one queue entry per lane if the count is like the last one that reached the host (+50 %),
          * every pixel of the launch if that is unknown (first frame, camera / option change); the kernel's stride loop
@@ -1704,23 +1713,23 @@ static int launch_generate(rt_ctx* c, int frame, int dst_phys, int prev_phys, bo
             const unsigned long long want = ((unsigned long long)last * 3ull / 2ull + TRACE_BLOCK - 1) / TRACE_BLOCK + 64ull;
             gv = want < (unsigned long long)g ? (int)want : g;
         }
-        k_candidate_visibility<<<gv, TRACE_BLOCK, 0, c->stream>>>(S, c->d_g0, c->d_g1, orec, c->d_visq[lane], c->d_visq_count + lane);
+        k_candidate_visibility<<<gv, TRACE_BLOCK, 0, L.stream>>>(S, L.g0, L.g1, orec, c->d_visq[lane], c->d_visq_count + lane);
         RT_HIP(c, hipGetLastError());
-        RT_HIP(c, hipMemcpyAsync(c->h_visq_count + lane, c->d_visq_count + lane, 4, hipMemcpyDeviceToHost, c->stream));
+        RT_HIP(c, hipMemcpyAsync(c->h_visq_count + lane, c->d_visq_count + lane, 4, hipMemcpyDeviceToHost, L.stream));
         return RT_OK;
     }
 #endif
-    if (fuse && sh) k_generate_candidate<true, true><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, prec, prad, orec, orad);
+    if (fuse && sh) k_generate_candidate<true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
 #ifdef RT_EXPERIMENTS
-    else if (fuse && c->tune_ris_pipe) k_generate_candidate<true, false, false, true><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, prec, prad, orec, orad);
+    else if (fuse && c->tune_ris_pipe) k_generate_candidate<true, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
 #endif
     else if (fuse && use_ws(c, g) && raycast_vis)
-        k_generate_candidate<true, false, false, false, true, true><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, c->d_g0, c->d_g1);
+        k_generate_candidate<true, false, false, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, L.g0, L.g1);
     else if (raycast_vis) RT_FAIL(c, RT_ERR_STATE, "the one-launch stage 0 needs the product's fused candidate kernel");
-    else if (fuse && use_ws(c, g)) k_generate_candidate<true, false, false, false, true><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, prec, prad, orec, orad);
-    else if (fuse) k_generate_candidate<true, false><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, prec, prad, orec, orad);
-    else if (sh) k_generate_candidate<false, true><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, prec, prad, orec, orad);
-    else k_generate_candidate<false, false><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, prec, prad, orec, orad);
+    else if (fuse && use_ws(c, g)) k_generate_candidate<true, false, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else if (fuse) k_generate_candidate<true, false><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else if (sh) k_generate_candidate<false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else k_generate_candidate<false, false><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -1734,7 +1743,7 @@ int rt_generate_candidate(rt_ctx* c, int frame, int dst)
     NEED_RES(c, dst);
     ++c->res_epoch; /* a reservoir buffer changes outside the staged frame: a pipelined stage 0 is stale */
     if (!c->has_gbuffer) RT_FAIL(c, RT_ERR_STATE, "no G-buffer: call rt_raycast or upload RT_BUF_VISIBILITY first");
-    return launch_generate(c, frame, c->res_map[dst], 0, false);
+    return launch_generate(c, whole_launch(c), frame, c->res_map[dst], 0, false);
 }
 
 int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
@@ -1748,12 +1757,13 @@ int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
     ++c->res_epoch; /* a reservoir buffer changes outside the staged frame: a pipelined stage 0 is stale */
     if (prev == inout) RT_FAIL(c, RT_ERR_ARG, "prev and inout must differ");
     const SceneView S = make_scene(c);
-    const FrameParams P = make_params(c, frame, 0);
+    const Launch L = whole_launch(c);
+    const FrameParams P = make_params(c, L, frame, 0);
     const int pp = c->res_map[prev], pi = c->res_map[inout];
     if (c->opt.use_shadowed_target_function)
-        k_temporal<true><<<launch_grid(c), BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+        k_temporal<true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
     else
-        k_temporal<false><<<launch_grid(c), BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+        k_temporal<false><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -1800,14 +1810,14 @@ static bool use_lds_spatial(const rt_ctx* c)
            halo_rows_needed(c->opt) <= SPL_HALO && c->opt.spatial_resampling_sample_count <= 5 &&
            c->row_begin == 0 && c->row_end == c->H;
 }
-/* shaded bit per pixel of all local rows, rebuilt on the context's stream when the G-buffer or the halo flags changed.
+/* shaded bit per pixel of all local rows, rebuilt on the launch's stream when the G-buffer or the halo flags changed.
  * rt_frame_stage does this right behind the raycast, on the main stream, so that a stage's two lanes only read it. */
-static int refresh_shaded_bits(rt_ctx* c)
+static int refresh_shaded_bits(rt_ctx* c, const Launch& L)
 {
     if (!c->shaded_bits_stale || !c->has_gbuffer || !use_lds_spatial(c)) return RT_OK;
     const int words = (c->W + 31) / 32;
     if (!c->d_shaded_bits) RT_HIP(c, hipMalloc(&c->d_shaded_bits, (size_t)c->lrows * words * 4));
-    k_shaded_bitmap<<<dim3((c->W + 255) / 256, c->lrows), 256, 0, c->stream>>>(c->W, c->lrows, c->d_g1, c->d_shaded_bits);
+    k_shaded_bitmap<<<dim3((c->W + 255) / 256, c->lrows), 256, 0, L.stream>>>(c->W, c->lrows, L.g1, c->d_shaded_bits);
     RT_HIP(c, hipGetLastError());
     c->shaded_bits_stale = false;
     return RT_OK;
@@ -1833,7 +1843,7 @@ static bool use_fused_final(const rt_ctx* c)
     return want != 0 && !c->opt.use_shadowed_target_function && c->opt.use_spatial_resampling && c->tune_spatial_variant == 2 && !c->tune_stream &&
            c->opt.spatial_resampling_passes >= 1;
 }
-static int launch_spatial(rt_ctx* c, int frame, int pass, int in_phys, int out_phys, bool fuse_final = false)
+static int launch_spatial(rt_ctx* c, const Launch& L, int frame, int pass, int in_phys, int out_phys, bool fuse_final = false)
 {
     const int need = halo_rows_needed(c->opt);
     if ((c->row_begin > 0 && c->row_begin - c->lrow0 < (need < c->row_begin ? need : c->row_begin)) ||
@@ -1841,7 +1851,7 @@ static int launch_spatial(rt_ctx* c, int frame, int pass, int in_phys, int out_p
         RT_FAIL(c, RT_ERR_STATE, "strip halo of %d rows is too small: spatial_resampling_radius %.1f needs %d", c->halo,
                 c->opt.spatial_resampling_radius, need);
     const SceneView S = make_scene(c);
-    const FrameParams P = make_params(c, frame, pass, K_SPATIAL);
+    const FrameParams P = make_params(c, L, frame, pass, K_SPATIAL);
     const bool lds_variant = use_lds_spatial(c);
     (void)lds_variant; /* the product build has no LDS-staged form */
     c->rec_gserial[out_phys] = c->gbuf_serial;
@@ -1849,25 +1859,25 @@ static int launch_spatial(rt_ctx* c, int frame, int pass, int in_phys, int out_p
     {
         /* the cooperative record traffic of key 8 = 2 applies to the <= 5 neighbour form (spatial_wave_shadowed) */
         if (c->tune_spatial_variant >= 2 && c->opt.use_spatial_resampling && c->opt.spatial_resampling_sample_count <= 5)
-            k_spatial<true, true><<<trace_grid(c), TRACE_BLOCK, (size_t)(RT_SHADOWED_SPATIAL_LDS), c->stream>>>(S, P, c->fuse, c->d_g0, c->d_g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys]);
+            k_spatial<true, true><<<trace_grid(c, L), TRACE_BLOCK, (size_t)(RT_SHADOWED_SPATIAL_LDS), L.stream>>>(S, P, c->fuse, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys]);
         else
-            k_spatial<true, false><<<trace_grid(c), TRACE_BLOCK, (size_t)(RT_SHADOWED_SPATIAL_LDS), c->stream>>>(S, P, c->fuse, c->d_g0, c->d_g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys]);
+            k_spatial<true, false><<<trace_grid(c, L), TRACE_BLOCK, (size_t)(RT_SHADOWED_SPATIAL_LDS), L.stream>>>(S, P, c->fuse, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys]);
     }
 #ifdef RT_EXPERIMENTS
     else if (lds_variant && c->tune_spatial_variant == 3)
     {
         /* software-pipelined cooperative kernel (r04): staged shaded bits + the next neighbour's record in flight */
-        const int rc = refresh_shaded_bits(c);
+        const int rc = refresh_shaded_bits(c, L);
         if (rc != RT_OK) return rc;
-#define RT_SPP(WV) k_spatial_pipe<WV><<<launch_grid(c), BLOCK, (size_t)c->tune_spatial_lds, c->stream>>>(P, c->d_shaded_bits, c->d_g0, c->d_g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
+#define RT_SPP(WV) k_spatial_pipe<WV><<<launch_grid(c, L), BLOCK, (size_t)c->tune_spatial_lds, L.stream>>>(P, c->d_shaded_bits, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
         switch (c->tune_spatial_waves < 0 ? RT_SPATIAL_PIPE_AUTO_WAVES : c->tune_spatial_waves) { case 4: RT_SPP(4); break; case 5: RT_SPP(5); break; case 6: RT_SPP(6); break; default: RT_SPP(0); break; }
 #undef RT_SPP
     }
     else if (lds_variant)
     {
-        const int rc = refresh_shaded_bits(c); /* no-op inside rt_frame / rt_frame_stage: done behind the raycast */
+        const int rc = refresh_shaded_bits(c, L); /* no-op inside rt_frame / rt_frame_stage: done behind the raycast */
         if (rc != RT_OK) return rc;
-#define RT_SPL(WV) k_spatial_lds<WV><<<launch_grid(c), BLOCK, (size_t)c->tune_spatial_lds, c->stream>>>(P, c->d_shaded_bits, c->d_g0, c->d_g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
+#define RT_SPL(WV) k_spatial_lds<WV><<<launch_grid(c, L), BLOCK, (size_t)c->tune_spatial_lds, L.stream>>>(P, c->d_shaded_bits, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
         switch (c->tune_spatial_waves) { case 4: RT_SPL(4); break; case 5: RT_SPL(5); break; case 6: RT_SPL(6); break; default: RT_SPL(0); break; }
 #undef RT_SPL
     }
@@ -1879,7 +1889,7 @@ static int launch_spatial(rt_ctx* c, int frame, int pass, int in_phys, int out_p
         const bool fused = c->fuse.recv[0] || c->fuse.recv[1] || c->fuse.send[0] || c->fuse.send[1];
         const bool store = c->tune_fuse_final != 2; /* 2: A/B only, the pass's output buffer is NOT written */
         uint32_t* px = c->tune_fuse_tonemap ? (uint32_t*)c->d_pixels : nullptr;
-#define RT_SPR(FU, ST) k_spatial_resolve<FU, ST><<<trace_grid(c), TRACE_BLOCK, 0, c->stream>>>(S, P, c->fuse, c->d_g0, c->d_g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys], c->d_accum, px)
+#define RT_SPR(FU, ST) k_spatial_resolve<FU, ST><<<trace_grid(c, L), TRACE_BLOCK, 0, L.stream>>>(S, P, c->fuse, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys], c->d_accum, px)
         if (fused) { if (store) RT_SPR(true, true); else RT_SPR(true, false); }
         else { if (store) RT_SPR(false, true); else RT_SPR(false, false); }
 #undef RT_SPR
@@ -1893,14 +1903,14 @@ static int launch_spatial(rt_ctx* c, int frame, int pass, int in_phys, int out_p
          * 256-thread workgroup's four slots wait for four free slots on one CU: 5 400 of 6 144 slots filled on average). More
          * wavefronts in flight (5 750), each slower (25.9 -> 27.9 us): the pass is bound by its misses in flight, +1.3 % */
         const bool fused = c->fuse.recv[0] || c->fuse.recv[1] || c->fuse.send[0] || c->fuse.send[1];
-#define RT_SPC1(FU) k_spatial_coop<RT_SPATIAL_GATHER_AUTO_WAVES, FU, TRACE_BLOCK><<<trace_grid(c), TRACE_BLOCK, (size_t)c->tune_spatial_lds, c->stream>>>(S, P, c->fuse, c->d_g0, c->d_g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
+#define RT_SPC1(FU) k_spatial_coop<RT_SPATIAL_GATHER_AUTO_WAVES, FU, TRACE_BLOCK><<<trace_grid(c, L), TRACE_BLOCK, (size_t)c->tune_spatial_lds, L.stream>>>(S, P, c->fuse, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
         if (fused) RT_SPC1(true); else RT_SPC1(false);
 #undef RT_SPC1
     }
 #endif
     else if (c->tune_spatial_variant == 2 || c->tune_spatial_variant == 3) /* 3 where the pipelined kernel does not apply (strips, radius > 30, > 5 neighbours) */
     {
-#define RT_SPC2(WV, FU) k_spatial_coop<WV, FU><<<launch_grid(c), BLOCK, (size_t)c->tune_spatial_lds, c->stream>>>(S, P, c->fuse, c->d_g0, c->d_g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
+#define RT_SPC2(WV, FU) k_spatial_coop<WV, FU><<<launch_grid(c, L), BLOCK, (size_t)c->tune_spatial_lds, L.stream>>>(S, P, c->fuse, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
 #define RT_SPC(WV) do { if (fused) RT_SPC2(WV, true); else RT_SPC2(WV, false); } while (0)
         const bool fused = c->fuse.recv[0] || c->fuse.recv[1] || c->fuse.send[0] || c->fuse.send[1];
 #ifdef RT_EXPERIMENTS
@@ -1914,7 +1924,7 @@ static int launch_spatial(rt_ctx* c, int frame, int pass, int in_phys, int out_p
 #ifdef RT_EXPERIMENTS
     else
     {
-#define RT_SPG(WV) k_spatial_gather<WV><<<launch_grid(c), BLOCK, (size_t)c->tune_spatial_lds, c->stream>>>(S, P, c->fuse, c->d_g0, c->d_g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
+#define RT_SPG(WV) k_spatial_gather<WV><<<launch_grid(c, L), BLOCK, (size_t)c->tune_spatial_lds, L.stream>>>(S, P, c->fuse, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys])
         switch (c->tune_spatial_waves < 0 ? RT_SPATIAL_GATHER_AUTO_WAVES : c->tune_spatial_waves) { case 4: RT_SPG(4); break; case 5: RT_SPG(5); break; case 6: RT_SPG(6); break; default: RT_SPG(0); break; }
 #undef RT_SPG
     }
@@ -1950,25 +1960,25 @@ int rt_spatial_resampling(rt_ctx* c, int frame, int pass, int in, int out)
         RT_HIP(c, hipGetLastError());
         c->rec_gserial[c->res_map[in]] = c->gbuf_serial;
     }
-    return launch_spatial(c, frame, pass, c->res_map[in], c->res_map[out]);
+    return launch_spatial(c, whole_launch(c), frame, pass, c->res_map[in], c->res_map[out]);
 }
 
 /* pixels: the staged frame maps each pixel in the resolve kernel itself (rt_tuning key 20, default on); NULL = resolve alone */
-static int launch_resolve(rt_ctx* c, int phys, uint32_t* pixels = nullptr)
+static int launch_resolve(rt_ctx* c, const Launch& L, int phys, uint32_t* pixels = nullptr)
 {
-    const int g = trace_grid(c);
+    const int g = trace_grid(c, L);
 #ifdef RT_EXPERIMENTS
     if (c->tune_stream)
     {
         /* persistent wavefronts, tiles dealt out round-robin (no job counter) */
         const int resident = c->n_cus * 4 * RT_RESOLVE_STREAM_WAVES; /* wavefronts the GPU holds at once: a multiple of 8 */
         const int wgs = g < resident ? g : resident;
-        k_resolve_stream<<<wgs, TRACE_BLOCK, 0, c->stream>>>(make_scene(c), make_params(c, 0, 0, K_RESOLVE), c->d_g0, c->d_g1, c->d_rec[phys], c->d_rad[phys], c->d_accum, g);
+        k_resolve_stream<<<wgs, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), make_params(c, L, 0, 0, K_RESOLVE), L.g0, L.g1, c->d_rec[phys], c->d_rad[phys], c->d_accum, g);
     }
     else
 #endif
-    if (use_ws(c, g)) k_resolve<true><<<g, TRACE_BLOCK, 0, c->stream>>>(make_scene(c), make_params(c, 0, 0, K_RESOLVE), c->d_g0, c->d_g1, c->d_rec[phys], c->d_rad[phys], c->d_accum, pixels);
-    else k_resolve<false><<<g, TRACE_BLOCK, 0, c->stream>>>(make_scene(c), make_params(c, 0, 0, K_RESOLVE), c->d_g0, c->d_g1, c->d_rec[phys], c->d_rad[phys], c->d_accum, pixels);
+    if (use_ws(c, g)) k_resolve<true><<<g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), make_params(c, L, 0, 0, K_RESOLVE), L.g0, L.g1, c->d_rec[phys], c->d_rad[phys], c->d_accum, pixels);
+    else k_resolve<false><<<g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), make_params(c, L, 0, 0, K_RESOLVE), L.g0, L.g1, c->d_rec[phys], c->d_rad[phys], c->d_accum, pixels);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -1978,12 +1988,12 @@ int rt_resolve(rt_ctx* c, int res)
     JOIN_TAIL(c);
     NEED_SCENE(c);
     NEED_RES(c, res);
-    return launch_resolve(c, c->res_map[res]);
+    return launch_resolve(c, whole_launch(c), c->res_map[res]);
 }
 
-static int launch_tone_mapping(rt_ctx* c)
+static int launch_tone_mapping(rt_ctx* c, const Launch& L)
 {
-    k_tone_mapping<<<launch_grid(c), BLOCK, 0, c->stream>>>(make_params(c, 0, 0), c->d_accum, c->d_pixels);
+    k_tone_mapping<<<launch_grid(c, L), BLOCK, 0, L.stream>>>(make_params(c, L, 0, 0), c->d_accum, c->d_pixels);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -1991,7 +2001,7 @@ int rt_tone_mapping(rt_ctx* c)
 {
     RT_CHECK_CTX(c);
     JOIN_TAIL(c);
-    return launch_tone_mapping(c);
+    return launch_tone_mapping(c, whole_launch(c));
 }
 
 /* kernelMain of examples/04_ao/04_ao.cu:31-88 = 06_ao_hiprt.cu:35-91 (frame_kernels.h k_ao): RGBA8 straight into the pixel
@@ -1999,8 +2009,9 @@ int rt_tone_mapping(rt_ctx* c)
 static int launch_ao(rt_ctx* c)
 {
     const SceneView S = make_scene(c);
-    const FrameParams P = make_params(c, 0, 0, K_RAYCAST); /* the tracing kernels' tile order: interleaved over the XCDs */
-    const int g = trace_grid(c);
+    const Launch L = whole_launch(c);
+    const FrameParams P = make_params(c, L, 0, 0, K_RAYCAST); /* the tracing kernels' tile order: interleaved over the XCDs */
+    const int g = trace_grid(c, L);
     RT_HIP(c, hipMemsetAsync(c->d_counter, 0, 8, c->stream));
     if (c->tune_ao_layout == 1) k_ao<1><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_pixels, c->d_counter);
     else k_ao<0><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, c->d_pixels, c->d_counter);
@@ -2019,9 +2030,10 @@ int rt_path_trace(rt_ctx* c, int example, int frame)
     if (example != 7 && example != 8 && example != 9) RT_FAIL(c, RT_ERR_ARG, "example must be 4 (04_ao), 6 (06_ao_hiprt), 7 (07_pt), 8 (08_nee) or 9 (09_ris)");
     if (example != 7 && c->n_lights == 0) RT_FAIL(c, RT_ERR_STATE, "08_nee / 09_ris need at least one emissive triangle");
     const SceneView S = make_scene(c);
-    FrameParams P = make_params(c, frame, 0, K_RAYCAST);
+    const Launch L = whole_launch(c);
+    FrameParams P = make_params(c, L, frame, 0, K_RAYCAST);
     const f3 sky = F3(c->opt.sky_color[0], c->opt.sky_color[1], c->opt.sky_color[2]);
-    const int g = trace_grid(c);
+    const int g = trace_grid(c, L);
     const int md = c->opt.max_depth;
     const bool sh = c->opt.use_shadowed_target_function != 0;
     const bool wavefront = c->pt_wavefront == 1 || (c->pt_wavefront == 2 && example == 9);
@@ -2057,7 +2069,7 @@ int rt_path_trace(rt_ctx* c, int example, int frame)
         return RT_OK;
     }
     RT_HIP(c, hipMemsetAsync(c->d_counter, 0, 8, c->stream));
-    if (example == 7) k_path_trace<7, false><<<launch_grid(c), BLOCK, 0, c->stream>>>(S, P, md, sky, c->d_accum, c->d_counter);
+    if (example == 7) k_path_trace<7, false><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, md, sky, c->d_accum, c->d_counter);
     else if (example == 8) k_path_trace<8, false><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, md, sky, c->d_accum, c->d_counter);
     else if (sh) k_path_trace<9, true><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, md, sky, c->d_accum, c->d_counter);
     else k_path_trace<9, false><<<g, TRACE_BLOCK, 0, c->stream>>>(S, P, md, sky, c->d_accum, c->d_counter);
@@ -2107,9 +2119,10 @@ static int denoise_alloc(rt_ctx* c)
 }
 static int denoise_guide(rt_ctx* c, const SceneView& S, hipStream_t st, float4* gx, float4* gn)
 {
-    const FrameParams PG = make_params(c, 0, 0, K_RAYCAST);
-    if (use_ws_primary(c, trace_grid(c))) k_denoise_guide<true><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, gx, gn);
-    else k_denoise_guide<false><<<trace_grid(c), TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, gx, gn);
+    const FrameParams PG = make_params(c, whole_launch(c), 0, 0, K_RAYCAST);
+    const int g = trace_grid(c, whole_launch(c));
+    if (use_ws_primary(c, g)) k_denoise_guide<true><<<g, TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, gx, gn);
+    else k_denoise_guide<false><<<g, TRACE_BLOCK, 0, st>>>(S, PG, c->d_dn_vis, gx, gn);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -2124,8 +2137,8 @@ static int denoise_level(rt_ctx* c, const FrameParams& P, const DnParams& D, hip
         if (last) k_denoise_iter_lds<true><<<gl, DN_LDS_BLOCK * DN_LDS_BLOCK, 0, st>>>(P, D, step, nbx, nby, c->d_trimat, c->d_accum, gx, gn, cin, cout, c->d_dn_hdr, c->d_pixels);
         else k_denoise_iter_lds<false><<<gl, DN_LDS_BLOCK * DN_LDS_BLOCK, 0, st>>>(P, D, step, nbx, nby, c->d_trimat, c->d_accum, gx, gn, cin, cout, nullptr, nullptr);
     }
-    else if (last) k_denoise_iter<true><<<launch_grid(c), BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, gx, gn, cin, cout, c->d_dn_hdr, c->d_pixels);
-    else k_denoise_iter<false><<<launch_grid(c), BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, gx, gn, cin, cout, nullptr, nullptr);
+    else if (last) k_denoise_iter<true><<<launch_grid(c, whole_launch(c)), BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, gx, gn, cin, cout, c->d_dn_hdr, c->d_pixels);
+    else k_denoise_iter<false><<<launch_grid(c, whole_launch(c)), BLOCK, 0, st>>>(P, D, step, c->d_trimat, c->d_accum, gx, gn, cin, cout, nullptr, nullptr);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -2150,9 +2163,9 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* params)
     const SceneView S = make_scene(c);
     DN_CK(denoise_guide(c, S, st, c->d_dn_gx, c->d_dn_gn));
     if (timed) RT_HIP(c, hipEventRecord(c->dn_ev[1], st));
-    const FrameParams P = make_params(c, 0, 0, K_SPATIAL);
+    const FrameParams P = make_params(c, whole_launch(c), 0, 0, K_SPATIAL);
     const DnParams D = {d.iterations, d.sigma_luminance, d.sigma_plane, d.normal_power_log2, d.variance_radius};
-    const int g = launch_grid(c);
+    const int g = launch_grid(c, whole_launch(c));
     k_denoise_demod<<<g, BLOCK, 0, st>>>(P, c->d_trimat, c->d_accum, c->d_dn_gn, c->d_dn_col[1]);
     k_denoise_var<<<g, BLOCK, 0, st>>>(P, D, c->d_dn_gx, c->d_dn_gn, c->d_dn_col[1], c->d_dn_col[0]);
     RT_HIP(c, hipGetLastError());
@@ -2217,7 +2230,7 @@ int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_de
     const SceneView S = make_scene(c);
     DN_CK(denoise_guide(c, S, st, c->d_dt_gx[cur], c->d_dt_gn[cur]));
     if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[1], st));
-    const FrameParams P = make_params(c, 0, 0, K_SPATIAL);
+    const FrameParams P = make_params(c, whole_launch(c), 0, 0, K_SPATIAL);
     const DnParams D = {d.iterations, d.sigma_luminance, d.sigma_plane, d.normal_power_log2, d.variance_radius};
     DnTemporal T;
     T.rg_origin = F3(c->dt_rg.origin[0], c->dt_rg.origin[1], c->dt_rg.origin[2]);
@@ -2226,7 +2239,7 @@ int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_de
     T.alpha_c = t.alpha_color;
     T.alpha_m = t.alpha_moments;
     T.has_history = c->dt_valid ? 1 : 0;
-    const int g = launch_grid(c);
+    const int g = launch_grid(c, whole_launch(c));
     float4 *gx = c->d_dt_gx[cur], *gn = c->d_dt_gn[cur], *mom = c->d_dt_mom[cur];
     k_denoise_temporal<<<g, BLOCK, 0, st>>>(P, T, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
                                             c->d_dt_mom[prev], c->d_dn_col[1], mom);
@@ -2303,7 +2316,7 @@ int rt_frame_stage_begin(rt_ctx* c, int frame, int stage, int clear_first)
     c->last_frame = frame;
     /* a spatial stage reads the shaded-bit rows from both lanes: (re)built here, on the main stream, if the halo flags
      * arrived after the raycast (cold frame of a strip) */
-    if (stage >= 1) { const int rc = refresh_shaded_bits(c); if (rc != RT_OK) return rc; }
+    if (stage >= 1) { const int rc = refresh_shaded_bits(c, whole_launch(c)); if (rc != RT_OK) return rc; }
     RT_HIP(c, hipEventRecord(c->ev_stage, c->stream)); /* everything the stage reads is complete here */
     c->aux_used = false;
     c->fuse = HaloFuse{};
@@ -2335,10 +2348,22 @@ int rt_frame_stage_begin(rt_ctx* c, int frame, int stage, int clear_first)
     return RT_OK;
 }
 
-static int stage_run_ranges(rt_ctx* c, int frame, int stage, int part, int row0, int row1, int rowb0, int rowb1);
+static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part, int row0, int row1, int rowb0, int rowb1);
 int rt_frame_stage_run_part(rt_ctx* c, int frame, int stage, int part, int row0, int row1)
 {
-    return stage_run_ranges(c, frame, stage, part, row0, row1, 0, 0);
+    RT_CHECK_CTX(c);
+    return stage_run_ranges(c, whole_launch(c), frame, stage, part, row0, row1, 0, 0);
+}
+/* the stage's second lane: the second stream, ordered behind rt_frame_stage_begin / _fork at its first use; the per-kernel
+ * events belong to the main lane */
+static int second_lane(rt_ctx* c, Launch& lane)
+{
+    if (!c->aux_used) RT_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_stage, 0));
+    c->aux_used = true;
+    lane = whole_launch(c);
+    lane.stream = c->aux_stream;
+    lane.timed = false;
+    return RT_OK;
 }
 /* the stage's kernels over up to two disjoint row ranges in ONE launch each (a strip's two boundary bands);
  * ranges: n x {row0, row1}, n = 1 or 2; lane 1 = the second stream (as rt_frame_stage_run_async) */
@@ -2347,21 +2372,13 @@ int rt_frame_stage_run_ranges(rt_ctx* c, int frame, int stage, int part, int n, 
     RT_CHECK_CTX(c);
     if (!ranges || n < 1 || n > 2) RT_FAIL(c, RT_ERR_ARG, "1 or 2 row ranges");
     if (n == 2 && !(ranges[1] <= ranges[2] || ranges[3] <= ranges[0])) RT_FAIL(c, RT_ERR_ARG, "row ranges overlap");
-    if (!lane) return stage_run_ranges(c, frame, stage, part, ranges[0], ranges[1], n == 2 ? ranges[2] : 0, n == 2 ? ranges[3] : 0);
-    if (!c->aux_used) RT_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_stage, 0));
-    c->aux_used = true;
-    hipStream_t main_stream = c->stream;
-    const bool timing = c->timing;
-    c->stream = c->aux_stream;
-    c->timing = false;
-    const int rc = stage_run_ranges(c, frame, stage, part, ranges[0], ranges[1], n == 2 ? ranges[2] : 0, n == 2 ? ranges[3] : 0);
-    c->stream = main_stream;
-    c->timing = timing;
-    return rc;
+    Launch run = whole_launch(c);
+    if (lane) { const int rc = second_lane(c, run); if (rc != RT_OK) return rc; }
+    return stage_run_ranges(c, run, frame, stage, part, ranges[0], ranges[1], n == 2 ? ranges[2] : 0, n == 2 ? ranges[3] : 0);
 }
-static int stage_run_ranges(rt_ctx* c, int frame, int stage, int part, int row0, int row1, int rowb0, int rowb1)
+/* L: the lane (the stream the stage's kernels go to, whether its per-kernel events are recorded); its rows and tag are set here */
+static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part, int row0, int row1, int rowb0, int rowb1)
 {
-    RT_CHECK_CTX(c);
     NEED_SCENE(c);
     if (stage != c->f_stage) RT_FAIL(c, RT_ERR_STATE, "rt_frame_stage_run: expected stage %d, got %d", c->f_stage, stage);
     if (row0 < c->row_begin) row0 = c->row_begin;
@@ -2371,42 +2388,41 @@ static int stage_run_ranges(rt_ctx* c, int frame, int stage, int part, int row0,
     if (rowb0 >= rowb1) rowb0 = rowb1 = 0;
     if (row0 >= row1) { row0 = rowb0; row1 = rowb1; rowb0 = rowb1 = 0; }
     if (row0 >= row1) return RT_OK;
-    c->subb0 = rowb0; c->subb1 = rowb1;
+    L.row0 = row0; L.row1 = row1; L.rowb0 = rowb0; L.rowb1 = rowb1;
+    L.tag = c->frame_tag; /* launches of the staged frame write / trust own-visibility flags under the frame's tag */
     const int passes = c->opt.spatial_resampling_passes;
     const bool whole = row0 == c->row_begin && row1 == c->row_end && rowb0 >= rowb1;
-    const bool T = c->timing && whole;
-    auto mark = [&](int i) { if (T && i <= 8) hipEventRecord(c->ev[i], c->stream); };
-    c->sub0 = row0; c->sub1 = row1;
-    c->cur_tag = c->frame_tag; /* launches of the staged frame write / trust own-visibility flags under the frame's tag */
+    const bool T = L.timed && whole;
+    auto mark = [&](int i) { if (T && i <= 8) hipEventRecord(c->ev[i], L.stream); };
     int rc = RT_OK;
     if (stage == 0)
     {
         mark(0);
-        if (part != 2 && c->f_clear) rc = rt_clear(c);
+        if (part != 2 && c->f_clear) rc = clear_rows(c, L);
         mark(1);
         bool deferred = false; /* the primary rays are traced by the candidates' launch */
-        if (part != 2 && rc == RT_OK) rc = raycast_or_take(c, whole, frame, part == 0 && whole && use_fused_stage0(c), &deferred);
+        if (part != 2 && rc == RT_OK) rc = raycast_or_take(c, L, whole, frame, part == 0 && whole && use_fused_stage0(c), &deferred);
         if (part != 2) c->stage0_one_launch = deferred;
-        if (part != 2 && rc == RT_OK && row0 == c->row_begin && row1 == c->row_end && !deferred) rc = refresh_shaded_bits(c);
+        if (part != 2 && rc == RT_OK && row0 == c->row_begin && row1 == c->row_end && !deferred) rc = refresh_shaded_bits(c, L);
         mark(2);
         if (part != 1 && rc == RT_OK && !c->gen_taken)
         {
-            rc = join_tail_for(c, c->fY); /* this frame's candidates may go where the previous frame's resolve still reads */
-            if (rc == RT_OK) rc = launch_generate(c, frame, c->fY, c->fX, c->opt.use_temporal_resampling != 0, deferred ? c->d_vis : nullptr);
+            rc = join_tail_for(c, L, c->fY); /* this frame's candidates may go where the previous frame's resolve still reads */
+            if (rc == RT_OK) rc = launch_generate(c, L, frame, c->fY, c->fX, c->opt.use_temporal_resampling != 0, deferred ? L.vis : nullptr);
         }
-        if (deferred && rc == RT_OK) rc = refresh_shaded_bits(c);
+        if (deferred && rc == RT_OK) rc = refresh_shaded_bits(c, L);
         mark(3);
     }
     else if (stage <= passes)
     {
         const int k = stage - 1;
-        rc = join_tail_for(c, c->f_out); /* the pass's output buffer can be the one the previous frame's resolve reads */
+        rc = join_tail_for(c, L, c->f_out); /* the pass's output buffer can be the one the previous frame's resolve reads */
         if (rc == RT_OK && k == passes - 1 && use_fused_final(c))
         {
-            rc = join_tail(c); /* the kernel writes the accumulation buffer and the pixels the previous frame's tail writes */
-            if (rc == RT_OK) rc = launch_spatial(c, frame, k, c->f_in, c->f_out, true);
+            rc = join_tail(c, L); /* the kernel writes the accumulation buffer and the pixels the previous frame's tail writes */
+            if (rc == RT_OK) rc = launch_spatial(c, L, frame, k, c->f_in, c->f_out, true);
         }
-        else if (rc == RT_OK) rc = launch_spatial(c, frame, k, c->f_in, c->f_out);
+        else if (rc == RT_OK) rc = launch_spatial(c, L, frame, k, c->f_in, c->f_out);
         if (k < 3) mark(4 + k);
     }
     else
@@ -2422,46 +2438,36 @@ static int stage_run_ranges(rt_ctx* c, int frame, int stage, int part, int row0,
         {
             /* the last pass has shaded (and, key 20, tone-mapped) these rows already */
             mark(7);
-            if (!c->tune_fuse_tonemap) rc = launch_tone_mapping(c);
+            if (!c->tune_fuse_tonemap) rc = launch_tone_mapping(c, L);
             mark(8);
-            c->sub0 = c->sub1 = -1;
-            c->subb0 = c->subb1 = 0;
-            c->cur_tag = 0u;
             return rc;
         }
-        const bool tail = whole && use_tail(c);
-        hipStream_t ms = c->stream;
+        const bool tail = whole && use_tail(c, L.timed); /* never while timed: mark() records on L.stream */
+        Launch R = L;
         if (tail)
         {
             /* resolve + tone_mapping on the tail stream, behind everything enqueued so far (and behind the previous
              * frame's tail: same stream); the main stream does not wait for them */
-            RT_HIP(c, hipEventRecord(c->ev_tail_go, ms));
+            RT_HIP(c, hipEventRecord(c->ev_tail_go, L.stream));
             RT_HIP(c, hipStreamWaitEvent(c->tail_stream, c->ev_tail_go, 0));
-            c->stream = c->tail_stream;
+            R.stream = c->tail_stream;
         }
-        else rc = join_tail(c);
+        else rc = join_tail(c, L);
         /* tone_mapping reads the pixel's own accumulation value only (common/kernels/common.cu:30-74): k_resolve maps what it
          * has just written (r05; not the persistent-wavefront A/B form, which has no such parameter) */
         const bool fuse_tm = c->tune_fuse_tonemap != 0 && !c->tune_stream;
-        if (rc == RT_OK) rc = launch_resolve(c, final_phys, fuse_tm ? (uint32_t*)c->d_pixels : nullptr);
+        if (rc == RT_OK) rc = launch_resolve(c, R, final_phys, fuse_tm ? (uint32_t*)c->d_pixels : nullptr);
         mark(7);
-        if (rc == RT_OK && !fuse_tm) rc = launch_tone_mapping(c);
+        if (rc == RT_OK && !fuse_tm) rc = launch_tone_mapping(c, R);
         mark(8);
-        if (tail)
+        if (tail && rc == RT_OK)
         {
-            c->stream = ms;
-            if (rc == RT_OK)
-            {
-                RT_HIP(c, hipEventRecord(c->ev_tail, c->tail_stream));
-                c->tail_pending_main = true;
-                c->tail_phys = final_phys;
-            }
+            RT_HIP(c, hipEventRecord(c->ev_tail, c->tail_stream));
+            c->tail_pending_main = true;
+            c->tail_phys = final_phys;
         }
         c->resolve_on_tail = tail;
     }
-    c->sub0 = c->sub1 = -1;
-    c->subb0 = c->subb1 = 0;
-    c->cur_tag = 0u;
     return rc;
 }
 
@@ -2482,16 +2488,9 @@ int rt_frame_stage_fork(rt_ctx* c)
 int rt_frame_stage_run_async(rt_ctx* c, int frame, int stage, int part, int row0, int row1)
 {
     RT_CHECK_CTX(c);
-    if (!c->aux_used) RT_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_stage, 0));
-    c->aux_used = true;
-    hipStream_t main_stream = c->stream;
-    const bool timing = c->timing;
-    c->stream = c->aux_stream;
-    c->timing = false; /* the per-kernel events belong to the main lane */
-    const int rc = rt_frame_stage_run_part(c, frame, stage, part, row0, row1);
-    c->stream = main_stream;
-    c->timing = timing;
-    return rc;
+    Launch lane;
+    const int rc = second_lane(c, lane);
+    return rc != RT_OK ? rc : stage_run_ranges(c, lane, frame, stage, part, row0, row1, 0, 0);
 }
 
 /* all parts of the stage (part 0); stage 0 can be split: part 1 = [clear,] raycast, part 2 = generate */
@@ -2528,7 +2527,7 @@ int rt_frame_stage_end(rt_ctx* c, int stage)
         /* logical RT_RES_0 still equals the post-temporal reservoirs: materialise the copy the
          * reference's save_temporal_reservoir makes (10_restir_di.cpp:314-321) */
         const size_t n = local_pixels(c);
-        { const int jr = join_tail_for(c, X); if (jr != RT_OK) return jr; }
+        { const int jr = join_tail_for(c, whole_launch(c), X); if (jr != RT_OK) return jr; }
         c->rec_gserial[X] = c->rec_gserial[Y];
         RT_HIP(c, hipMemcpyAsync(c->d_rec[X], c->d_rec[Y], n * 64, hipMemcpyDeviceToDevice, c->stream));
         RT_HIP(c, hipMemcpyAsync(c->d_rad[X], c->d_rad[Y], n * 16, hipMemcpyDeviceToDevice, c->stream));
@@ -2691,7 +2690,7 @@ int rt_upload(rt_ctx* c, int buf, const void* src, size_t bytes)
             if (bytes != n * 16) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 16);
             NEED_SCENE(c);
             RT_HIP(c, hipMemcpyAsync(c->d_vis, src, bytes, hipMemcpyHostToDevice, c->stream));
-            FrameParams P = make_params(c, 0, 0);
+            FrameParams P = make_params(c, whole_launch(c), 0, 0);
             P.row0 = c->lrow0; P.row1 = c->lrow0 + c->lrows; /* all rows held, halos included */
             k_gbuffer_from_vis<<<tile_grid(c->W, c->lrows), BLOCK, 0, c->stream>>>(make_scene(c), P, c->d_vis, c->d_g0, c->d_g1);
             RT_HIP(c, hipGetLastError());
@@ -2854,13 +2853,12 @@ int rt_halo_mark_sides(rt_ctx* c, int frame, int pass, int n_pass, void* bitmaps
      * over all own rows when the bands meet) */
     const int lo_end = c->row_begin + c->halo < c->row_end ? c->row_begin + c->halo : c->row_end;
     const int hi_beg = c->row_end - c->halo > c->row_begin ? c->row_end - c->halo : c->row_begin;
-    if (bm[0] && bm[1] && lo_end < hi_beg) { c->sub0 = c->row_begin; c->sub1 = lo_end; c->subb0 = hi_beg; c->subb1 = c->row_end; }
-    else if (bm[0] && bm[1]) { c->sub0 = c->row_begin; c->sub1 = c->row_end; c->subb0 = c->subb1 = 0; }
-    else if (bm[0]) { c->sub0 = c->row_begin; c->sub1 = lo_end; c->subb0 = c->subb1 = 0; }
-    else { c->sub0 = hi_beg; c->sub1 = c->row_end; c->subb0 = c->subb1 = 0; }
-    const FrameParams P = make_params(c, frame, pass, K_OTHER);
-    const int grid = launch_grid(c);
-    c->sub0 = c->sub1 = -1; c->subb0 = c->subb1 = 0;
+    Launch L = whole_launch(c); /* its rows: the launch's extent */
+    if (bm[0] && bm[1] && lo_end < hi_beg) { L.row1 = lo_end; L.rowb0 = hi_beg; L.rowb1 = c->row_end; }
+    else if (bm[0] && !bm[1]) L.row1 = lo_end;
+    else if (!bm[0]) L.row0 = hi_beg;
+    const FrameParams P = make_params(c, L, frame, pass, K_OTHER);
+    const int grid = launch_grid(c, L);
     /* marks collected per workgroup in an LDS window, one global atomic per non-zero word (frame_kernels.h) where it applies */
     const bool window = c->tune_mark_window && (c->W % 32) == 0 && n_pass <= MARK_MAX_PASSES && halo_rows_needed(c->opt) <= SPL_HALO;
     if (window)
@@ -3110,12 +3108,13 @@ int rt_lane(rt_ctx* c, int second)
     if (second)
     {
         if (c->lane_saved) RT_FAIL(c, RT_ERR_STATE, "rt_lane(1) twice");
-        if (!c->aux_used) RT_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_stage, 0));
-        c->aux_used = true;
+        Launch lane;
+        const int rc = second_lane(c, lane);
+        if (rc != RT_OK) return rc;
         c->lane_main = c->stream;
         c->lane_timing = c->timing;
-        c->stream = c->aux_stream;
-        c->timing = false;
+        c->stream = lane.stream;
+        c->timing = lane.timed;
         c->lane_saved = true;
     }
     else if (c->lane_saved)
@@ -3132,7 +3131,7 @@ int rt_ray_count(rt_ctx* c, uint64_t* rays, uint64_t* shaded_pixels)
     RT_CHECK_CTX(c);
     if (!c->has_gbuffer) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
     RT_HIP(c, hipMemsetAsync(c->d_counter, 0, 8, c->stream));
-    k_count_shaded<<<launch_grid(c), BLOCK, 0, c->stream>>>(make_params(c, 0, 0), c->d_g1, c->d_counter);
+    k_count_shaded<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), 0, 0), c->d_g1, c->d_counter);
     RT_HIP(c, hipGetLastError());
     unsigned long long shaded = 0;
     RT_HIP(c, hipMemcpyAsync(&shaded, c->d_counter, 8, hipMemcpyDeviceToHost, c->stream));
@@ -3158,7 +3157,7 @@ int rt_ray_count(rt_ctx* c, uint64_t* rays, uint64_t* shaded_pixels)
             {
                 /* halo rows: G-buffer flags if the neighbours' were exchanged for this frame, else the records */
                 const bool g1_ok = (c->row_begin == c->lrow0 || c->halo_flags_epoch[0] == c->epoch) && (c->row_end == c->lrow0 + c->lrows || c->halo_flags_epoch[1] == c->epoch);
-                k_spatial_bytes<<<launch_grid(c), BLOCK, 0, c->stream>>>(make_params(c, c->last_frame, k), c->d_g1,
+                k_spatial_bytes<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), c->last_frame, k), c->d_g1,
                                                                         c->d_rec[c->res_map[RT_RES_TEMPORAL]], d, g1_ok);
             }
             RT_HIP(c, hipGetLastError());
@@ -3208,7 +3207,7 @@ int rt_exp_wave_clock(rt_ctx* c, int kernel, int pass, uint64_t* out, size_t n_w
         return RT_OK;
     }
     /* one-wavefront workgroups over 8 x 8 tiles at most: every order's grid fits in twice the tile count */
-    const size_t words = 16 * ((size_t)trace_grid(c) + 1024) + 8 * (size_t)launch_grid(c); /* k_raycast_quad: four workgroups per tile */
+    const size_t words = 16 * ((size_t)trace_grid(c, whole_launch(c)) + 1024) + 8 * (size_t)launch_grid(c, whole_launch(c)); /* k_raycast_quad: four workgroups per tile */
     if (kernel >= 0 && words > c->wave_clock_words)
     {
         if (c->d_wave_clock) hipFree(c->d_wave_clock);
@@ -3235,7 +3234,7 @@ int rt_exp_tile_perm(rt_ctx* c, int kernel, const uint32_t* perm, size_t n)
     if (c->d_tile_perm[kernel]) { hipFree(c->d_tile_perm[kernel]); c->d_tile_perm[kernel] = nullptr; c->tile_perm_n[kernel] = 0; }
     c->spec_valid = false; c->spec_gen_valid = false;
     if (n == 0) return RT_OK;
-    if (!perm || n != (size_t)trace_grid(c)) RT_FAIL(c, RT_ERR_ARG, "the permutation must cover the kernel's %d workgroups", trace_grid(c));
+    if (!perm || n != (size_t)trace_grid(c, whole_launch(c))) RT_FAIL(c, RT_ERR_ARG, "the permutation must cover the kernel's %d workgroups", trace_grid(c, whole_launch(c)));
     std::vector<uint8_t> seen(n, 0);
     for (size_t b = 0; b < n; ++b)
     {
@@ -3299,7 +3298,7 @@ int rt_spatial_bytes(rt_ctx* c, int frame, int pass, int in, uint64_t* bytes, ui
     unsigned long long* d = nullptr;
     RT_HIP(c, hipMalloc(&d, 24));
     RT_HIP(c, hipMemsetAsync(d, 0, 24, c->stream));
-    k_spatial_bytes<<<launch_grid(c), BLOCK, 0, c->stream>>>(make_params(c, frame, pass), c->d_g1, c->d_rec[c->res_map[in]], d);
+    k_spatial_bytes<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), frame, pass), c->d_g1, c->d_rec[c->res_map[in]], d);
     RT_HIP(c, hipGetLastError());
     unsigned long long h[2] = {0, 0};
     RT_HIP(c, hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, c->stream));
@@ -3439,7 +3438,7 @@ int rt_tuning(rt_ctx* c, int key, int value)
     else if (key == 13 && value >= -1 && value <= 1) c->tune_ws = value;
     else if (key == 15 && (value == 0 || value == 1)) c->tune_stream = value;
     else if (key == 16 && value >= -1 && value <= 2) c->tune_ws_primary = value;
-    else if (key == 14 && value >= -1 && value <= 2) { c->tune_spec = value; if (!use_next_raycast(c)) c->spec_valid = false; if (!use_next_generate(c)) c->spec_gen_valid = false; }
+    else if (key == 14 && value >= -1 && value <= 2) { c->tune_spec = value; if (!use_next_raycast(c, c->timing)) c->spec_valid = false; if (!use_next_generate(c, c->timing)) c->spec_gen_valid = false; }
     else if (key == 17 && value >= -1 && value <= 1) c->tune_tail = value;
     else if (key == 18 && (value == 0 || value == 1)) c->tune_mark_quick = value;
     else if (key == 19 && (value == 0 || value == 1)) c->tune_mark_window = value;
