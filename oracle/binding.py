@@ -310,6 +310,22 @@ def have_ref():
     return os.path.exists(REF_BIN)
 
 
+_ref_rays = None
+
+
+def have_ref_rays():
+    """oracle/_ref/ref_kernels is there AND was built from a driver that runs the reference's ray-using kernels (the commands
+    behind ref_raycast ... ref_frame). A binary of an older driver, which `make -C oracle` could not replace because the
+    reference checkout is absent, still serves the ray-less commands (have_ref) but not these."""
+    global _ref_rays
+    if _ref_rays is None:
+        try:
+            _ref_rays = have_ref() and b"rays" in subprocess.run([REF_BIN, "caps"], capture_output=True, timeout=60).stdout
+        except Exception:
+            _ref_rays = False
+    return _ref_rays
+
+
 REF_CAMERA_BIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_ref", "ref_camera")
 
 
@@ -374,6 +390,85 @@ def ref_run(cmd, **blobs):
         _write_blobs(fin, enc)
         subprocess.check_call([REF_BIN, cmd, fin, fout])
         return _read_blobs(fout)
+
+
+# The reference's ray-using kernels on the host. The intersection under them is the project's definition
+# (ref_driver.cpp "intersection by definition": brute force over the reference's intersect_ray_triangle), everything
+# around it is the reference's own code. `trace` is (pixels, 4) int32 in pixel order: rays traced, primID of the last
+# ray (-1 = miss), shadow rays (tmax 0.99) that hit, shadow rays that missed.
+TRACE_RAYS, TRACE_LAST, TRACE_SHADOW_HIT, TRACE_SHADOW_MISS = range(4)
+
+
+def _ref_trace(o):
+    return np.frombuffer(o["trace"], dtype=np.int32).reshape(-1, 4).copy()
+
+
+def _ref_res(o):
+    return np.frombuffer(o["res"], dtype=RESERVOIR).copy()
+
+
+def ref_raycast(W, H, tris, raygen):
+    o = ref_run("raycast", W=W, H=H, tris=tris, raygen=raygen)
+    return np.frombuffer(o["vis"], dtype=VISIBILITY).copy(), _ref_trace(o)
+
+
+def ref_generate_candidate(W, H, frame, tris, vis, eye, opt, lights):
+    o = ref_run("generate_candidate", W=W, H=H, frame=frame, tris=tris, vis=vis, options=opt, eye=np.asarray(eye, np.float32), lights=lights)
+    return _ref_res(o), _ref_trace(o)
+
+
+def ref_temporal_resampling(W, H, frame, tris, vis, eye, opt, prev, res):
+    o = ref_run("temporal_resampling", W=W, H=H, frame=frame, tris=tris, vis=vis, options=opt, eye=np.asarray(eye, np.float32), prev=prev, res=res)
+    return _ref_res(o), _ref_trace(o)
+
+
+def ref_spatial_resampling(W, H, frame, pas, tris, vis, eye, opt, rin):
+    """non-shaded pixels of the result are unwritten (0xCD bytes), 10_restir_di.cu:275-287"""
+    o = ref_run("spatial_resampling", W=W, H=H, frame=frame, tris=tris, vis=vis, options=opt, eye=np.asarray(eye, np.float32), res=rin, **{"pass": pas})
+    return _ref_res(o), _ref_trace(o)
+
+
+def ref_resolve(W, H, tris, vis, eye, opt, res, accum):
+    o = ref_run("resolve", W=W, H=H, frame=0, tris=tris, vis=vis, options=opt, eye=np.asarray(eye, np.float32), res=res,
+                accum=np.ascontiguousarray(accum, np.float32))
+    return np.frombuffer(o["accum"], dtype=np.float32).reshape(-1, 4).copy(), _ref_trace(o)
+
+
+def ref_path_trace(example, W, H, frame, tris, raygen, opt, accum, lights):
+    o = ref_run("path_trace", W=W, H=H, example=example, frame=frame, tris=tris, raygen=raygen, options=opt, lights=lights,
+                accum=np.ascontiguousarray(accum, np.float32))
+    return np.frombuffer(o["accum"], dtype=np.float32).reshape(-1, 4).copy(), _ref_trace(o)
+
+
+def ref_ao(example, W, H, tris, raygen):
+    """kernelMain of examples/04_ao (example=4, its own loop) or examples/06_ao_hiprt (6, through the intersection by definition)"""
+    o = ref_run({4: "ao04", 6: "ao06"}[example], W=W, H=H, tris=tris, raygen=raygen)
+    return np.frombuffer(o["pixels"], dtype=np.uint8).reshape(H, W, 4).copy()
+
+
+def ref_frame(W, H, frame, tris, raygen, eye, opt, lights, state):
+    """One frame through the reference's kernels only, sequenced as 10_restir_di.cpp:257-379 (what Scene.frame restates).
+    Returns the rays the intersector counted. Non-shaded pixels of r0 / r1 are whatever the kernels left there."""
+    rays = 0
+    state["vis"], t = ref_raycast(W, H, tris, raygen)
+    rays += int(t[:, 0].sum())
+    vis = state["vis"]
+    state["r0"], t = ref_generate_candidate(W, H, frame, tris, vis, eye, opt, lights)
+    rays += int(t[:, 0].sum())
+    state["r0"], t = ref_temporal_resampling(W, H, frame, tris, vis, eye, opt, state["temporal"], state["r0"])
+    rays += int(t[:, 0].sum())
+    state["temporal"] = np.frombuffer(ref_run("save_temporal_reservoir", W=W, H=H, frame=frame, tris=tris, vis=vis, options=opt,
+                                              eye=np.asarray(eye, np.float32), res=state["r0"])["res"], dtype=RESERVOIR).copy()
+    src, dst = "r0", "r1"
+    for k in range(int(opt["spatial_resampling_passes"][0])):
+        if k != 0:
+            src, dst = dst, src
+        state[dst], t = ref_spatial_resampling(W, H, frame, k, tris, vis, eye, opt, state[src])
+        rays += int(t[:, 0].sum())
+    state["accum"], t = ref_resolve(W, H, tris, vis, eye, opt, state[dst], state["accum"])
+    rays += int(t[:, 0].sum())
+    state["pixels"] = np.frombuffer(ref_run("tone_mapping", W=W, H=H, accum=state["accum"])["pixels"], dtype=np.uint8).reshape(H, W, 4).copy()
+    return rays
 
 
 def ref_fn(name, x):

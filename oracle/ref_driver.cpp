@@ -11,19 +11,26 @@
  * with the ROCm clang++ (clang evaluates call arguments left to right like hipcc; the
  * reference relies on that order for its RNG draws, 10_restir_di.cu:88-89,310).
  *
- * What is NOT here: any stand-in for HIPRT or Orochi. The reference's HIPRT headers are
- * used as shipped (declarations only). The HIPRT device implementation is a missing
- * binary blob, so raytrace() (common/raytrace.hpp:18-43) cannot run: the executable is
- * linked with --unresolved-symbols=ignore-all and this driver only ever runs code paths
- * that never reach raytrace():
+ * HIPRT. The reference's HIPRT headers are used as shipped; they only DECLARE hiprtGlobalStack and
+ * hiprtGeomTraversalClosestCustomStack<...>, whose device implementation is a missing binary blob.
+ * This driver defines those members itself (section "intersection by definition" below). That code
+ * is THIS PROJECT'S DEFINITION of the intersection, NOT HIPRT: DESIGN.md section 2 defines raytrace()
+ * (common/raytrace.hpp:18-43) as the closest hit of the reference's own intersect_ray_triangle
+ * (common/core.hpp:91-136) over all triangles in index order, the interval [tmin, tmax] inclusive,
+ * ties going to the highest index, exactly as examples/04_ao/04_ao.cu:8-29 loops. It pins nothing
+ * about the intersection (that stays pinned by definition only), but with it raytrace(),
+ * check_visibility() and every kernel AROUND the ray run unmodified on the host:
  *   - every inline function of common/{rng,core,camera,math,reservoir}.hpp;
- *   - examples/04_ao/04_ao.cu kernelMain (brute force, HIPRT-free)            [config #1]
- *   - generate_candidate with use_visibility_reuse = use_shadowed_target_function = false
- *   - temporal_resampling / spatial_resampling with use_shadowed_target_function = false
- *   - save_temporal_reservoir, clear, tone_mapping.
- * raycast, the ray of resolve and the visibility-reuse ray of generate_candidate stay unpinned by
- * the reference (DESIGN.md "Oracle"); resolve's ARITHMETIC is pinned through the reference's own functions with the ray's
- * answer V as an input (cmd_fn id 12, ref::resolve_arithmetic below).
+ *   - examples/04_ao/04_ao.cu kernelMain and examples/06_ao_hiprt/06_ao_hiprt.cu kernelMain;
+ *   - examples/10_restir_di: raycast, generate_candidate, temporal_resampling, save_temporal_reservoir,
+ *     spatial_resampling (visibility reuse and the shadowed target function included), resolve;
+ *   - the path_trace kernels of examples/07_pt, 08_nee and 09_ris;
+ *   - clear, tone_mapping.
+ * The executable links with no unresolved symbol allowed: a reach into real HIPRT is a link error.
+ * The ray-using commands also write `trace`, four int32 per pixel recorded by the intersector while
+ * the reference's kernel ran that pixel: rays traced, primID of the last ray (-1 = miss), shadow rays
+ * (tmax == 0.99f, raytrace.hpp:49) that hit, shadow rays that missed. Tests take their "this input is
+ * not trivial" counts from it.
  *
  * Kernel parameters of type TypedBuffer<T> are declared by value in the reference; the
  * type has a deleted copy constructor, so the Itanium C++ ABI passes it by invisible
@@ -67,7 +74,7 @@ namespace ref
 /* The ARITHMETIC of the reference's resolve kernel (examples/10_restir_di/10_restir_di.cu:433-458) on given operands, through
  * the reference's own functions, constants and vector operators, statement for statement and operand for operand in the kernel's
  * order (`1.0f / PI * color`, `brdf * G * V * radiance * ucw`, the float4 `+=` / `=` of the accumulation). The kernel itself
- * cannot run here: its V = check_visibility(...) reaches raytrace(), i.e. HIPRT, a missing binary — so V is an INPUT. This is what
+ * runs too (command `resolve`); here V is an INPUT, so that values of V the scene never produces are covered. This is what
  * pins the expression order of the oracle's o_resolve. */
 static float4 resolve_arithmetic(float3 color, float3 surf_p, float3 surf_n, float3 hit_position, float3 hit_normal, float3 sample_radiance,
                                  float ucw, float V, bool accumulate, float4 accumulation)
@@ -89,6 +96,89 @@ namespace ref_ao
 using namespace ref;
 #include "examples/04_ao/04_ao.cu"
 }  // namespace ref_ao
+
+/* ------------------------------------------------------------ intersection by definition
+ * THE PROJECT'S DEFINITION OF THE INTERSECTION, NOT HIPRT (see the header). The two `_impl` class
+ * templates only have to be complete types of the size and alignment hiprt_common.h asserts
+ * (48 B / 8 and 128 B / 16); the ray and the geometry live beside them, per host thread.
+ * hiprtGeometry (a void*) points at a GeomByDefinition. */
+namespace ref
+{
+struct GeomByDefinition { const Triangle* tris; int n; };
+struct TraceRecord { int rays, last_prim, shadow_hit, shadow_miss; };
+static thread_local struct { hiprtRay ray; const GeomByDefinition* g; } g_trav;
+static thread_local TraceRecord g_rec;
+
+template <typename E, bool D> class alignas(8) hiprtGlobalStack_impl { public: uint32_t unused[12]; };
+template <typename S, hiprtPrimitiveNodeType P, hiprtTraversalType T>
+class alignas(16) hiprtGeomTraversalCustomStack_impl { public: uint32_t unused[32]; };
+
+hiprtGlobalStack::hiprtGlobalStack(hiprtGlobalStackBuffer, hiprtSharedStackBuffer) {}
+hiprtGlobalStack::~hiprtGlobalStack() {}
+
+/* generic member templates: raytrace.hpp has already instantiated the class, a specialisation would come too late */
+template <typename S>
+hiprtGeomTraversalClosestCustomStack<S>::hiprtGeomTraversalClosestCustomStack(hiprtGeometry geom, const hiprtRay& ray, S&, hiprtTraversalHint,
+                                                                             void*, hiprtFuncTable, uint32_t)
+{
+    g_trav.ray = ray;
+    g_trav.g = (const GeomByDefinition*)geom;
+}
+template <typename S>
+hiprtHit hiprtGeomTraversalClosestCustomStack<S>::getNextHit()
+{
+    const hiprtRay& r = g_trav.ray;
+    const float3 ro = make_float3(r.origin.x, r.origin.y, r.origin.z), rd = make_float3(r.direction.x, r.direction.y, r.direction.z);
+    float t = r.maxT, bu = 0.0f, bv = 0.0f;
+    int index = -1;
+    for (int i = 0; i < g_trav.g->n; ++i) /* 04_ao.cu:14-24 with the ray's own interval */
+    {
+        const Triangle& tri = g_trav.g->tris[i];
+        float u, v;
+        if (intersect_ray_triangle(&t, &u, &v, ro, rd, r.minT, t, tri.vertices[0], tri.vertices[1], tri.vertices[2]))
+        {
+            index = i; bu = u; bv = v;
+        }
+    }
+    hiprtHit h;
+    h.primID = index < 0 ? hiprtInvalidValue : (uint32_t)index;
+    h.t = t;
+    h.uv = {bu, bv};
+    ++g_rec.rays;
+    g_rec.last_prim = index;
+    if (r.maxT == 0.99f) { if (index < 0) ++g_rec.shadow_miss; else ++g_rec.shadow_hit; }
+    return h;
+}
+}  // namespace ref
+/* KERNEL gives C linkage: the three path_trace and the second kernelMain get names of their own */
+namespace ref_ao06
+{
+using namespace ref;
+#define kernelMain kernelMain_06
+#include "examples/06_ao_hiprt/06_ao_hiprt.cu"
+#undef kernelMain
+}  // namespace ref_ao06
+namespace ref_pt07
+{
+using namespace ref;
+#define path_trace path_trace_07
+#include "examples/07_pt/07_pt.cu"
+#undef path_trace
+}  // namespace ref_pt07
+namespace ref_pt08
+{
+using namespace ref;
+#define path_trace path_trace_08
+#include "examples/08_nee/08_nee.cu"
+#undef path_trace
+}  // namespace ref_pt08
+namespace ref_pt09
+{
+using namespace ref;
+#define path_trace path_trace_09
+#include "examples/09_ris/09_ris.cu"
+#undef path_trace
+}  // namespace ref_pt09
 
 /* ------------------------------------------------------------ blob files */
 typedef std::map<std::string, std::vector<uint8_t>> Blobs;
@@ -139,20 +229,33 @@ static void view(ref::TypedBuffer<T>& tb, T* data, size_t n)
     tb.m_size = n;
 }
 
+/* one host thread runs the grid, thread by thread; `trace` (optional, 4 int32 per thread id) receives what the
+ * intersector recorded while that thread ran */
 template <class K>
-static void run_grid(int n_threads, K&& body)
+static void run_grid(int n_threads, K&& body, std::vector<ref::TraceRecord>* trace = nullptr)
 {
     blockDim.x = 256; blockDim.y = blockDim.z = 1;
     const int blocks = (n_threads + 255) / 256;
+    if (trace) trace->assign((size_t)n_threads, ref::TraceRecord{0, -1, 0, 0});
     for (int b = 0; b < blocks; ++b)
     {
         blockIdx.x = b; blockIdx.y = blockIdx.z = 0;
         for (int t = 0; t < 256; ++t)
         {
             threadIdx.x = t; threadIdx.y = threadIdx.z = 0;
+            ref::g_rec = ref::TraceRecord{0, -1, 0, 0};
             body();
+            const int tid = b * 256 + t;
+            if (trace && tid < n_threads) (*trace)[(size_t)tid] = ref::g_rec;
         }
     }
+}
+/* thread id -> pixel index, as every kernel computes it */
+static void write_trace(FILE* out, const std::vector<ref::TraceRecord>& tr, int W, int H)
+{
+    std::vector<ref::TraceRecord> px(tr.size());
+    for (int tid = 0; tid < W * H; ++tid) px[(size_t)((tid % W) + (H - tid / W - 1) * W)] = tr[(size_t)tid];
+    write_blob(out, "trace", px.data(), px.size() * sizeof(ref::TraceRecord));
 }
 
 using TBTri = ref::TypedBuffer<ref::Triangle>;
@@ -172,6 +275,11 @@ typedef void (*spatial_fn)(int, int, int, int, ref::hiprtGeometry, const TBTri&,
 typedef void (*clear_fn)(TBF4&, int, int);
 typedef void (*tone_fn)(TBU8&, TBF4&, int, int);
 typedef void (*ao_fn)(TBU8&, ref::RayGenerator, int, int, const TBTri&);
+typedef void (*ao06_fn)(TBU8&, ref::RayGenerator, int, int, ref::hiprtGeometry, TBTri&);
+typedef void (*raycast_fn)(int, int, ref::hiprtGeometry, const TBTri&, ref::RayGenerator, TBVis&);
+typedef void (*resolve_fn)(TBF4&, int, int, ref::hiprtGeometry, const TBTri&, const TBVis&, float3, ref::Options, const TBRes&);
+typedef void (*pt07_fn)(int, int, int, ref::hiprtGeometry, const TBTri&, ref::RayGenerator, ref::Options, TBF4&);
+typedef void (*pt089_fn)(int, int, int, ref::hiprtGeometry, const TBTri&, const TBU32&, ref::RayGenerator, ref::Options, TBF4&);
 
 static int cmd_kat()
 {
@@ -286,6 +394,7 @@ int main(int argc, char** argv)
     if (argc < 2) { fprintf(stderr, "usage: ref_kernels <cmd> [in.bin out.bin]\n"); return 2; }
     const std::string cmd = argv[1];
     if (cmd == "kat") return cmd_kat();
+    if (cmd == "caps") { printf("rays\n"); return 0; } /* this build runs the ray-using kernels (binding.have_ref_rays) */
     if (argc < 4) { fprintf(stderr, "need in/out files\n"); return 2; }
     Blobs b = read_blobs(argv[2]);
     FILE* out = fopen(argv[3], "wb");
@@ -323,6 +432,57 @@ int main(int argc, char** argv)
         run_grid(N, [&] { f(pix, rg, W, H, tris); });
         write_blob(out, "pixels", px.data(), px.size());
     }
+    else if (cmd == "ao06")
+    {
+        TBTri tris; view(tris, ptr<ref::Triangle>(b, "tris"), count<ref::Triangle>(b, "tris"));
+        ref::GeomByDefinition g{tris.m_data, (int)tris.m_size};
+        ref::RayGenerator rg = *ptr<ref::RayGenerator>(b, "raygen");
+        std::vector<uint8_t> px((size_t)N * 4, 0);
+        TBU8 pix; view(pix, px.data(), px.size());
+        std::vector<ref::TraceRecord> tr;
+        auto f = reinterpret_cast<ao06_fn>(&ref_ao06::kernelMain_06);
+        run_grid(N, [&] { f(pix, rg, W, H, (ref::hiprtGeometry)&g, tris); }, &tr);
+        write_blob(out, "pixels", px.data(), px.size());
+        write_trace(out, tr, W, H);
+    }
+    else if (cmd == "raycast")
+    {
+        TBTri tris; view(tris, ptr<ref::Triangle>(b, "tris"), count<ref::Triangle>(b, "tris"));
+        ref::GeomByDefinition g{tris.m_data, (int)tris.m_size};
+        ref::RayGenerator rg = *ptr<ref::RayGenerator>(b, "raygen");
+        std::vector<ref::Visibility> v((size_t)N);
+        memset((void*)v.data(), 0xCD, sizeof(ref::Visibility) * (size_t)N);
+        TBVis vis; view(vis, v.data(), v.size());
+        std::vector<ref::TraceRecord> tr;
+        auto f = reinterpret_cast<raycast_fn>(&ref::raycast);
+        run_grid(N, [&] { f(W, H, (ref::hiprtGeometry)&g, tris, rg, vis); }, &tr);
+        write_blob(out, "vis", v.data(), sizeof(ref::Visibility) * (size_t)N);
+        write_trace(out, tr, W, H);
+    }
+    else if (cmd == "path_trace")
+    {
+        TBTri tris; view(tris, ptr<ref::Triangle>(b, "tris"), count<ref::Triangle>(b, "tris"));
+        ref::GeomByDefinition g{tris.m_data, (int)tris.m_size};
+        ref::RayGenerator rg = *ptr<ref::RayGenerator>(b, "raygen");
+        ref::Options opt = *ptr<ref::Options>(b, "options");
+        const int example = geti(b, "example"), frame = geti(b, "frame");
+        TBF4 acc; view(acc, ptr<float4>(b, "accum"), (size_t)N);
+        std::vector<ref::TraceRecord> tr;
+        if (example == 7)
+        {
+            auto f = reinterpret_cast<pt07_fn>(&ref_pt07::path_trace_07);
+            run_grid(N, [&] { f(W, H, frame, (ref::hiprtGeometry)&g, tris, rg, opt, acc); }, &tr);
+        }
+        else if (example == 8 || example == 9)
+        {
+            TBU32 lights; view(lights, ptr<uint32_t>(b, "lights"), count<uint32_t>(b, "lights"));
+            auto f = example == 8 ? reinterpret_cast<pt089_fn>(&ref_pt08::path_trace_08) : reinterpret_cast<pt089_fn>(&ref_pt09::path_trace_09);
+            run_grid(N, [&] { f(W, H, frame, (ref::hiprtGeometry)&g, tris, lights, rg, opt, acc); }, &tr);
+        }
+        else { fprintf(stderr, "path_trace: example must be 7, 8 or 9\n"); return 2; }
+        write_blob(out, "accum", acc.m_data, (uint64_t)N * 16);
+        write_trace(out, tr, W, H);
+    }
     else
     {
         TBTri tris; view(tris, ptr<ref::Triangle>(b, "tris"), count<ref::Triangle>(b, "tris"));
@@ -330,24 +490,17 @@ int main(int argc, char** argv)
         ref::Options opt = *ptr<ref::Options>(b, "options");
         const float3 eye = f3(ptr<float>(b, "eye"));
         const int frame = geti(b, "frame");
-        if (opt.use_shadowed_target_function)
-        {
-            fprintf(stderr, "shadowed target function needs HIPRT: not runnable\n");
-            return 3;
-        }
+        ref::GeomByDefinition g{tris.m_data, (int)tris.m_size};
+        const ref::hiprtGeometry geom = (ref::hiprtGeometry)&g;
+        std::vector<ref::TraceRecord> tr;
         if (cmd == "generate_candidate")
         {
-            if (opt.use_visibility_reuse)
-            {
-                fprintf(stderr, "visibility reuse needs HIPRT: not runnable\n");
-                return 3;
-            }
             TBU32 lights; view(lights, ptr<uint32_t>(b, "lights"), count<uint32_t>(b, "lights"));
             std::vector<ref::Reservoir> r((size_t)N);
             memset((void*)r.data(), 0xCD, sizeof(ref::Reservoir) * (size_t)N);
             TBRes res; view(res, r.data(), r.size());
             auto f = reinterpret_cast<gen_fn>(&ref::generate_candidate);
-            run_grid(N, [&] { f(W, H, frame, nullptr, tris, vis, eye, lights, opt, res); });
+            run_grid(N, [&] { f(W, H, frame, geom, tris, vis, eye, lights, opt, res); }, &tr);
             write_blob(out, "res", r.data(), sizeof(ref::Reservoir) * (size_t)N);
         }
         else if (cmd == "temporal_resampling")
@@ -355,7 +508,7 @@ int main(int argc, char** argv)
             TBRes prev; view(prev, ptr<ref::Reservoir>(b, "prev"), (size_t)N);
             TBRes res; view(res, ptr<ref::Reservoir>(b, "res"), (size_t)N);
             auto f = reinterpret_cast<temporal_fn>(&ref::temporal_resampling);
-            run_grid(N, [&] { f(W, H, frame, nullptr, tris, vis, eye, opt, prev, res); });
+            run_grid(N, [&] { f(W, H, frame, geom, tris, vis, eye, opt, prev, res); }, &tr);
             write_blob(out, "res", res.m_data, sizeof(ref::Reservoir) * (size_t)N);
         }
         else if (cmd == "save_temporal_reservoir")
@@ -375,10 +528,19 @@ int main(int argc, char** argv)
             memset((void*)o.data(), 0xCD, sizeof(ref::Reservoir) * (size_t)N);
             TBRes outb; view(outb, o.data(), o.size());
             auto f = reinterpret_cast<spatial_fn>(&ref::spatial_resampling);
-            run_grid(N, [&] { f(W, H, frame, pass, nullptr, tris, vis, eye, opt, in, outb); });
+            run_grid(N, [&] { f(W, H, frame, pass, geom, tris, vis, eye, opt, in, outb); }, &tr);
             write_blob(out, "res", o.data(), sizeof(ref::Reservoir) * (size_t)N);
         }
+        else if (cmd == "resolve")
+        {
+            TBRes res; view(res, ptr<ref::Reservoir>(b, "res"), (size_t)N);
+            TBF4 acc; view(acc, ptr<float4>(b, "accum"), (size_t)N);
+            auto f = reinterpret_cast<resolve_fn>(&ref::resolve);
+            run_grid(N, [&] { f(acc, W, H, geom, tris, vis, eye, opt, res); }, &tr);
+            write_blob(out, "accum", acc.m_data, (uint64_t)N * 16);
+        }
         else { fprintf(stderr, "unknown command %s\n", cmd.c_str()); return 2; }
+        if (!tr.empty()) write_trace(out, tr, W, H);
     }
     fclose(out);
     return 0;

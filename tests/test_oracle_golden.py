@@ -32,7 +32,7 @@ def _libm(oracle):
 FNS = ["warp_unit_triangle", "sample_hemisphere", "sample_2d_gaussian", "geometry_term", "intersect_ray_triangle",
        "luminance", "normal_rejection", "depth_rejection", "triangle_props", "aces", "surface_ray", "tangent_world",
        # the arithmetic of resolve (10_restir_di.cu:433-458) through the reference's own functions and operators, the shadow ray's
-       # answer V given (the kernel itself needs HIPRT): pins the expression order of the oracle's o_resolve
+       # answer V given (the kernel itself: tests/test_oracle_reference_rays.py): pins the expression order of the oracle's o_resolve
        "resolve_arithmetic"]
 
 
