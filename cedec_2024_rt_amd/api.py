@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .types import OPTIONS, RAYGEN, RESERVOIR, TRIANGLE, VISIBILITY, default_options
+from .types import OPTIONS, RAYGEN, RESERVOIR, TRIANGLE, VISIBILITY, TraceMode, Tune, default_options  # noqa: F401 (re-exported)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librestir_rt.so")
@@ -736,15 +736,15 @@ class Renderer:
         return st & 0xFFFF
 
     def trace_occluded_ws(self, rays):
-        """any-hit answers of the work-sharing walk (trace mode 5; rays with tmax < 0 are lanes without a ray), plus the
+        """any-hit answers of the work-sharing walk (TraceMode.OCCLUDED_WS; rays with tmax < 0 are lanes without a ray), plus the
         passes each ray's wavefront ran and the steals of each lane"""
         rr = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         raw = np.zeros((len(rr), 2), dtype=np.uint32)
-        self._ck(self.L.rt_trace_mode(self.h, 5))
+        self._ck(self.L.rt_trace_mode(self.h, TraceMode.OCCLUDED_WS))
         try:
             self._ck(self.L.rt_trace_stats(self.h, _p(rr), len(rr), _p(raw)))
         finally:
-            self._ck(self.L.rt_trace_mode(self.h, 0))
+            self._ck(self.L.rt_trace_mode(self.h, TraceMode.WIDE))
         return (raw[:, 0] >> 31).astype(bool), raw[:, 0] & 0x7fff, raw[:, 1] & 0xffff
 
     def bvh_config(self, split_factor):
@@ -772,8 +772,8 @@ class Renderer:
                     3: "device pre-split + top-down binned SAH (32 bins) + 4-wide collapse, all on the GPU"}
 
     def bvh_builder(self):
-        """name of the builder this context's rt_scene_set used / will use (rt_tuning key 5)"""
-        return self.BVH_BUILDERS.get(self.tuning_get(5), "?")
+        """name of the builder this context's rt_scene_set used / will use (Tune.BVH_BUILDER)"""
+        return self.BVH_BUILDERS.get(self.tuning_get(Tune.BVH_BUILDER), "?")
 
     def build_ms(self):
         ms = C.c_float()

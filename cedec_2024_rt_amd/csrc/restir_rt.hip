@@ -9,6 +9,7 @@
  * Compile with -ffp-contract=off (parity contract, rt_device.h).
  */
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -350,6 +351,16 @@ static SceneView make_scene(const rt_ctx* c)
     return S;
 }
 static size_t local_pixels(const rt_ctx* c) { return (size_t)c->W * (size_t)c->lrows; }
+
+/* for the tables of rt_trace_mode and rt_tuning at the end of the file (templates cannot live inside extern "C") */
+template <class Row, int N> static constexpr bool rows_in_order(const Row (&rows)[N], int count, int Row::*id)
+{
+    if (N != count) return false;
+    for (int i = 0; i < N; ++i)
+        if (rows[i].*id != i) return false;
+    return true;
+}
+template <int LO, int HI> static bool within(int v) { return v >= LO && v <= HI; }
 
 extern "C" {
 
@@ -3309,14 +3320,68 @@ int rt_spatial_bytes(rt_ctx* c, int frame, int pass, int in, uint64_t* bytes, ui
     return RT_OK;
 }
 
-/* the binary tree is built by rt_scene_set only: after an rt_scene_update the walks of it refuse */
+/* ---- trace modes (enum rt_trace_mode_id): ONE row per mode holds what rt_trace_closest and rt_trace_stats launch in it ---- */
+typedef hipError_t (*TraceLaunch)(rt_ctx* c, const float* d_rays, uint32_t n, void* d_out);
+/* name = one launch of a ray-list kernel in workgroups of `threads` over `rays` rays; out_t = float (hits) or uint32_t (counters) */
+#define TRACE_LAUNCH(name, out_t, threads, rays, ...) \
+    static hipError_t name(rt_ctx* c, const float* d_r, uint32_t n, void* d_o) \
+    { __VA_ARGS__<<<(n + (rays) - 1) / (rays), threads, 0, c->stream>>>(make_scene(c), d_r, (int)n, (out_t*)d_o); return hipGetLastError(); }
+#ifdef RT_EXPERIMENTS
+#define RT_EXP(launch) launch
+static hipError_t trace_queue(rt_ctx* c, const float* d_r, uint32_t n, void* d_h) /* both queue modes: closest / any hit */
+{
+    unsigned int* d_head = (unsigned int*)c->d_counter;
+    if (hipError_t e = hipMemsetAsync(d_head, 0, 8, c->stream)) return e;
+    const int grid = 256 * 6; /* persistent: 6 workgroups per CU (24 KB LDS each) */
+    if (c->trace_mode == RT_TRACE_QUEUE_CLOSEST) k_trace_queue<false><<<grid, BLOCK, 0, c->stream>>>(make_scene(c).wide, d_r, (int)n, (float*)d_h, d_head);
+    else k_trace_queue<true><<<grid, BLOCK, 0, c->stream>>>(make_scene(c).wide, d_r, (int)n, (float*)d_h, d_head);
+    return hipGetLastError();
+}
+#else
+#define RT_EXP(launch) nullptr /* an A/B form of librestir_rt_exp.so */
+#endif
+TRACE_LAUNCH(trace_wide, float, 256, 256, k_trace_closest<0>)
+TRACE_LAUNCH(trace_wide_any, float, 256, 256, k_trace_closest<0, true>)
+TRACE_LAUNCH(trace_occluded_ws, float, TRACE_BLOCK, TRACE_BLOCK, k_trace_anyhit<true>)
+TRACE_LAUNCH(trace_occluded_lane, float, TRACE_BLOCK, TRACE_BLOCK, k_trace_anyhit<false>)
+#ifdef RT_EXPERIMENTS
+TRACE_LAUNCH(trace_closest_quad, float, TRACE_BLOCK, 16, k_trace_closest_quad)
+TRACE_LAUNCH(trace_binary, float, 256, 256, k_trace_closest<1>)
+#endif
+TRACE_LAUNCH(stats_ws, uint32_t, TRACE_BLOCK, TRACE_BLOCK, k_trace_stats_ws)
+TRACE_LAUNCH(stats_wide, uint32_t, 256, 256, k_trace_stats<0>)
+TRACE_LAUNCH(stats_wide_any, uint32_t, 256, 256, k_trace_stats<0, true>)
+#ifdef RT_EXPERIMENTS
+TRACE_LAUNCH(stats_binary, uint32_t, 256, 256, k_trace_stats<1>) /* also counts the modes that have no counting kernel of their own */
+#endif
+struct TraceRow
+{
+    int mode;
+    TraceLaunch closest; /* nullptr: this library does not carry the mode (rt_trace_mode: RT_ERR_UNSUPPORTED) */
+    bool closest_binary; /* walks the binary tree, which only rt_scene_set builds: refuses after an rt_scene_update */
+    TraceLaunch stats;   /* nullptr: this library has no counting kernel for the mode (rt_trace_stats: RT_ERR_UNSUPPORTED) */
+    bool stats_binary;
+};
+static constexpr TraceRow TRACE_MODES[] = {
+    {RT_TRACE_WIDE, trace_wide, false, stats_wide, false},
+    {RT_TRACE_BINARY, RT_EXP(trace_binary), true, RT_EXP(stats_binary), true},
+    {RT_TRACE_QUEUE_CLOSEST, RT_EXP(trace_queue), false, RT_EXP(stats_binary), true},
+    {RT_TRACE_QUEUE_ANY, RT_EXP(trace_queue), false, RT_EXP(stats_binary), true},
+    {RT_TRACE_WIDE_ANY, trace_wide_any, false, stats_wide_any, false},
+    {RT_TRACE_OCCLUDED_WS, trace_occluded_ws, false, stats_ws, false},
+    {RT_TRACE_OCCLUDED_LANE, trace_occluded_lane, false, RT_EXP(stats_binary), true},
+    {RT_TRACE_CLOSEST_QUAD, RT_EXP(trace_closest_quad), false, RT_EXP(stats_binary), true},
+};
+static_assert(rows_in_order(TRACE_MODES, RT_TRACE_MODE_COUNT, &TraceRow::mode), "TRACE_MODES: one row per mode, row i = mode i");
+
 #define RT_CHECK_BINARY_TREE(c, binary)                                                                                   \
     do { if ((binary) && (c)->bin_stale) RT_FAIL(c, RT_ERR_STATE, "trace mode %d walks the binary tree, which rt_scene_update does not refit", (c)->trace_mode); } while (0)
 int rt_trace_closest(rt_ctx* c, const float* rays, uint32_t n, float* hits)
 {
     RT_CHECK_CTX(c);
     if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "no scene");
-    RT_CHECK_BINARY_TREE(c, c->trace_mode == 1);
+    const TraceRow& mode = TRACE_MODES[c->trace_mode];
+    RT_CHECK_BINARY_TREE(c, mode.closest_binary);
     if (n == 0) return RT_OK;
     float *d_r = nullptr, *d_h = nullptr;
     RT_HIP(c, hipMalloc(&d_r, (size_t)n * 32));
@@ -3326,26 +3391,7 @@ int rt_trace_closest(rt_ctx* c, const float* rays, uint32_t n, float* hits)
     RT_HIP(c, hipEventCreate(&e0));
     RT_HIP(c, hipEventCreate(&e1));
     RT_HIP(c, hipEventRecord(e0, c->stream));
-#ifdef RT_EXPERIMENTS
-    if (c->trace_mode == 2 || c->trace_mode == 3)
-    {
-        unsigned int* d_head = (unsigned int*)c->d_counter;
-        RT_HIP(c, hipMemsetAsync(d_head, 0, 8, c->stream));
-        const int grid = 256 * 6; /* persistent: 6 workgroups per CU (24 KB LDS each) */
-        if (c->trace_mode == 2) k_trace_queue<false><<<grid, BLOCK, 0, c->stream>>>(make_scene(c).wide, d_r, (int)n, d_h, d_head);
-        else k_trace_queue<true><<<grid, BLOCK, 0, c->stream>>>(make_scene(c).wide, d_r, (int)n, d_h, d_head);
-    }
-    else
-#endif
-    if (c->trace_mode == 0) k_trace_closest<0><<<(n + 255) / 256, 256, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_h);
-    else if (c->trace_mode == 4) k_trace_closest<0, true><<<(n + 255) / 256, 256, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_h);
-    else if (c->trace_mode == 5) k_trace_anyhit<true><<<(n + TRACE_BLOCK - 1) / TRACE_BLOCK, TRACE_BLOCK, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_h);
-    else if (c->trace_mode == 6) k_trace_anyhit<false><<<(n + TRACE_BLOCK - 1) / TRACE_BLOCK, TRACE_BLOCK, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_h);
-#ifdef RT_EXPERIMENTS
-    else if (c->trace_mode == 7) k_trace_closest_quad<<<(n + 15) / 16, TRACE_BLOCK, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_h);
-    else k_trace_closest<1><<<(n + 255) / 256, 256, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_h);
-#endif
-    RT_HIP(c, hipGetLastError());
+    RT_HIP(c, mode.closest(c, d_r, n, d_h));
     RT_HIP(c, hipEventRecord(e1, c->stream));
     RT_HIP(c, hipMemcpyAsync(hits, d_h, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
@@ -3367,20 +3413,16 @@ int rt_trace_stats(rt_ctx* c, const float* rays, uint32_t n, uint32_t* stats)
 {
     RT_CHECK_CTX(c);
     if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "no scene");
-    RT_CHECK_BINARY_TREE(c, c->trace_mode != 0 && c->trace_mode != 4 && c->trace_mode != 5);
+    const TraceRow& mode = TRACE_MODES[c->trace_mode];
+    if (!mode.stats) RT_FAIL(c, RT_ERR_UNSUPPORTED, "trace mode %d has no counting kernel in this library (librestir_rt_exp.so counts it on the binary walk)", c->trace_mode);
+    RT_CHECK_BINARY_TREE(c, mode.stats_binary);
     if (n == 0) return RT_OK;
     float* d_r = nullptr;
     uint32_t* d_s = nullptr;
     RT_HIP(c, hipMalloc(&d_r, (size_t)n * 32));
     RT_HIP(c, hipMalloc(&d_s, (size_t)n * 8));
     RT_HIP(c, hipMemcpyAsync(d_r, rays, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    if (c->trace_mode == 5) k_trace_stats_ws<<<(n + TRACE_BLOCK - 1) / TRACE_BLOCK, TRACE_BLOCK, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_s);
-    else if (c->trace_mode == 0) k_trace_stats<0><<<(n + 255) / 256, 256, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_s);
-    else if (c->trace_mode == 4) k_trace_stats<0, true><<<(n + 255) / 256, 256, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_s);
-#ifdef RT_EXPERIMENTS
-    else k_trace_stats<1><<<(n + 255) / 256, 256, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_s);
-#endif
-    RT_HIP(c, hipGetLastError());
+    RT_HIP(c, mode.stats(c, d_r, n, d_s));
     RT_HIP(c, hipMemcpyAsync(stats, d_s, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     hipFree(d_r); hipFree(d_s);
@@ -3395,114 +3437,89 @@ int rt_bvh_config(rt_ctx* c, float split_factor)
     c->bvh_split_factor = split_factor;
     return RT_OK;
 }
-/* performance knobs (results never depend on them): keys 0..3 = tile order of raycast /
- * generate_candidate(+temporal) / spatial_resampling / resolve (0 row-major, 1 column-major inside
- * each XCD band); key 4 = extra LDS bytes per spatial workgroup (limits resident workgroups per CU). */
-/* keys / values that select code the product library does not carry (A/B forms measured and left off; csrc/Makefile builds
- * them into librestir_rt_exp.so with -DRT_EXPERIMENTS, which the variant tests and tools load) */
-static bool experiment_only(int key, int value)
+/* ---- performance knobs (enum rt_tuning_key; results never depend on them): ONE row per key holds all rt_tuning and
+ * rt_tuning_get know about it. Retiring an A/B form = narrowing its row's `accepts` and deleting its kernel. ---- */
+struct TuneRow
 {
-#ifdef RT_EXPERIMENTS
-    (void)key; (void)value;
-    return false;
-#else
-    switch (key)
-    {
-        case 5: return value != 3;                 /* BVH builders 0 (LBVH), 1 (host SAH), 2 (PLOC + host top): the default is 3 */
-        case 8: return value != 2;                 /* spatial pass forms: gather, LDS-staged bits, software-pipelined */
-        case 9: return value != -1 && value != RT_SPATIAL_GATHER_AUTO_WAVES; /* other register budgets of the pass */
-        case 10: return true;                      /* PLOC search radius (builder 2) */
-        case 11: case 12: case 15: return value != 0; /* deferred visibility queue, pipelined RIS loop form, resolve as a stream */
-        case 23: return value > 0;                 /* last pass + resolve in one kernel */
-        case 24: return value != 0;                /* half-density raycast with helper lanes */
-        case 16: return value == 2;                /* four lanes per primary ray */
-        default: return false;
-    }
-#endif
-}
+    int key;
+    const char* name;
+    int& (*field)(rt_ctx*);
+    bool (*accepts)(int);    /* the values of the key: anything else is RT_ERR_ARG */
+    bool (*product)(int);    /* those librestir_rt.so carries: for anything else it answers RT_ERR_UNSUPPORTED, BEFORE it looks at
+                                `accepts` (the rest are A/B forms measured and left off, which csrc/Makefile builds into
+                                librestir_rt_exp.so with -DRT_EXPERIMENTS; the variant tests and tools load that one) */
+    void (*on_set)(rt_ctx*); /* what else a new value invalidates; nullptr = nothing */
+};
+static bool any_value(int) { return true; }
+static bool no_value(int) { return false; }
+#define TUNE_ROW(KEY, FIELD, ...) {RT_TUNE_##KEY, "RT_TUNE_" #KEY, [](rt_ctx* c) -> int& { return c->FIELD; }, __VA_ARGS__}
+static constexpr TuneRow TUNING[] = {
+    TUNE_ROW(TILE_RAYCAST, tune_tile_mode[0], within<-1, 7>, any_value, nullptr),
+    TUNE_ROW(TILE_GENERATE, tune_tile_mode[1], within<-1, 7>, any_value, nullptr),
+    TUNE_ROW(TILE_SPATIAL, tune_tile_mode[2], within<-1, 7>, any_value, nullptr),
+    TUNE_ROW(TILE_RESOLVE, tune_tile_mode[3], within<-1, 7>, any_value, nullptr),
+    TUNE_ROW(SPATIAL_LDS, tune_spatial_lds, within<0, 160 * 1024>, any_value, nullptr),
+    TUNE_ROW(BVH_BUILDER, bvh_builder, within<0, 3>, within<3, 3>, nullptr), /* before rt_scene_set; [exp] 0 LBVH, 1 host SAH, 2 PLOC + host top */
+    TUNE_ROW(PT_WAVEFRONT, pt_wavefront, within<0, 2>, any_value, nullptr),
+    TUNE_ROW(BVH_BFS_RECORDS, bvh_bfs_records, within<0, INT_MAX>, any_value, nullptr), /* before rt_scene_set */
+    TUNE_ROW(SPATIAL_VARIANT, tune_spatial_variant, within<0, 4>, within<2, 2>, [](rt_ctx* c) { c->shaded_bits_stale = true; }), /* [exp] gather, LDS-staged bits, software-pipelined, one-wavefront workgroups */
+    TUNE_ROW(SPATIAL_WAVES, tune_spatial_waves, [](int v) { return v == 0 || v == -1 || (v >= 4 && v <= 6); },
+             [](int v) { return v == -1 || v == RT_SPATIAL_GATHER_AUTO_WAVES; }, nullptr), /* [exp] the other register budgets of the pass */
+    TUNE_ROW(PLOC_RADIUS, ploc_radius, within<1, 256>, no_value, nullptr), /* before rt_scene_set; [exp] builder 2 */
+    TUNE_ROW(DEFER_VIS, tune_defer_vis, within<0, 1>, within<0, 0>, nullptr), /* [exp] deferred visibility queue */
+    TUNE_ROW(RIS_PIPE, tune_ris_pipe, within<0, 1>, within<0, 0>, nullptr),   /* [exp] pipelined RIS loop form */
+    TUNE_ROW(WS, tune_ws, within<-1, 1>, any_value, nullptr),
+    TUNE_ROW(SPEC, tune_spec, within<-1, 2>, any_value,
+             [](rt_ctx* c) { if (!use_next_raycast(c, c->timing)) c->spec_valid = false; if (!use_next_generate(c, c->timing)) c->spec_gen_valid = false; }),
+    TUNE_ROW(STREAM, tune_stream, within<0, 1>, within<0, 0>, nullptr), /* [exp] resolve as a stream */
+    TUNE_ROW(WS_PRIMARY, tune_ws_primary, within<-1, 2>, [](int v) { return v != 2; }, nullptr), /* [exp] 2 = four lanes per primary ray */
+    TUNE_ROW(TAIL, tune_tail, within<-1, 1>, any_value, nullptr),
+    TUNE_ROW(MARK_QUICK, tune_mark_quick, within<0, 1>, any_value, nullptr),
+    TUNE_ROW(MARK_WINDOW, tune_mark_window, within<0, 1>, any_value, nullptr),
+    TUNE_ROW(FUSE_TONEMAP, tune_fuse_tonemap, within<0, 1>, any_value, nullptr),
+    TUNE_ROW(MARK_CACHE, tune_mark_cache, within<0, 1>, any_value, [](rt_ctx* c) { c->mark_bits_epoch = 0; }),
+    TUNE_ROW(SPEC_FREE, tune_spec_free, within<-1, 1>, any_value, [](rt_ctx* c) { c->spec_valid = false; c->spec_gen_valid = false; }),
+    TUNE_ROW(FUSE_FINAL, tune_fuse_final, within<-1, 2>, within<INT_MIN, 0>, nullptr), /* [exp] last pass + resolve in one kernel */
+    TUNE_ROW(HALF_RAYCAST, tune_half_raycast, within<0, 1>, within<0, 0>, nullptr), /* [exp] half-density raycast with helper lanes */
+    TUNE_ROW(FUSE_RAYCAST, tune_fuse_raycast, within<-1, 1>, any_value, nullptr),
+    TUNE_ROW(MARK_SPLIT, tune_mark_split, within<0, 1>, any_value, nullptr),
+    TUNE_ROW(AO_LAYOUT, tune_ao_layout, within<0, 1>, any_value, nullptr),
+    TUNE_ROW(DN_LAYOUT, tune_dn_layout, within<0, 1>, any_value, nullptr),
+};
+static_assert(rows_in_order(TUNING, RT_TUNE_COUNT, &TuneRow::key), "TUNING: one row per key, row i = key i");
+
 int rt_tuning(rt_ctx* c, int key, int value)
 {
     RT_CHECK_CTX(c);
-    if (experiment_only(key, value))
-        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_tuning %d = %d selects an A/B form that only librestir_rt_exp.so (built with -DRT_EXPERIMENTS) carries", key, value);
-    if (key >= 0 && key <= 3 && value >= -1 && value <= 7) c->tune_tile_mode[key] = value;
-    else if (key == 4 && value >= 0 && value <= 160 * 1024) c->tune_spatial_lds = value;
-    else if (key == 5 && value >= 0 && value <= 3) c->bvh_builder = value; /* before rt_scene_set */
-    else if (key == 6 && value >= 0 && value <= 2) c->pt_wavefront = value;
-    else if (key == 7 && value >= 0) c->bvh_bfs_records = value; /* before rt_scene_set */
-    else if (key == 8 && value >= 0 && value <= 4) { c->tune_spatial_variant = value; c->shaded_bits_stale = true; }
-    else if (key == 9 && (value == 0 || value == -1 || (value >= 4 && value <= 6))) c->tune_spatial_waves = value;
-    else if (key == 10 && value >= 1 && value <= 256) c->ploc_radius = value; /* before rt_scene_set */
-    else if (key == 11 && (value == 0 || value == 1)) c->tune_defer_vis = value;
-    else if (key == 12 && (value == 0 || value == 1)) c->tune_ris_pipe = value;
-    else if (key == 13 && value >= -1 && value <= 1) c->tune_ws = value;
-    else if (key == 15 && (value == 0 || value == 1)) c->tune_stream = value;
-    else if (key == 16 && value >= -1 && value <= 2) c->tune_ws_primary = value;
-    else if (key == 14 && value >= -1 && value <= 2) { c->tune_spec = value; if (!use_next_raycast(c, c->timing)) c->spec_valid = false; if (!use_next_generate(c, c->timing)) c->spec_gen_valid = false; }
-    else if (key == 17 && value >= -1 && value <= 1) c->tune_tail = value;
-    else if (key == 18 && (value == 0 || value == 1)) c->tune_mark_quick = value;
-    else if (key == 19 && (value == 0 || value == 1)) c->tune_mark_window = value;
-    else if (key == 20 && (value == 0 || value == 1)) c->tune_fuse_tonemap = value;
-    else if (key == 21 && (value == 0 || value == 1)) { c->tune_mark_cache = value; c->mark_bits_epoch = 0; }
-    else if (key == 23 && value >= -1 && value <= 2) c->tune_fuse_final = value;
-    else if (key == 24 && (value == 0 || value == 1)) c->tune_half_raycast = value;
-    else if (key == 25 && value >= -1 && value <= 1) c->tune_fuse_raycast = value;
-    else if (key == 26 && (value == 0 || value == 1)) c->tune_mark_split = value;
-    else if (key == 27 && (value == 0 || value == 1)) c->tune_ao_layout = value;
-    else if (key == 28 && (value == 0 || value == 1)) c->tune_dn_layout = value;
-    else if (key == 22 && value >= -1 && value <= 1) { c->tune_spec_free = value; c->spec_valid = false; c->spec_gen_valid = false; }
-    else RT_FAIL(c, RT_ERR_ARG, "bad tuning key/value %d/%d", key, value);
+    if (key < 0 || key >= RT_TUNE_COUNT) RT_FAIL(c, RT_ERR_ARG, "bad tuning key/value %d/%d", key, value);
+    const TuneRow& row = TUNING[key];
+#ifndef RT_EXPERIMENTS
+    if (!row.product(value))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_tuning %d (%s) = %d selects an A/B form that only librestir_rt_exp.so (built with -DRT_EXPERIMENTS) carries", key, row.name, value);
+#endif
+    if (!row.accepts(value)) RT_FAIL(c, RT_ERR_ARG, "bad tuning key/value %d (%s)/%d", key, row.name, value);
+    row.field(c) = value;
+    if (row.on_set) row.on_set(c);
     return RT_OK;
 }
 int rt_tuning_get(rt_ctx* c, int key, int* value)
 {
     RT_CHECK_CTX(c);
     if (!value) return RT_ERR_ARG;
-    switch (key)
-    {
-        case 0: case 1: case 2: case 3: *value = c->tune_tile_mode[key]; break;
-        case 4: *value = c->tune_spatial_lds; break;
-        case 5: *value = c->bvh_builder; break;
-        case 6: *value = c->pt_wavefront; break;
-        case 7: *value = c->bvh_bfs_records; break;
-        case 8: *value = c->tune_spatial_variant; break;
-        case 9: *value = c->tune_spatial_waves; break;
-        case 10: *value = c->ploc_radius; break;
-        case 11: *value = c->tune_defer_vis; break;
-        case 12: *value = c->tune_ris_pipe; break;
-        case 13: *value = c->tune_ws; break;
-        case 14: *value = c->tune_spec; break;
-        case 15: *value = c->tune_stream; break;
-        case 16: *value = c->tune_ws_primary; break;
-        case 17: *value = c->tune_tail; break;
-        case 18: *value = c->tune_mark_quick; break;
-        case 19: *value = c->tune_mark_window; break;
-        case 20: *value = c->tune_fuse_tonemap; break;
-        case 21: *value = c->tune_mark_cache; break;
-        case 22: *value = c->tune_spec_free; break;
-        case 23: *value = c->tune_fuse_final; break;
-        case 24: *value = c->tune_half_raycast; break;
-        case 25: *value = c->tune_fuse_raycast; break;
-        case 26: *value = c->tune_mark_split; break;
-        case 27: *value = c->tune_ao_layout; break;
-        case 28: *value = c->tune_dn_layout; break;
-        default: RT_FAIL(c, RT_ERR_ARG, "bad tuning key %d", key);
-    }
+    if (key < 0 || key >= RT_TUNE_COUNT) RT_FAIL(c, RT_ERR_ARG, "bad tuning key %d", key);
+    *value = TUNING[key].field(c);
     return RT_OK;
 }
 #ifndef RT_BUILD_ID
 #define RT_BUILD_ID "unknown"
 #endif
 const char* rt_build_id(void) { return RT_BUILD_ID; }
-/* which traversal rt_trace_closest / rt_trace_stats exercise: 0 = 4-wide quantised BVH with the
- * LDS stack (the one every frame kernel uses), 1 = binary LBVH with the stackless trail. */
+/* which traversal rt_trace_closest / rt_trace_stats exercise: a row of TRACE_MODES (enum rt_trace_mode_id) */
 int rt_trace_mode(rt_ctx* c, int mode)
 {
     RT_CHECK_CTX(c);
-    if (mode < 0 || mode > 7) RT_FAIL(c, RT_ERR_ARG, "mode must be 0..7");
-#ifndef RT_EXPERIMENTS
-    if ((mode >= 1 && mode <= 3) || mode == 7) RT_FAIL(c, RT_ERR_UNSUPPORTED, "trace mode %d (binary stackless walk / ray queue / four lanes per ray) is an A/B form of librestir_rt_exp.so", mode);
-#endif
+    if (mode < 0 || mode >= RT_TRACE_MODE_COUNT) RT_FAIL(c, RT_ERR_ARG, "mode must be 0..7");
+    if (!TRACE_MODES[mode].closest) RT_FAIL(c, RT_ERR_UNSUPPORTED, "trace mode %d (binary stackless walk / ray queue / four lanes per ray) is an A/B form of librestir_rt_exp.so", mode);
     c->trace_mode = mode;
     return RT_OK;
 }

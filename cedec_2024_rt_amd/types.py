@@ -5,6 +5,8 @@ Triangle common/core.hpp:38-43 (60 B), Visibility common/core.hpp:167-172 (16 B)
 Reservoir common/reservoir.hpp:5-38 (76 B), Options common/options.hpp:4-22 (48 B),
 RayGenerator common/camera.hpp:5-9 (36 B).
 """
+import enum
+
 import numpy as np
 
 TRIANGLE = np.dtype([("v", "<f4", (3, 3)), ("color", "<f4", 3), ("emissive", "<f4", 3)])
@@ -62,3 +64,49 @@ def bench_options(**kw):
     d = dict(use_temporal_resampling=1, use_spatial_resampling=1)
     d.update(kw)
     return default_options(**d)
+
+
+class Tune(enum.IntEnum):
+    """rt_tuning keys: enum rt_tuning_key of include/restir_rt_internal.h, which says what each one does. The numbers are
+    frozen (RT_TUNING, bench.py and every measurement log use them); tests/test_abi.py compares the two lists."""
+    TILE_RAYCAST = 0
+    TILE_GENERATE = 1
+    TILE_SPATIAL = 2
+    TILE_RESOLVE = 3
+    SPATIAL_LDS = 4
+    BVH_BUILDER = 5
+    PT_WAVEFRONT = 6
+    BVH_BFS_RECORDS = 7
+    SPATIAL_VARIANT = 8
+    SPATIAL_WAVES = 9
+    PLOC_RADIUS = 10
+    DEFER_VIS = 11
+    RIS_PIPE = 12
+    WS = 13
+    SPEC = 14
+    STREAM = 15
+    WS_PRIMARY = 16
+    TAIL = 17
+    MARK_QUICK = 18
+    MARK_WINDOW = 19
+    FUSE_TONEMAP = 20
+    MARK_CACHE = 21
+    SPEC_FREE = 22
+    FUSE_FINAL = 23
+    HALF_RAYCAST = 24
+    FUSE_RAYCAST = 25
+    MARK_SPLIT = 26
+    AO_LAYOUT = 27
+    DN_LAYOUT = 28
+
+
+class TraceMode(enum.IntEnum):
+    """rt_trace_mode modes: enum rt_trace_mode_id of include/restir_rt_internal.h"""
+    WIDE = 0
+    BINARY = 1
+    QUEUE_CLOSEST = 2
+    QUEUE_ANY = 3
+    WIDE_ANY = 4
+    OCCLUDED_WS = 5
+    OCCLUDED_LANE = 6
+    CLOSEST_QUAD = 7

@@ -247,96 +247,152 @@ int rt_bvh_config(rt_ctx* ctx, float split_factor);
 /* wide_height: levels of the 4-wide tree the kernels walk; a walk holds at most 3 stack entries per level */
 int rt_bvh_info(rt_ctx* ctx, uint32_t* n_references, uint32_t* n_wide_records, uint32_t* wide_height);
 int rt_build_ms(rt_ctx* ctx, float* ms); /* wall time of the last rt_scene_set (upload + tables + BVH build), synchronised */
-/* which traversal rt_trace_closest / rt_trace_stats exercise: 0 = 4-wide quantised BVH + LDS stack
- * (what every frame kernel uses, default), 1 = binary LBVH + stackless trail (A/B measurements),
- * 2/3 = persistent lane-refill queue (closest / any hit), 4 = mode 0 with any-hit (shadow-ray)
- * semantics: hits[i].index >= 0 iff occluded; 5 / 6 = shadow rays in one-wavefront workgroups as the frame kernels
- * walk them, with the work-sharing walk (5; rt_trace_stats then returns its pass / steal counters) or one lane per ray
- * (6); rays with tmax < 0 are lanes without a ray; [exp] 7 (r06) = closest hit with FOUR LANES PER RAY, 16 rays per wavefront
- * (closest_quad: what rt_tuning key 16 = 2 gives the primary rays). rt_trace_time: device ms of the last call's kernel. */
+/* which traversal rt_trace_closest / rt_trace_stats exercise. THE NUMBERS ARE FROZEN: tools, tests and every measurement log use
+ * them. [exp] modes are A/B forms of librestir_rt_exp.so: the product library answers RT_ERR_UNSUPPORTED for them. Modes 4 .. 6
+ * trace shadow rays (any hit): hits[i].index >= 0 iff occluded. rt_trace_stats answers RT_ERR_UNSUPPORTED in a mode for which
+ * the library at hand has no counting kernel (the product library: mode 6). */
+enum rt_trace_mode_id
+{
+    RT_TRACE_WIDE = 0,          /* 4-wide quantised BVH + LDS stack (what every frame kernel uses, default) */
+    RT_TRACE_BINARY = 1,        /* [exp] binary LBVH + stackless trail (A/B measurements) */
+    RT_TRACE_QUEUE_CLOSEST = 2, /* [exp] persistent lane-refill queue, closest hit */
+    RT_TRACE_QUEUE_ANY = 3,     /* [exp] persistent lane-refill queue, any hit */
+    RT_TRACE_WIDE_ANY = 4,      /* mode 0 with any-hit (shadow-ray) semantics */
+    RT_TRACE_OCCLUDED_WS = 5,   /* shadow rays in one-wavefront workgroups as the frame kernels walk them, with the work-sharing
+                                   walk (rt_trace_stats then returns its pass / steal counters); rays with tmax < 0 are lanes
+                                   without a ray */
+    RT_TRACE_OCCLUDED_LANE = 6, /* the same with one lane per ray */
+    RT_TRACE_CLOSEST_QUAD = 7,  /* [exp] (r06) closest hit with FOUR LANES PER RAY, 16 rays per wavefront (closest_quad: what
+                                   RT_TUNE_WS_PRIMARY = 2 gives the primary rays) */
+    RT_TRACE_MODE_COUNT
+};
 int rt_trace_mode(rt_ctx* ctx, int mode);
-int rt_trace_time(rt_ctx* ctx, float* ms);
+int rt_trace_time(rt_ctx* ctx, float* ms); /* device ms of the last rt_trace_closest call's kernel */
 /* Performance knobs; RESULTS NEVER DEPEND ON THEM (every key / value is tested bit for bit against the default). rt_tuning_get
  * returns the value a key holds, -1 meaning "auto" where a key has one. Keys marked [exp] select A/B forms that were measured and
  * left off: they are compiled only into librestir_rt_exp.so (csrc/Makefile, -DRT_EXPERIMENTS); the product library answers
  * RT_ERR_UNSUPPORTED for them. History and numbers of every key: docs/MEASUREMENT_LOG_*.md.
- *
- * Launch geometry
- *  0..3  workgroup -> tile order of raycast (and rt_path_trace) / generate_candidate / spatial_resampling / resolve. Workgroup b runs
- *        on XCD b % 8. 0, 1: XCD k takes ONE band of tile rows, row by row / column by column (r01-r04). r05, the XCDs
- *        interleaved: 2, 3 = XCD k takes tile rows k, k + 8, ... (row by row / column by column), 4 = tile b (row-major) on XCD
- *        b % 8, 5 = the same in stripes 32 tiles wide, 6, 7 = row-major runs of 4 / 16 tiles per XCD. -1 auto (default for all
- *        four): tracing kernels 2 on whole frames, 4 on strips (a band costs what its part of the scene costs: raycast -14 %,
- *        generate_candidate -9 %, resolve -12 %, an 8-rank 4K strip -7 %); the spatial pass 1 on whole frames and strips of
- *        400 rows or more (its +-87-px neighbour window must stay in one XCD's L2), 4 on shorter strips, 7 with the shadowed
- *        target function (4.67 -> 3.83 ms per frame). profiles/r05_tile_interleave_ab.txt.
- *  4     extra LDS bytes per unshadowed spatial workgroup (round 1's occupancy throttle; default 0).
- *  9     register budget of the unshadowed spatial pass in wavefronts per SIMD: -1 auto = 6 (default). [exp] 4, 5, 0 (= unbounded, 7).
- *  13    shadow rays of generate_candidate / resolve through the work-sharing any-hit walk: 1 always (default), 0 never, -1 only
- *        for launches of about one generation of wavefronts.
- *  16    primary rays through the work-sharing closest-hit walk: -1 auto = launches of about one generation of wavefronts, i.e.
- *        strips (default), 0 never, 1 always (a whole frame's coherent 8 x 8 tiles gain nothing: 0.311 -> 0.318 ms); [exp] 2 (r06) =
- *        four lanes per primary ray (k_raycast_quad: 16 rays per wavefront, each lane one child box of the 4-wide record, four
- *        times the wavefronts: 78 -> 95 us for 135 rows, 228 -> 474 us for a whole frame; profiles/r06_quad_walk_ab.txt).
- *  24    [exp] (r05) raycast at half density: a wavefront carries 32 primary rays and 32 rayless lanes that only take work from
- *        the others' stacks, twice the wavefronts (would a strip's one-generation launch finish sooner with two lanes per ray?
- *        No: 80 -> 94 us for 135 rows, 269 -> 449 us for a whole frame; profiles/r05_half_raycast_ab.txt). Default 0.
- * Scene (before rt_scene_set)
- *  5     BVH builder: 3 = on the device: pre-split, top-down binned SAH, 4-wide collapse; the host reads counters (default;
- *        11 ms for 212 k triangles). [exp] 0 = device LBVH + host collapse (r01), 1 = host binned SAH (the tree builder 3
- *        reproduces; 230 ms), 2 = device PLOC + host SAH over the top 8 192 clusters. All feed the same walk.
- *  7     wide-BVH records emitted breadth-first before the collapse goes depth-first (default 2048; no measurable effect).
- *  10    [exp] PLOC search radius of builder 2 (default 16).
- * Frame structure
- *  6     rt_path_trace: 0 one launch per frame (the reference's shape), 1 one launch per bounce over the compacted list of live
- *        paths, 2 auto (default: per bounce for 09_ris).
- *  14    the NEXT frame's stage 0 on a stream of its own beside this frame's passes, exchanges and resolve: 0 never, 1 its
- *        primary rays (second / third G-buffer set), 2 its generate_candidate + temporal_resampling too (the reference saves the
- *        history before the passes, 10_restir_di.cpp:314-321), -1 auto = 2 (default; level 1 while rt_timing is enabled on a
- *        whole-frame context). The next frame takes the results if frame number, camera, scene, options (rt_state_epoch) and
- *        reservoir buffers are unchanged, and runs its own stage 0 otherwise. rt_sync waits for that stream too.
- *  17    resolve + tone_mapping of a staged frame on a "tail" stream of their own: -1 auto = 1 on (default), 0 off. Off while
- *        rt_timing is enabled.
- *  25    (r05) stage 0 of the staged frame as ONE launch: the candidates' kernel traces the primary ray of its pixel first
- *        (raycast needs nothing else, generate_candidate nothing but it; as two launches the second waits for the first one's
- *        ramp-down): -1 auto = whole-frame contexts (default), 0 two launches, 1 also on strips. Applies to the product's fused
- *        candidate kernel (temporal merge on, unshadowed target), also while rt_timing brackets the kernels (r06:
- *        rt_stage0_one_launch); rt_raycast / rt_generate_candidate are always the two kernels.
- *  20    the staged frame's resolve kernel tone-maps the pixel it has just accumulated (common/kernels/common.cu:30-74 reads
- *        nothing else): 1 (default), 0 = two launches as the reference. rt_resolve / rt_tone_mapping are always the two kernels.
- *  22    (r05) the look-ahead stage 0 (key 14) of frame f+1 waits neither for the main stream (frame f took its own stage 0 from
- *        the look-ahead stream) nor for resolve(f-1): with three G-buffer sets and five reservoir buffers resolve(f-2) is the
- *        last reader of what it overwrites. -1 auto = strips (default: rank 4 of 8 at 1080p 0.306 -> 0.287 ms), 0 never (r04's
- *        dependencies), 1 always (a whole 1080p frame: 1.277 -> 1.296 ms).
- * Spatial pass
- *  8     2 = the wavefront fetches the 64 records of a round together, four lanes per 64-B record, as LDS-DMA loads that land
- *        transposed in LDS, and writes its 64 records the same way (default, the only product form). [exp] 0 = one per-lane
- *        gather per neighbour (r01), 1 = the tile's +-87-px window of shaded bits staged in LDS (r02), 3 = form 2 software-
- *        pipelined over that window (r04: 0.152 against 0.1435 ms), 4 = form 2 as one-wavefront workgroups on 8 x 8 tiles (r05:
- *        more wavefronts in flight, each slower: +1.3 %).
- *  23    [exp] (r05) the LAST spatial pass + resolve in one kernel (k_spatial_resolve): 1 = with the pass's own stores, 2 = records
- *        kept in registers (the pass's output buffer is NOT written), 0 / -1 = two kernels (default). Measured slower:
- *        profiles/r05_fused_tail_ab.txt.
- * Candidates / resolve A/B forms
- *  11    [exp] visibility-reuse rays of the fused candidate kernel only for candidates that survive the temporal merge, through a
- *        compacted queue (75 % survive in the bench scene: no gain). Default 0.
- *  12    [exp] software-pipelined RIS loop form. Default 0.
- *  15    [exp] resolve as a stream of persistent wavefronts (0.48 against 0.36 ms, r02). Default 0.
- * Strips (multi-GPU)
- *  18    rt_halo_mark: rows more than 40 rows from a neighbour's region test the pass's first draws against a bound on the
- *        neighbour distance before replaying log / sqrt / sincos: 1 (default), 0 = full replay.
- *  19    rt_halo_mark collects a workgroup's marks in an LDS bitmap of its +-87-pixel window, one global atomic per non-zero
- *        word: 1 (default; widths that are multiples of 32, reach <= 87 px, <= 3 passes per call), 0 = one atomic per mark.
- *  21    (r05) the shaded-bit rows key 19 reads are built once per camera / scene / option epoch: 1 (default), 0 = in front of
- *        every mark (r04).
- *  26    (r06) rt_halo_mark as one workgroup per (tile, pass) instead of one per tile that replays the passes in series: 0
- *        (default = r02-r05), 1. A strip's mark launch is half a generation of wavefronts and lasts as long as one thread's
- *        chain of 3 x 5 neighbour replays - but it is not on the frame's critical chain and its total work stays the same:
- *        measured +-1 % (profiles/r06_mark_split_ab.txt).
- * Ambient occlusion (rt_path_trace example 4 / 6)
- *  27    (r07) layout of the 64 occlusion rays per pixel: 0 (default) pixel-major, a lane walks its own pixel's rays back to back
- *        and draws each when it starts it; 1 ray-major, the wavefront walks one pixel's 64 rays at a time (lane i from draw 3i
- *        through the PCG jump-ahead). Same image either way (ambient occlusion). */
+ * THE NUMBERS ARE FROZEN: bench.py, RT_TUNING=14=0,17=0, tools/profile_round.sh and every measurement log use them. A new key
+ * takes the next number; a retired one keeps its number. */
+enum rt_tuning_key
+{
+    /* ---- Launch geometry ---- */
+    /* workgroup -> tile order of raycast (and rt_path_trace) / generate_candidate / spatial_resampling / resolve. Workgroup b runs
+     * on XCD b % 8. 0, 1: XCD k takes ONE band of tile rows, row by row / column by column (r01-r04). r05, the XCDs
+     * interleaved: 2, 3 = XCD k takes tile rows k, k + 8, ... (row by row / column by column), 4 = tile b (row-major) on XCD
+     * b % 8, 5 = the same in stripes 32 tiles wide, 6, 7 = row-major runs of 4 / 16 tiles per XCD. -1 auto (default for all
+     * four): tracing kernels 2 on whole frames, 4 on strips (a band costs what its part of the scene costs: raycast -14 %,
+     * generate_candidate -9 %, resolve -12 %, an 8-rank 4K strip -7 %); the spatial pass 1 on whole frames and strips of
+     * 400 rows or more (its +-87-px neighbour window must stay in one XCD's L2), 4 on shorter strips, 7 with the shadowed
+     * target function (4.67 -> 3.83 ms per frame). profiles/r05_tile_interleave_ab.txt. */
+    RT_TUNE_TILE_RAYCAST = 0,
+    RT_TUNE_TILE_GENERATE = 1,
+    RT_TUNE_TILE_SPATIAL = 2,
+    RT_TUNE_TILE_RESOLVE = 3,
+    /* extra LDS bytes per unshadowed spatial workgroup (round 1's occupancy throttle; default 0). */
+    RT_TUNE_SPATIAL_LDS = 4,
+    /* register budget of the unshadowed spatial pass in wavefronts per SIMD: -1 auto = 6 (default). [exp] 4, 5, 0 (= unbounded, 7). */
+    RT_TUNE_SPATIAL_WAVES = 9,
+    /* shadow rays of generate_candidate / resolve through the work-sharing any-hit walk: 1 always (default), 0 never, -1 only
+     * for launches of about one generation of wavefronts. */
+    RT_TUNE_WS = 13,
+    /* primary rays through the work-sharing closest-hit walk: -1 auto = launches of about one generation of wavefronts, i.e.
+     * strips (default), 0 never, 1 always (a whole frame's coherent 8 x 8 tiles gain nothing: 0.311 -> 0.318 ms); [exp] 2 (r06) =
+     * four lanes per primary ray (k_raycast_quad: 16 rays per wavefront, each lane one child box of the 4-wide record, four
+     * times the wavefronts: 78 -> 95 us for 135 rows, 228 -> 474 us for a whole frame; profiles/r06_quad_walk_ab.txt). */
+    RT_TUNE_WS_PRIMARY = 16,
+    /* [exp] (r05) raycast at half density: a wavefront carries 32 primary rays and 32 rayless lanes that only take work from
+     * the others' stacks, twice the wavefronts (would a strip's one-generation launch finish sooner with two lanes per ray?
+     * No: 80 -> 94 us for 135 rows, 269 -> 449 us for a whole frame; profiles/r05_half_raycast_ab.txt). Default 0. */
+    RT_TUNE_HALF_RAYCAST = 24,
+
+    /* ---- Scene (before rt_scene_set) ---- */
+    /* BVH builder: 3 = on the device: pre-split, top-down binned SAH, 4-wide collapse; the host reads counters (default;
+     * 11 ms for 212 k triangles). [exp] 0 = device LBVH + host collapse (r01), 1 = host binned SAH (the tree builder 3
+     * reproduces; 230 ms), 2 = device PLOC + host SAH over the top 8 192 clusters. All feed the same walk. */
+    RT_TUNE_BVH_BUILDER = 5,
+    /* wide-BVH records emitted breadth-first before the collapse goes depth-first (default 2048; no measurable effect). */
+    RT_TUNE_BVH_BFS_RECORDS = 7,
+    /* [exp] PLOC search radius of builder 2 (default 16). */
+    RT_TUNE_PLOC_RADIUS = 10,
+
+    /* ---- Frame structure ---- */
+    /* rt_path_trace: 0 one launch per frame (the reference's shape), 1 one launch per bounce over the compacted list of live
+     * paths, 2 auto (default: per bounce for 09_ris). */
+    RT_TUNE_PT_WAVEFRONT = 6,
+    /* the NEXT frame's stage 0 on a stream of its own beside this frame's passes, exchanges and resolve: 0 never, 1 its
+     * primary rays (second / third G-buffer set), 2 its generate_candidate + temporal_resampling too (the reference saves the
+     * history before the passes, 10_restir_di.cpp:314-321), -1 auto = 2 (default; level 1 while rt_timing is enabled on a
+     * whole-frame context). The next frame takes the results if frame number, camera, scene, options (rt_state_epoch) and
+     * reservoir buffers are unchanged, and runs its own stage 0 otherwise. rt_sync waits for that stream too. */
+    RT_TUNE_SPEC = 14,
+    /* resolve + tone_mapping of a staged frame on a "tail" stream of their own: -1 auto = 1 on (default), 0 off. Off while
+     * rt_timing is enabled. */
+    RT_TUNE_TAIL = 17,
+    /* (r05) stage 0 of the staged frame as ONE launch: the candidates' kernel traces the primary ray of its pixel first
+     * (raycast needs nothing else, generate_candidate nothing but it; as two launches the second waits for the first one's
+     * ramp-down): -1 auto = whole-frame contexts (default), 0 two launches, 1 also on strips. Applies to the product's fused
+     * candidate kernel (temporal merge on, unshadowed target), also while rt_timing brackets the kernels (r06:
+     * rt_stage0_one_launch); rt_raycast / rt_generate_candidate are always the two kernels. */
+    RT_TUNE_FUSE_RAYCAST = 25,
+    /* the staged frame's resolve kernel tone-maps the pixel it has just accumulated (common/kernels/common.cu:30-74 reads
+     * nothing else): 1 (default), 0 = two launches as the reference. rt_resolve / rt_tone_mapping are always the two kernels. */
+    RT_TUNE_FUSE_TONEMAP = 20,
+    /* (r05) the look-ahead stage 0 (RT_TUNE_SPEC) of frame f+1 waits neither for the main stream (frame f took its own stage 0
+     * from the look-ahead stream) nor for resolve(f-1): with three G-buffer sets and five reservoir buffers resolve(f-2) is the
+     * last reader of what it overwrites. -1 auto = strips (default: rank 4 of 8 at 1080p 0.306 -> 0.287 ms), 0 never (r04's
+     * dependencies), 1 always (a whole 1080p frame: 1.277 -> 1.296 ms). */
+    RT_TUNE_SPEC_FREE = 22,
+
+    /* ---- Spatial pass ---- */
+    /* 2 = the wavefront fetches the 64 records of a round together, four lanes per 64-B record, as LDS-DMA loads that land
+     * transposed in LDS, and writes its 64 records the same way (default, the only product form). [exp] 0 = one per-lane
+     * gather per neighbour (r01), 1 = the tile's +-87-px window of shaded bits staged in LDS (r02), 3 = form 2 software-
+     * pipelined over that window (r04: 0.152 against 0.1435 ms), 4 = form 2 as one-wavefront workgroups on 8 x 8 tiles (r05:
+     * more wavefronts in flight, each slower: +1.3 %). */
+    RT_TUNE_SPATIAL_VARIANT = 8,
+    /* [exp] (r05) the LAST spatial pass + resolve in one kernel (k_spatial_resolve): 1 = with the pass's own stores, 2 = records
+     * kept in registers (the pass's output buffer is NOT written), 0 / -1 = two kernels (default). Measured slower:
+     * profiles/r05_fused_tail_ab.txt. */
+    RT_TUNE_FUSE_FINAL = 23,
+
+    /* ---- Candidates / resolve A/B forms ---- */
+    /* [exp] visibility-reuse rays of the fused candidate kernel only for candidates that survive the temporal merge, through a
+     * compacted queue (75 % survive in the bench scene: no gain). Default 0. */
+    RT_TUNE_DEFER_VIS = 11,
+    /* [exp] software-pipelined RIS loop form. Default 0. */
+    RT_TUNE_RIS_PIPE = 12,
+    /* [exp] resolve as a stream of persistent wavefronts (0.48 against 0.36 ms, r02). Default 0. */
+    RT_TUNE_STREAM = 15,
+
+    /* ---- Strips (multi-GPU) ---- */
+    /* rt_halo_mark: rows more than 40 rows from a neighbour's region test the pass's first draws against a bound on the
+     * neighbour distance before replaying log / sqrt / sincos: 1 (default), 0 = full replay. */
+    RT_TUNE_MARK_QUICK = 18,
+    /* rt_halo_mark collects a workgroup's marks in an LDS bitmap of its +-87-pixel window, one global atomic per non-zero
+     * word: 1 (default; widths that are multiples of 32, reach <= 87 px, <= 3 passes per call), 0 = one atomic per mark. */
+    RT_TUNE_MARK_WINDOW = 19,
+    /* (r05) the shaded-bit rows RT_TUNE_MARK_WINDOW reads are built once per camera / scene / option epoch: 1 (default), 0 = in
+     * front of every mark (r04). */
+    RT_TUNE_MARK_CACHE = 21,
+    /* (r06) rt_halo_mark as one workgroup per (tile, pass) instead of one per tile that replays the passes in series: 0
+     * (default = r02-r05), 1. A strip's mark launch is half a generation of wavefronts and lasts as long as one thread's
+     * chain of 3 x 5 neighbour replays - but it is not on the frame's critical chain and its total work stays the same:
+     * measured +-1 % (profiles/r06_mark_split_ab.txt). */
+    RT_TUNE_MARK_SPLIT = 26,
+
+    /* ---- Ambient occlusion (rt_path_trace example 4 / 6) ---- */
+    /* (r07) layout of the 64 occlusion rays per pixel: 0 (default) pixel-major, a lane walks its own pixel's rays back to back
+     * and draws each when it starts it; 1 ray-major, the wavefront walks one pixel's 64 rays at a time (lane i from draw 3i
+     * through the PCG jump-ahead). Same image either way (ambient occlusion). */
+    RT_TUNE_AO_LAYOUT = 27,
+
+    /* ---- Denoiser (rt_denoise, rt_denoise_temporal) ---- */
+    /* layout of the a-trous levels: 0 per-lane gathers, 1 residue lattice in LDS. The same results. */
+    RT_TUNE_DN_LAYOUT = 28,
+
+    RT_TUNE_COUNT
+};
 int rt_tuning(rt_ctx* ctx, int key, int value);
 /* the value a key holds now (measurement records name the builder / variants that were really used) */
 int rt_tuning_get(rt_ctx* ctx, int key, int* value);

@@ -48,6 +48,28 @@ def test_public_header_stands_alone_and_the_host_app_needs_no_more_for_a_frame()
             subprocess.run([cc, "-fsyntax-only", "-Wall", "-Werror", "-x", lang, os.path.join(inc, h)], check=True)
 
 
+def test_tuning_keys_and_trace_modes_have_the_same_names_in_c_and_python():
+    """enum rt_tuning_key / rt_trace_mode_id of the internal header == types.Tune / types.TraceMode, name for name and value for
+    value; the keys are 0 .. 28 without a gap (the numbers are frozen: RT_TUNING, bench.py and the measurement logs use them)."""
+    from cedec_2024_rt_amd import api, types
+
+    src = open(os.path.join(ROOT, "include", "restir_rt_internal.h")).read()
+
+    def enumerators(enum, prefix, count):
+        body = re.search(r"enum %s\s*\{(.*?)\n\};" % enum, src, re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        names = [e.strip() for e in body.split(",") if e.strip()]
+        assert names[-1] == count and all(re.fullmatch(prefix + r"[A-Z0-9_]+ = \d+", e) for e in names[:-1]), names
+        return {e.split(" = ")[0][len(prefix):]: int(e.split(" = ")[1]) for e in names[:-1]}
+
+    tune, trace = enumerators("rt_tuning_key", "RT_TUNE_", "RT_TUNE_COUNT"), enumerators("rt_trace_mode_id", "RT_TRACE_", "RT_TRACE_MODE_COUNT")
+    assert sorted(tune.values()) == list(range(29)) and sorted(trace.values()) == list(range(8))
+    assert tune == {m.name: m.value for m in types.Tune} and len(types.Tune.__members__) == len(tune)  # __members__ counts aliases too
+    assert trace == {m.name: m.value for m in types.TraceMode} and len(types.TraceMode.__members__) == len(trace)
+    assert api.Tune is types.Tune and api.TraceMode is types.TraceMode
+    assert (tune["TILE_RAYCAST"], tune["BVH_BUILDER"], tune["SPEC"], tune["TAIL"], tune["DN_LAYOUT"]) == (0, 5, 14, 17, 28)
+
+
 def test_product_library_carries_no_experiment_kernels():
     """the A/B forms (per-lane gather / LDS-staged / software-pipelined spatial pass, fused last pass + resolve,
     resolve as a stream, ray queue, PLOC builder ...) are code objects of librestir_rt_exp.so only; both libraries export the

@@ -21,7 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 APP = os.path.join(ROOT, "app", "restir_app")
 FOVY = np.float32(np.pi) / np.float32(4)
 RT_ERR_ARG, RT_ERR_STATE = 1, 3
-AO_KEY = 27
 BLOCKS_AO_RAYS_1080P = 99_726_016  # 2 073 600 primary rays + 64 x 1 525 819 hit pixels
 
 
@@ -48,7 +47,7 @@ def _renderer(api, tris, W, H, eye, at, rows=None, layout=None):
     r.set_scene(tris)
     r.lookat(eye, at)
     if layout is not None:
-        r.tuning(AO_KEY, layout)
+        r.tuning(api.Tune.AO_LAYOUT, layout)
     return r
 
 
@@ -106,7 +105,7 @@ def test_both_layouts_give_the_same_image(api, oracle, scenes, golden_dir, block
     tris, W, H, ref = blocks_ao
     for layout in (0, 1):
         r = _renderer(api, tris, W, H, scenes.DEFAULT_EYE, scenes.DEFAULT_LOOKAT, layout=layout)
-        assert r.tuning_get(AO_KEY) == layout
+        assert r.tuning_get(api.Tune.AO_LAYOUT) == layout
         px = r.ambient_occlusion()
         assert np.array_equal(px, ref), f"layout {layout}: {_diff(px, ref)} pixels differ"
         assert r.path_trace_rays() == BLOCKS_AO_RAYS_1080P
@@ -123,7 +122,7 @@ def test_both_layouts_give_the_same_image(api, oracle, scenes, golden_dir, block
     r = api.Renderer(64, 48)
     for bad in (-1, 2):
         with pytest.raises(api.RtError):
-            r.tuning(AO_KEY, bad)
+            r.tuning(api.Tune.AO_LAYOUT, bad)
     r.close()
 
 

@@ -73,7 +73,7 @@ def _check(api, r, scene, params, layouts=(0, 1)):
     rg_up = r.raygen()["up"][0]
     ref = None
     for lay in layouts:
-        r.tuning(28, lay)
+        r.tuning(api.Tune.DN_LAYOUT, lay)
         hdr = r.denoise(hdr=True, **params).reshape(-1, 4)
         if ref is None:
             ref = denoise_ref.denoise(r.W, r.H, tris, r.download(api.RT_BUF_DENOISE_GUIDE), eye, rg_up, acc, **params)
@@ -216,7 +216,7 @@ def test_error_codes(api, blocks, room):
     assert r.L.rt_download(r.h, api.RT_BUF_DENOISED, buf.ctypes.data, buf.nbytes) == RT_OK
     assert r.L.rt_download(r.h, api.RT_BUF_DENOISED, buf.ctypes.data, buf.nbytes - 16) == RT_ERR_ARG
     assert r.L.rt_upload(r.h, api.RT_BUF_DENOISED, buf.ctypes.data, buf.nbytes) == RT_ERR_ARG  # download only
-    assert r.L.rt_tuning(r.h, 28, 2) == RT_ERR_ARG
+    assert r.L.rt_tuning(r.h, api.Tune.DN_LAYOUT, 2) == RT_ERR_ARG
     r.close()
     s = api.Renderer(W, H, rows=(0, H // 2), halo=8)
     s.set_scene(room[0])

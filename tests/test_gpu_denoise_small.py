@@ -52,7 +52,7 @@ def _renderer(api, tris, W, H, layout=None):
     r.lookat(cs.EYE, cs.AT)
     r.set_options(bench_options())
     if layout is not None:
-        r.tuning(28, layout)
+        r.tuning(api.Tune.DN_LAYOUT, layout)
     return r
 
 
@@ -67,7 +67,7 @@ def test_small_images_equal_restatement_and_reference(api, tris, W, H):
         ref = None
         for lay in (0, 1):
             name = f"{W} x {H}, layout {lay}, {params}"
-            r.tuning(28, lay)
+            r.tuning(api.Tune.DN_LAYOUT, lay)
             hdr = r.denoise(hdr=True, **params).reshape(-1, 4)
             px = r.download(api.RT_BUF_PIXELS)
             if case is None:

@@ -60,7 +60,7 @@ def _renderer(api, scene, W, H, layout=None, **opt):
     r.lookat(eye, at)
     r.set_options(bench_options(**opt))
     if layout is not None:
-        r.tuning(28, layout)
+        r.tuning(api.Tune.DN_LAYOUT, layout)
     return r
 
 

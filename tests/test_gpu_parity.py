@@ -133,20 +133,21 @@ def test_lbvh_equals_brute_force(api, oracle, scenes, golden_scenes):
         ref = sc.trace_closest(rays, force_brute=True)
         for builder in (0, 1, 2, 3):  # 0: device LBVH (Morton + Karras), 1: host binned SAH, 2: device PLOC, 3: device binned SAH
             r = api.Renderer(8, 8, exp=True)  # builders 0-2 and walk modes 1-3: librestir_rt_exp.so
-            r.tuning(5, builder)
+            r.tuning(api.Tune.BVH_BUILDER, builder)
             r.set_scene(tris)
-            # 0: 4-wide quantised BVH + LDS stack (production), 1: binary tree + stackless trail,
-            # 2: persistent ray queue with lane refill (closest hit), 7 (r06): four lanes per ray, one child box each (closest_quad)
-            for mode in (0, 1, 2, 7):
+            M = api.TraceMode
+            # the 4-wide quantised BVH + LDS stack (production), the binary tree + stackless trail, the persistent ray queue with
+            # lane refill (closest hit), (r06) four lanes per ray, one child box each (closest_quad)
+            for mode in (M.WIDE, M.BINARY, M.QUEUE_CLOSEST, M.CLOSEST_QUAD):
                 r.trace_mode(mode)
                 dev = r.trace_closest(rays)
                 assert _eq_bits(dev, ref), f"{name} builder {builder} mode {mode}: {(dev.view(np.uint32) != ref.view(np.uint32)).any(axis=1).sum()} rays differ"
-            # shadow-ray semantics (3: persistent queue, 4: the frame kernels' any-hit walk): occluded <=> a closest hit exists
-            for mode in (3, 4):
+            # shadow-ray semantics (the persistent queue, the frame kernels' any-hit walk): occluded <=> a closest hit exists
+            for mode in (M.QUEUE_ANY, M.WIDE_ANY):
                 r.trace_mode(mode)
                 occ = r.trace_closest(rays)[:, 3].view(np.int32) >= 0
                 assert (occ == (ref[:, 3].view(np.int32) >= 0)).all(), f"{name} builder {builder} any-hit mode {mode}"
-            # 5: the work-sharing any-hit walk (idle lanes take over half of a busy lane's stack), also with a third
+            # OCCLUDED_WS: the work-sharing any-hit walk (idle lanes take over half of a busy lane's stack), also with a third
             # of the lanes holding no ray at all (tmax < 0: they only help)
             occ, passes, steals = r.trace_occluded_ws(rays)
             assert (occ == (ref[:, 3].view(np.int32) >= 0)).all(), f"{name} builder {builder} work-sharing walk"
@@ -190,14 +191,15 @@ def test_deep_traversal_stack_spills_past_lds(api, oracle):
     assert (ref[:, 3].view(np.int32) >= 0).mean() > 0.5
     for builder in (0, 1, 2, 3):
         r = api.Renderer(8, 8, exp=True)  # builders 0-2 and walk modes 1-3: librestir_rt_exp.so
-        r.tuning(5, builder)
+        r.tuning(api.Tune.BVH_BUILDER, builder)
         r.set_scene(tris)
         assert 3 * (r.bvh_info()["wide_height"] - 1) >= 24 + 6, r.bvh_info()
-        for mode in (0, 2, 7):  # 7: closest_quad keeps its whole (inner-records-only) stack in LDS
+        M = api.TraceMode
+        for mode in (M.WIDE, M.QUEUE_CLOSEST, M.CLOSEST_QUAD):  # closest_quad keeps its whole (inner-records-only) stack in LDS
             r.trace_mode(mode)
             dev = r.trace_closest(rays)
             assert _eq_bits(dev, ref), f"builder {builder} mode {mode}"
-        for mode in (3, 4):
+        for mode in (M.QUEUE_ANY, M.WIDE_ANY):
             r.trace_mode(mode)
             occ = r.trace_closest(rays)[:, 3].view(np.int32) >= 0
             assert (occ == (ref[:, 3].view(np.int32) >= 0)).all(), f"builder {builder} any-hit mode {mode}"
@@ -216,19 +218,19 @@ def test_lbvh_blocks_scene_vs_oracle_bvh(api, oracle, scenes):
     ref = sc.trace_closest(rays)
     for builder in (0, 1, 2, 3):
         r = api.Renderer(8, 8, exp=True)  # builders 0-2 and walk modes 1-3: librestir_rt_exp.so
-        r.tuning(5, builder)
+        r.tuning(api.Tune.BVH_BUILDER, builder)
         r.set_scene(tris)
         info = r.scene_info()
         print(f"builder {builder}: rt_scene_set {r.build_ms():.1f} ms, {r.bvh_info()}, binary height {info['bvh_height']}")
         assert info["triangles"] == len(tris) and info["lights"] == len(scenes.light_indices(tris))
-        for mode in (0, 1, 2, 7):
+        for mode in (api.TraceMode.WIDE, api.TraceMode.BINARY, api.TraceMode.QUEUE_CLOSEST, api.TraceMode.CLOSEST_QUAD):
             r.trace_mode(mode)
             dev = r.trace_closest(rays)
             assert _eq_bits(dev, ref), f"builder {builder} mode {mode}: {(dev.view(np.uint32) != ref.view(np.uint32)).any(axis=1).sum()} rays differ"
         occ, passes, steals = r.trace_occluded_ws(rays)
         assert (occ == (ref[:, 3].view(np.int32) >= 0)).all(), f"builder {builder} work-sharing walk"
         assert steals.sum() > 1000, steals.sum()
-        r.trace_mode(0)
+        r.trace_mode(api.TraceMode.WIDE)
         # a 2000-ray subset against true brute force
         sub = rays[:2000]
         assert _eq_bits(r.trace_closest(sub), sc.trace_closest(sub, force_brute=True))
@@ -578,7 +580,7 @@ def test_path_tracers_07_and_09(api, oracle, scenes, golden_scenes, example, sce
     r.clear()
     for frame in range(1, frames + 1):
         cnt = oracle.new_counters()
-        r.tuning(6, frame % 2)  # alternate: one launch per frame / wavefront (one launch per bounce, compaction)
+        r.tuning(api.Tune.PT_WAVEFRONT, frame % 2)  # alternate: one launch per frame / wavefront (one launch per bounce, compaction)
         r.path_trace(example, frame)
         sc.path_trace(example, W, H, frame, rg, opt, acc, cnt=cnt)
         got = r.download(api.RT_BUF_ACCUMULATION)
@@ -696,6 +698,53 @@ def test_edge_cases_and_error_codes(api, oracle, scenes):
     r4.close()
 
 
+def test_tuning_matrix(api):
+    """rt_tuning, rt_tuning_get and rt_trace_mode answer every key / value / mode as they did while rt_tuning was a 29-arm chain
+    beside a switch: tests/golden/tuning_matrix.json holds the answers of that commit's code, product and experiments build
+    (docs/MEASUREMENT_LOG_r12.md section 2; the format of tools/record_tuning_matrix.py: return codes, read-back values and defaults
+    for keys -1 .. 30 and 99), replayed entry for entry on the libraries of this tree. No kernel is launched."""
+    import json
+    import sys
+
+    if os.environ.get("RT_TUNING") or os.environ.get("RT_LIB_PATH") or os.environ.get("RT_EXPERIMENTS"):
+        pytest.skip("the matrix holds the answers of the two libraries of the tree with no key set")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import record_tuning_matrix as rec
+
+    with open(os.path.join(ROOT, "tests", "golden", "tuning_matrix.json")) as f:
+        gold = json.load(f)
+    assert (gold["keys"], gold["values"], gold["modes"]) == (rec.KEYS, rec.VALUES, rec.MODES)
+    for name, path in (("product", api.LIB_PATH), ("experiments", api.EXP_LIB_PATH)):
+        got, want = rec.measure(path), gold[name]
+        for ki, key in enumerate(rec.KEYS):
+            assert got["defaults"][ki] == want["defaults"][ki], f"{name}: default of key {key} {{rc, value}}"
+            for vi, value in enumerate(rec.VALUES):
+                assert got["tuning"][ki][vi] == want["tuning"][ki][vi], f"{name}: key {key} = {value} {{rc set, rc get, value}}"
+        assert got["trace_mode"] == want["trace_mode"], f"{name}: rt_trace_mode over {rec.MODES}"
+
+
+def test_trace_stats_needs_a_counting_kernel(api, scenes):
+    """rt_trace_stats in a trace mode for which the library has no counting kernel refuses (the product library in
+    api.TraceMode.OCCLUDED_LANE: it used to launch nothing and copy uninitialised device memory back with RT_OK); the work-sharing
+    mode beside it still returns its counters."""
+    if os.environ.get("RT_LIB_PATH") or os.environ.get("RT_EXPERIMENTS"):
+        pytest.skip("about the product library")
+    r = api.Renderer(8, 8)
+    tris = scenes.make_quad_room()
+    r.set_scene(tris)
+    v = tris["v"].reshape(-1, 3)
+    rays = _random_rays(np.random.default_rng(12), 1000, v.min(0) - 0.5, v.max(0) + 0.5)
+    r.trace_mode(api.TraceMode.OCCLUDED_LANE)
+    occluded = r.trace_closest(rays)[:, 3].view(np.int32) >= 0
+    raw = np.zeros((len(rays), 2), np.uint32)
+    assert r.L.rt_trace_stats(r.h, rays.ctypes.data, len(rays), raw.ctypes.data) == 5  # RT_ERR_UNSUPPORTED
+    assert b"librestir_rt_exp" in r.L.rt_last_error(r.h) and not raw.any()
+    occ, passes, _ = r.trace_occluded_ws(rays)
+    assert 0.1 < occluded.mean() < 0.9 and (occ == occluded).all()
+    assert (passes[occluded] > 0).all()  # a ray is found occluded in a pass of its wavefront
+    r.close()
+
+
 def test_round3_entry_points(api, scenes):
     """rt_tuning_get reads back what rt_tuning set (and the defaults), rt_build_id names the build, rt_side_stream hands out
     the tail stream, rt_halo_fuse_set refuses to be called outside a spatial stage or for a side without a neighbour."""
@@ -704,14 +753,14 @@ def test_round3_entry_points(api, scenes):
     L = api.load_library(exp=True)
     r = api.Renderer(64, 48, exp=True)
     if not os.environ.get("RT_TUNING"):  # the defaults (soak runs force other settings through the environment)
-        assert r.tuning_get(5) == 3 and "SAH" in r.bvh_builder()      # default builder: the device SAH build
-        assert r.tuning_get(14) == -1 and r.tuning_get(17) == -1 and r.tuning_get(13) == 1
-        assert r.tuning_get(0) == -1 and r.tuning_get(2) == -1 and r.tuning_get(16) == -1 and r.tuning_get(19) == 1  # r04 autos
+        assert r.tuning_get(api.Tune.BVH_BUILDER) == 3 and "SAH" in r.bvh_builder()      # default builder: the device SAH build
+        assert r.tuning_get(api.Tune.SPEC) == -1 and r.tuning_get(api.Tune.TAIL) == -1 and r.tuning_get(api.Tune.WS) == 1
+        assert r.tuning_get(api.Tune.TILE_RAYCAST) == -1 and r.tuning_get(api.Tune.TILE_SPATIAL) == -1 and r.tuning_get(api.Tune.WS_PRIMARY) == -1 and r.tuning_get(api.Tune.MARK_WINDOW) == 1  # r04 autos
     for key, val in ((5, 1), (14, 2), (17, 1), (9, 5), (13, 0)):
         r.tuning(key, val)
         assert r.tuning_get(key) == val
     with pytest.raises(api.RtError):
-        r.tuning(5, 4)
+        r.tuning(api.Tune.BVH_BUILDER, 4)
     with pytest.raises(api.RtError):
         r.tuning_get(99)
     # the PRODUCT library carries none of the A/B forms and says so
@@ -821,7 +870,7 @@ def test_lds_staged_spatial_variant_is_bit_identical(api, scenes, W, H, optkw):
         r.set_scene(tris)
         r.lookat(eye, at)
         r.set_options(bench_options(**optkw))
-        r.tuning(8, variant)
+        r.tuning(api.Tune.SPATIAL_VARIANT, variant)
         rs.append(r)
     for frame in (1, 2, 3):
         for r in rs:
@@ -847,8 +896,8 @@ def test_candidate_kernel_variants_are_bit_identical(api, scenes):
         r.set_scene(tris)
         r.lookat((0.5, 2.5, 6.0), (0.0, 1.5, -1.0))
         r.set_options(bench_options())
-        r.tuning(11, k11)
-        r.tuning(12, k12)
+        r.tuning(api.Tune.DEFER_VIS, k11)
+        r.tuning(api.Tune.RIS_PIPE, k12)
         rs.append(r)
     shaded = None
     for frame in (1, 2, 3, 4):
@@ -880,7 +929,7 @@ def test_work_sharing_shadow_walk_is_bit_identical(api, scenes):
             r.set_scene(tris)
             r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
             r.set_options(bench_options())
-            r.tuning(13, ws)
+            r.tuning(api.Tune.WS, ws)
             rs.append(r)
         for frame in (1, 2, 3, 4):
             for r in rs:
@@ -905,7 +954,7 @@ def test_work_sharing_closest_hit_walk_is_bit_identical(api, scenes):
             r = api.Renderer(640, 360)
             r.set_scene(tris)
             r.lookat(eye, at)
-            r.tuning(16, ws)
+            r.tuning(api.Tune.WS_PRIMARY, ws)
             r.raycast()
             out.append(r.download(api.RT_BUF_VISIBILITY))
             r.close()
@@ -927,7 +976,7 @@ def test_resolve_as_a_stream_is_bit_identical(api, scenes):
             r.set_scene(tris)
             r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
             r.set_options(bench_options(accumulate=acc, spatial_resampling_radius=20.0))
-            r.tuning(15, stream)
+            r.tuning(api.Tune.STREAM, stream)
             rs.append(r)
         for frame in (1, 2, 3):
             for r in rs:
@@ -958,8 +1007,8 @@ def test_next_frame_raycast_overlap_is_bit_identical(api, scenes):
         r.set_scene(tris)
         r.lookat((0.5, 2.5, 6.0), (0.0, 1.5, -1.0))
         r.set_options(bench_options())
-        r.tuning(14, spec)
-        r.tuning(17, tail)
+        r.tuning(api.Tune.SPEC, spec)
+        r.tuning(api.Tune.TAIL, tail)
         rs.append(r)
     frame = 0
     steps = ("still", "still", "orbit", "still", "options", "still", "kernels", "still", "still", "upload", "still", "jump", "still",
@@ -1276,7 +1325,7 @@ def test_random_triangle_soups_differential(api, oracle, seed):
         for mode in (0, 1):
             acc = np.zeros((W * H, 4), np.float32)
             cnt = oracle.new_counters()
-            r.tuning(6, mode)
+            r.tuning(api.Tune.PT_WAVEFRONT, mode)
             r.path_trace(example, 3)
             sc.path_trace(example, W, H, 3, rg, popt, acc, cnt=cnt)
             got = r.download(api.RT_BUF_ACCUMULATION)

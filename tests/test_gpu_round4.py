@@ -12,6 +12,8 @@
 import numpy as np
 import pytest
 
+from cedec_2024_rt_amd.types import Tune as T
+
 pytestmark = pytest.mark.gpu
 
 FOVY = np.float32(np.pi) / np.float32(4)
@@ -60,8 +62,8 @@ def _oracle_frames(oracle, tris, W, H, eye, at, frames, **optkw):
 
 
 @pytest.mark.parametrize("W,H,frames,tuning", [
-    (480, 270, 12, {}),            # defaults: pipelined stage 0 (key 14) + tail stream (key 17), as bench.py runs
-    (480, 270, 12, {14: 1}),       # only the next frame's primary rays ahead
+    (480, 270, 12, {}),            # defaults: pipelined stage 0 (SPEC) + tail stream (TAIL), as bench.py runs
+    (480, 270, 12, {T.SPEC: 1}),       # only the next frame's primary rays ahead
     (1920, 1080, 6, {}),           # the benchmark's own size
 ])
 def test_timed_path_back_to_back_frames_vs_oracle(api, oracle, scenes, W, H, frames, tuning):
@@ -78,7 +80,7 @@ def test_timed_path_back_to_back_frames_vs_oracle(api, oracle, scenes, W, H, fra
     import os
 
     if not os.environ.get("RT_TUNING"):  # (soak runs force other settings through the environment)
-        assert r.tuning_get(14) == tuning.get(14, -1) and r.tuning_get(17) == -1  # the defaults bench.py runs with
+        assert r.tuning_get(api.Tune.SPEC) == tuning.get(T.SPEC, -1) and r.tuning_get(api.Tune.TAIL) == -1  # the defaults bench.py runs with
     r.set_scene(tris)
     r.lookat(eye, at)
     r.set_options(bench_options())
@@ -265,7 +267,7 @@ def test_walk_stats_account_for_every_reference_ray(api, oracle, scenes, shadowe
     W, H, frames = 480, 270, 3
     tris = scenes.make_blocks_restir()
     r = api.Renderer(W, H)
-    r.tuning(14, 0)  # every kernel exactly `frames` times (no stage 0 of a frame that is never rendered)
+    r.tuning(api.Tune.SPEC, 0)  # every kernel exactly `frames` times (no stage 0 of a frame that is never rendered)
     r.set_scene(tris)
     r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
     r.set_options(bench_options(use_shadowed_target_function=shadowed))

@@ -18,6 +18,8 @@ import time
 import numpy as np
 import pytest
 
+from cedec_2024_rt_amd.types import Tune as T
+
 pytestmark = pytest.mark.gpu
 
 FOVY = np.float32(np.pi) / np.float32(4)
@@ -65,35 +67,35 @@ def _oracle_frames(oracle, tris, W, H, eye, at, frames, **optkw):
 
 
 @pytest.mark.parametrize("W,H,frames,tuning,optkw", [
-    (480, 270, 12, {23: 1}, {}),                  # last pass + resolve fused, the pass's records stored
-    (480, 270, 12, {23: 2}, {}),                  # ... records kept in registers (A/B form)
-    (480, 270, 12, {23: 1, 20: 0}, {}),           # ... with the reference's separate tone_mapping launch
-    (480, 270, 12, {23: 1, 14: 0, 17: 0}, {}),    # ... frames back to back on one stream (the headline's form)
-    (480, 270, 7, {23: 1}, {"accumulate": 1}),    # ... accumulating (resolve reads the buffer it adds to)
-    (480, 270, 5, {23: 1}, {"spatial_resampling_passes": 1}),
-    (480, 270, 5, {23: 1}, {"spatial_resampling_passes": 2}),
-    (480, 270, 12, {22: 1}, {}),                  # free-running look-ahead on a whole frame
-    (480, 270, 12, {22: 1, 23: 1}, {}),
-    (480, 270, 12, {20: 0}, {}),                  # the reference's two tail launches
-    (1920, 1080, 6, {23: 1, 22: 1}, {}),          # the benchmark's own size
-    (480, 270, 6, {24: 1}, {}),                   # half-density raycast (32 rays + 32 helper lanes per wavefront)
-    (1920, 1080, 3, {24: 1, 22: 1}, {}),
-    (480, 270, 5, {0: 2, 1: 3, 2: 2, 3: 3}, {}),  # r05 tile orders: tile rows interleaved over the XCDs, row- / column-major
-    (480, 270, 5, {0: 4, 1: 5, 2: 4, 3: 5}, {}),  # ... tile b on XCD b % 8, row by row / in stripes of 32 tiles
-    (480, 270, 5, {0: 6, 1: 7, 2: 6, 3: 7}, {}),  # ... runs of 4 / 16 tiles per XCD
-    (500, 277, 4, {0: 5, 1: 6, 2: 7, 3: 2}, {}),  # ... on an image whose sides are no multiple of the tile
-    (480, 270, 5, {0: 0, 1: 1, 2: 0, 3: 1}, {}),  # the band orders of r01-r04
-    (480, 270, 4, {2: 7}, {"use_shadowed_target_function": 1}),
-    (480, 270, 5, {8: 4}, {}),                    # the pass as one-wavefront workgroups on 8 x 8 tiles (A/B form)
-    (1920, 1080, 3, {0: 7, 1: 4, 2: 5, 3: 6}, {}),
-    (480, 270, 8, {25: 0}, {}),                   # stage 0 as two launches (r01-r04) ...
-    (480, 270, 8, {25: 1}, {}),                   # ... and as one: primary ray, then candidates + temporal merge (the default)
-    (480, 270, 8, {25: 1, 14: 0, 17: 0}, {}),     # ... frames back to back on one stream (the headline's form)
-    (500, 277, 5, {25: 1, 22: 1}, {}),
-    (480, 270, 6, {25: 1}, {"accumulate": 1}),
-    (480, 270, 4, {25: 1}, {"use_temporal_resampling": 0}),   # no temporal merge: the one-launch form does not apply, two launches run
-    (480, 270, 3, {25: 1}, {"use_shadowed_target_function": 1}),
-    (1920, 1080, 4, {25: 1}, {}),
+    (480, 270, 12, {T.FUSE_FINAL: 1}, {}),                  # last pass + resolve fused, the pass's records stored
+    (480, 270, 12, {T.FUSE_FINAL: 2}, {}),                  # ... records kept in registers (A/B form)
+    (480, 270, 12, {T.FUSE_FINAL: 1, T.FUSE_TONEMAP: 0}, {}),           # ... with the reference's separate tone_mapping launch
+    (480, 270, 12, {T.FUSE_FINAL: 1, T.SPEC: 0, T.TAIL: 0}, {}),    # ... frames back to back on one stream (the headline's form)
+    (480, 270, 7, {T.FUSE_FINAL: 1}, {"accumulate": 1}),    # ... accumulating (resolve reads the buffer it adds to)
+    (480, 270, 5, {T.FUSE_FINAL: 1}, {"spatial_resampling_passes": 1}),
+    (480, 270, 5, {T.FUSE_FINAL: 1}, {"spatial_resampling_passes": 2}),
+    (480, 270, 12, {T.SPEC_FREE: 1}, {}),                  # free-running look-ahead on a whole frame
+    (480, 270, 12, {T.SPEC_FREE: 1, T.FUSE_FINAL: 1}, {}),
+    (480, 270, 12, {T.FUSE_TONEMAP: 0}, {}),                  # the reference's two tail launches
+    (1920, 1080, 6, {T.FUSE_FINAL: 1, T.SPEC_FREE: 1}, {}),          # the benchmark's own size
+    (480, 270, 6, {T.HALF_RAYCAST: 1}, {}),                   # half-density raycast (32 rays + 32 helper lanes per wavefront)
+    (1920, 1080, 3, {T.HALF_RAYCAST: 1, T.SPEC_FREE: 1}, {}),
+    (480, 270, 5, {T.TILE_RAYCAST: 2, T.TILE_GENERATE: 3, T.TILE_SPATIAL: 2, T.TILE_RESOLVE: 3}, {}),  # r05 tile orders: tile rows interleaved over the XCDs, row- / column-major
+    (480, 270, 5, {T.TILE_RAYCAST: 4, T.TILE_GENERATE: 5, T.TILE_SPATIAL: 4, T.TILE_RESOLVE: 5}, {}),  # ... tile b on XCD b % 8, row by row / in stripes of 32 tiles
+    (480, 270, 5, {T.TILE_RAYCAST: 6, T.TILE_GENERATE: 7, T.TILE_SPATIAL: 6, T.TILE_RESOLVE: 7}, {}),  # ... runs of 4 / 16 tiles per XCD
+    (500, 277, 4, {T.TILE_RAYCAST: 5, T.TILE_GENERATE: 6, T.TILE_SPATIAL: 7, T.TILE_RESOLVE: 2}, {}),  # ... on an image whose sides are no multiple of the tile
+    (480, 270, 5, {T.TILE_RAYCAST: 0, T.TILE_GENERATE: 1, T.TILE_SPATIAL: 0, T.TILE_RESOLVE: 1}, {}),  # the band orders of r01-r04
+    (480, 270, 4, {T.TILE_SPATIAL: 7}, {"use_shadowed_target_function": 1}),
+    (480, 270, 5, {T.SPATIAL_VARIANT: 4}, {}),                    # the pass as one-wavefront workgroups on 8 x 8 tiles (A/B form)
+    (1920, 1080, 3, {T.TILE_RAYCAST: 7, T.TILE_GENERATE: 4, T.TILE_SPATIAL: 5, T.TILE_RESOLVE: 6}, {}),
+    (480, 270, 8, {T.FUSE_RAYCAST: 0}, {}),                   # stage 0 as two launches (r01-r04) ...
+    (480, 270, 8, {T.FUSE_RAYCAST: 1}, {}),                   # ... and as one: primary ray, then candidates + temporal merge (the default)
+    (480, 270, 8, {T.FUSE_RAYCAST: 1, T.SPEC: 0, T.TAIL: 0}, {}),     # ... frames back to back on one stream (the headline's form)
+    (500, 277, 5, {T.FUSE_RAYCAST: 1, T.SPEC_FREE: 1}, {}),
+    (480, 270, 6, {T.FUSE_RAYCAST: 1}, {"accumulate": 1}),
+    (480, 270, 4, {T.FUSE_RAYCAST: 1}, {"use_temporal_resampling": 0}),   # no temporal merge: the one-launch form does not apply, two launches run
+    (480, 270, 3, {T.FUSE_RAYCAST: 1}, {"use_shadowed_target_function": 1}),
+    (1920, 1080, 4, {T.FUSE_RAYCAST: 1}, {}),
 ])
 def test_new_launch_forms_vs_oracle(api, oracle, scenes, W, H, frames, tuning, optkw):
     """blocks_restir, bench options, frames enqueued back to back with no sync in between; accumulation, pixels and the temporal
@@ -102,7 +104,7 @@ def test_new_launch_forms_vs_oracle(api, oracle, scenes, W, H, frames, tuning, o
 
     tris = scenes.make_blocks_restir()
     eye, at = scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT
-    r = api.Renderer(W, H, exp=bool({23, 24} & set(tuning)) or tuning.get(8) == 4)  # A/B forms: librestir_rt_exp.so
+    r = api.Renderer(W, H, exp=bool({T.FUSE_FINAL, T.HALF_RAYCAST} & set(tuning)) or tuning.get(T.SPATIAL_VARIANT) == 4)  # A/B forms: librestir_rt_exp.so
     for k, v in tuning.items():
         r.tuning(k, v)
     r.set_scene(tris)
@@ -131,7 +133,7 @@ def test_fused_final_pass_writes_the_reference_buffers(api, scenes):
     rs = []
     for fused in (0, 1):
         r = api.Renderer(W, H, exp=True)
-        r.tuning(23, fused)
+        r.tuning(api.Tune.FUSE_FINAL, fused)
         r.set_scene(tris)
         r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
         r.set_options(bench_options())
@@ -162,7 +164,7 @@ def test_fused_final_pass_on_three_local_strips_vs_oracle(api, oracle, scenes):
     ctxs = []
     for b in bounds:
         c = api.Renderer(W, H, rows=b, halo=87, exp=True)
-        c.tuning(23, 1)
+        c.tuning(api.Tune.FUSE_FINAL, 1)
         c.set_scene(tris)
         c.lookat(eye, at)
         c.set_options(bench_options())
@@ -197,7 +199,7 @@ def test_one_launch_stage0_on_three_local_strips_vs_oracle(api, oracle, scenes):
     ctxs = []
     for b in bounds:
         c = api.Renderer(W, H, rows=b, halo=87)
-        c.tuning(25, 1)
+        c.tuning(api.Tune.FUSE_RAYCAST, 1)
         c.set_scene(tris)
         c.lookat(eye, at)
         c.set_options(bench_options())
@@ -278,7 +280,7 @@ def test_cached_mark_rows_give_the_same_plans(api, scenes):
     out = []
     for cache in (1, 0):
         c = api.Renderer(W, H, rows=bounds[rank], halo=87)
-        c.tuning(21, cache)
+        c.tuning(api.Tune.MARK_CACHE, cache)
         c.set_scene(tris)
         c.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
         c.set_options(bench_options())

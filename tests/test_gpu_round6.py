@@ -59,14 +59,14 @@ def test_timed_frames_run_the_one_launch_stage0_and_match_the_oracle(api, oracle
     r.set_scene(tris)
     r.lookat(eye, at)
     r.set_options(bench_options())
-    r.tuning(16, 0)  # a 480 x 270 launch is "about one generation of wavefronts": auto would give its primary rays the strips' work-sharing walk, two launches
-    r.tuning(13, 1)  # the defaults this test is about, whatever RT_TUNING (soak runs) has set on the context
-    r.tuning(25, -1)
+    r.tuning(api.Tune.WS_PRIMARY, 0)  # a 480 x 270 launch is "about one generation of wavefronts": auto would give its primary rays the strips' work-sharing walk, two launches
+    r.tuning(api.Tune.WS, 1)  # the defaults this test is about, whatever RT_TUNING (soak runs) has set on the context
+    r.tuning(api.Tune.FUSE_RAYCAST, -1)
     r.timing_enable(True)
     forms = []
     for f in range(1, frames + 1):
         if f == 4:
-            r.tuning(25, 0)  # the reference's two kernels under the same events
+            r.tuning(api.Tune.FUSE_RAYCAST, 0)  # the reference's two kernels under the same events
         r.frame(f)
         t = r.timing()
         forms.append(r.stage0_one_launch())
@@ -127,9 +127,9 @@ def test_halo_marks_one_workgroup_per_tile_and_pass_give_the_same_plans(api, sce
     out = {}
     for split, window in ((1, 1), (0, 1), (1, 0), (0, 0)):
         c = api.Renderer(W, H, rows=bounds[rank], halo=87)
-        c.tuning(26, split)
-        c.tuning(19, window)
-        assert c.tuning_get(26) == split  # default 0 (measured: no gain)
+        c.tuning(api.Tune.MARK_SPLIT, split)
+        c.tuning(api.Tune.MARK_WINDOW, window)
+        assert c.tuning_get(api.Tune.MARK_SPLIT) == split  # default 0 (measured: no gain)
         c.set_scene(tris)
         c.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
         c.set_options(bench_options())
@@ -157,7 +157,7 @@ def test_halo_marks_one_workgroup_per_tile_and_pass_give_the_same_plans(api, sce
 
 
 def test_four_lanes_per_primary_ray_writes_the_same_gbuffer(api, oracle, scenes):
-    """rt_tuning 16 = 2 (k_raycast_quad, bvh.h closest_quad): rt_raycast with 16 rays per wavefront, each lane one child box of the
+    """RT_TUNE_WS_PRIMARY = 2 (k_raycast_quad, bvh.h closest_quad): rt_raycast with 16 rays per wavefront, each lane one child box of the
     4-wide record == the one-lane-per-ray walks, Visibility records byte for byte (whole image, a strip with a ragged width, a tiny
     image), and whole strip frames through rt_frame_stage against the oracle (10_restir_di.cu:9-34 behind common/raytrace.hpp:18-43)"""
     from cedec_2024_rt_amd.types import bench_options
@@ -167,8 +167,8 @@ def test_four_lanes_per_primary_ray_writes_the_same_gbuffer(api, oracle, scenes)
     for W, H, rows in ((480, 270, None), (1918, 1080, (405, 540)), (37, 19, None)):
         vis = {}
         for mode in (0, 1, 2):
-            r = api.Renderer(W, H, rows=rows, halo=87 if rows else 0, exp=True)  # 16 = 2: librestir_rt_exp.so
-            r.tuning(16, mode)
+            r = api.Renderer(W, H, rows=rows, halo=87 if rows else 0, exp=True)  # WS_PRIMARY = 2 is in librestir_rt_exp.so
+            r.tuning(api.Tune.WS_PRIMARY, mode)
             r.set_scene(tris)
             r.lookat(eye, at)
             r.set_options(bench_options())
@@ -186,7 +186,7 @@ def test_four_lanes_per_primary_ray_writes_the_same_gbuffer(api, oracle, scenes)
     ctxs = []
     for b in bounds:
         c = api.Renderer(W, H, rows=b, halo=87, exp=True)
-        c.tuning(16, 2)
+        c.tuning(api.Tune.WS_PRIMARY, 2)
         c.set_scene(tris)
         c.lookat(eye, at)
         c.set_options(bench_options())
@@ -234,11 +234,11 @@ def test_look_ahead_soak_camera_moves_key22_toggles_and_per_kernel_calls_between
         elif ev == 1:
             v = int(rng.choice([-1, 0, 1]))
             for r in rig.everyone():
-                r.tuning(22, v)
+                r.tuning(api.Tune.SPEC_FREE, v)
         elif ev == 2:
             v = int(rng.choice([-1, 0, 1, 2]))
             for r in rig.everyone():
-                r.tuning(14, v)
+                r.tuning(api.Tune.SPEC, v)
         elif ev == 3:
             for r in rig.everyone():
                 r.raycast()

@@ -19,6 +19,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from cedec_2024_rt_amd.types import TraceMode, Tune
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -120,16 +122,16 @@ def _updates(scenes, tris, seed):
 
 def _check_walks(r, tris, rays, oracle, what):
     ref = oracle.Scene(tris, use_bvh=False).trace_closest(rays, force_brute=True)
-    for mode in (0,):
+    for mode in (TraceMode.WIDE,):
         r.trace_mode(mode)
         dev = r.trace_closest(rays)
         assert _eq_bits(dev, ref), f"{what}: mode {mode}: {_diff(dev, ref)} rays differ"
     hit = ref[:, 3].view(np.int32) >= 0
-    for mode in (4, 5, 6):  # any-hit walks: occluded <=> a closest hit exists
+    for mode in (TraceMode.WIDE_ANY, TraceMode.OCCLUDED_WS, TraceMode.OCCLUDED_LANE):  # any-hit walks: occluded <=> a closest hit exists
         r.trace_mode(mode)
         occ = r.trace_closest(rays)[:, 3].view(np.int32) >= 0
         assert (occ == hit).all(), f"{what}: any-hit mode {mode}: {int((occ != hit).sum())} rays differ"
-    r.trace_mode(0)
+    r.trace_mode(TraceMode.WIDE)
     occ, _, _ = r.trace_occluded_ws(rays)
     assert (occ == hit).all(), f"{what}: work-sharing walk"
     holes = rays.copy()
@@ -155,7 +157,7 @@ def test_refitted_walks_equal_brute_force(api, oracle, scenes, golden_scenes):
         for bfs in (None, 0):
             r = api.Renderer(8, 8)
             if bfs is not None:
-                r.tuning(7, bfs)
+                r.tuning(Tune.BVH_BFS_RECORDS, bfs)
             r.set_scene(tris)
             info = r.bvh_info()
             for label, first, span, whole in _updates(scenes, tris, 5):
@@ -177,9 +179,9 @@ def test_refit_every_builder_of_the_experiments_library(api, oracle, scenes, gol
     for name, tris in (("cornellbox1", golden_scenes["cornellbox1"]), ("soup", _soup(6, 4000))):
         for builder, bfs in ((0, None), (1, None), (2, None), (3, None), (0, 100000), (1, 0)):
             r = api.Renderer(8, 8, exp=True)
-            r.tuning(5, builder)
+            r.tuning(Tune.BVH_BUILDER, builder)
             if bfs is not None:
-                r.tuning(7, bfs)
+                r.tuning(Tune.BVH_BFS_RECORDS, bfs)
             r.set_scene(tris)
             info = r.bvh_info()
             for label, first, span, whole in _updates(scenes, tris, 9)[2:4]:
@@ -188,9 +190,9 @@ def test_refit_every_builder_of_the_experiments_library(api, oracle, scenes, gol
                 rays = _random_rays(rng, 4000, v.min(0) - 0.5, v.max(0) + 0.5)
                 _check_walks(r, whole, rays, oracle, f"{name} builder {builder} bfs {bfs}: {label}")
                 assert r.bvh_info() == info
-            r.trace_mode(1)
+            r.trace_mode(TraceMode.BINARY)
             assert r.L.rt_trace_closest(r.h, rays.ctypes.data, len(rays), np.zeros((len(rays), 4), np.float32).ctypes.data) == RT_ERR_STATE
-            r.trace_mode(0)
+            r.trace_mode(TraceMode.WIDE)
             r.close()
 
 
@@ -414,11 +416,11 @@ def test_deep_deck_deformed_and_refitted(api, oracle):
     rays[::7, 6] = 500.0
     ref = oracle.Scene(new, use_bvh=False).trace_closest(rays, force_brute=True)
     assert (ref[:, 3].view(np.int32) >= 0).mean() > 0.5
-    for mode in (0,):
+    for mode in (TraceMode.WIDE,):
         r.trace_mode(mode)
         dev = r.trace_closest(rays)
         assert _eq_bits(dev, ref), f"mode {mode}: {_diff(dev, ref)} rays differ"
-    for mode in (4, 6):
+    for mode in (TraceMode.WIDE_ANY, TraceMode.OCCLUDED_LANE):
         r.trace_mode(mode)
         occ = r.trace_closest(rays)[:, 3].view(np.int32) >= 0
         assert (occ == (ref[:, 3].view(np.int32) >= 0)).all(), f"any-hit mode {mode}"

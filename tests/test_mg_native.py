@@ -308,8 +308,8 @@ def test_halo_mark_quick_reject_marks_the_same_records():
         for frame in (1, 2, 3, 4):
             got = []
             for quick, window in ((0, 0), (1, 0), (0, 1), (1, 1)):  # key 19 (r04): marks collected in an LDS window per workgroup
-                mid.tuning(18, quick)
-                mid.tuning(19, window)
+                mid.tuning(api.Tune.MARK_QUICK, quick)
+                mid.tuning(api.Tune.MARK_WINDOW, window)
                 bm = torch.full((2, 3 * words), -1, dtype=torch.int32, device="cuda")
                 torch.cuda.synchronize()  # torch fills on its own stream; the context marks on its non-blocking stream
                 rc = L.rt_halo_mark_sides(mid.h, frame, 0, 3, C.c_void_p(bm[0].data_ptr()), C.c_void_p(bm[1].data_ptr()))

@@ -1,5 +1,5 @@
 """GPU. Ambient occlusion at 1920x1080 on blocks_ao.obj (same scene, size, camera (8,8,8) -> (0,0,0)
-and 64 rays per hit pixel) through rt_path_trace(ctx, 6, 0), both layouts of rt_tuning key 27 alternated in ONE process.
+and 64 rays per hit pixel) through rt_path_trace(ctx, 6, 0), both layouts of RT_TUNE_AO_LAYOUT (rt_tuning key 27) alternated in ONE process.
 
 Every repeat times, for each layout in turn, `--launches` launches after one warm-up (host clock around rt_sync; the launches
 are back to back on the context's stream). Reported per layout: median / min / max ms per launch over the repeats, Gray/s in
@@ -43,7 +43,9 @@ def make_renderer():
 
 
 def timed(r, layout, launches):
-    r.tuning(27, layout)
+    from cedec_2024_rt_amd.types import Tune
+
+    r.tuning(Tune.AO_LAYOUT, layout)
     r.path_trace(6, 0)  # warm-up
     r.sync()
     t0 = time.perf_counter()
@@ -82,7 +84,7 @@ def measure(reps, launches):
         }
     r.close()
     d = make_renderer()
-    out["default_layout"] = d.tuning_get(27)
+    out["default_layout"] = d.tuning_get(api.Tune.AO_LAYOUT)
     d.close()
     return out
 

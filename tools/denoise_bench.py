@@ -45,8 +45,8 @@ def main():
     r.set_scene(scenes.make_blocks_restir())
     r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
     r.set_options(bench_options(accumulate=1))
-    r.tuning(25, 0)  # the frame's raycast as a launch of its own (timed as ms[1])
-    r.tuning(14, 0)
+    r.tuning(api.Tune.FUSE_RAYCAST, 0)  # the frame's raycast as a launch of its own (timed as ms[1])
+    r.tuning(api.Tune.SPEC, 0)
     r.timing_enable(True)
     raycast = []
     for f in range(1, 4 + a.reps):
@@ -57,7 +57,7 @@ def main():
     out = dict(tool="tools/denoise_bench.py", build_id=api.build_id(), size=[W, H], scene="scenes.make_blocks_restir (bench stand-in)",
                reps=a.reps, unit="ms (median, HIP events on the context's stream)", raycast_ms=float(np.median(raycast)), layouts={})
     for lay in (0, 1):
-        r.tuning(28, lay)
+        r.tuning(api.Tune.DN_LAYOUT, lay)
         rows = {}
         for it in range(1, 9):
             for _ in range(a.warmup):
@@ -96,7 +96,7 @@ def temporal(a):
                unit="ms (median, HIP events on the context's stream)", layouts={})
     frame = 0
     for lay in (0, 1):
-        r.tuning(28, lay)
+        r.tuning(api.Tune.DN_LAYOUT, lay)
         rows = {}
         for it in (0, 1, 5, 8):
             r.denoise_temporal_reset()

@@ -16,9 +16,10 @@ sys.path.insert(0, ROOT)
 from cedec_2024_rt_amd import api, scenes  # noqa: E402
 from cedec_2024_rt_amd.types import bench_options  # noqa: E402
 
-FORMS = (("plain walk", {16: 0, 24: 0}), ("work-sharing walk", {16: 1, 24: 0}), ("half density + helpers", {16: 1, 24: 1}),
-         ("four lanes per ray (r06, key 16 = 2)", {16: 2, 24: 0}))
-if os.environ.get("RAYCAST_FORMS"):  # e.g. RAYCAST_FORMS=0,1,3 with RT_LIB_PATH=<a product-library variant> (it refuses the experiments' key 24)
+WS_PRIMARY, HALF_RAYCAST = api.Tune.WS_PRIMARY, api.Tune.HALF_RAYCAST
+FORMS = (("plain walk", {WS_PRIMARY: 0, HALF_RAYCAST: 0}), ("work-sharing walk", {WS_PRIMARY: 1, HALF_RAYCAST: 0}),
+         ("half density + helpers", {WS_PRIMARY: 1, HALF_RAYCAST: 1}), ("four lanes per ray (r06)", {WS_PRIMARY: 2, HALF_RAYCAST: 0}))
+if os.environ.get("RAYCAST_FORMS"):  # e.g. RAYCAST_FORMS=0,1,3 with RT_LIB_PATH=<a product-library variant> (it refuses the experiments' HALF_RAYCAST)
     FORMS = tuple(FORMS[int(i)] for i in os.environ["RAYCAST_FORMS"].split(","))
 tris = scenes.make_blocks_restir()
 for case in sys.argv[1:] or ["1920x1080:135", "1920x1080:270", "1920x1080:1080", "3840x2160:270"]:
@@ -34,7 +35,7 @@ for case in sys.argv[1:] or ["1920x1080:135", "1920x1080:270", "1920x1080:1080",
     line = []
     for name, keys in FORMS:
         for k, v in keys.items():
-            if k != 24 or v != 0 or not os.environ.get("RAYCAST_FORMS"):
+            if k != HALF_RAYCAST or v != 0 or not os.environ.get("RAYCAST_FORMS"):
                 r.tuning(k, v)
         r.clear()
         for _ in range(20):

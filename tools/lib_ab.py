@@ -60,19 +60,19 @@ def main():
                 row = {}
                 for label, t14, t17 in (("unpipelined", 0, 0), ("pipelined", -1, -1)):
                     r.timing_enable(False)
-                    r.tuning(14, t14)
-                    r.tuning(17, t17)
+                    r.tuning(api.Tune.SPEC, t14)
+                    r.tuning(api.Tune.TAIL, t17)
                     run(n, 6)
                     r.sync()
                     t0 = time.perf_counter()
                     run(n, args.frames)
                     r.sync()
                     row[label] = round((time.perf_counter() - t0) / args.frames * 1e3, 4)
-                r.tuning(14, 0)
-                r.tuning(17, 0)
+                r.tuning(api.Tune.SPEC, 0)
+                r.tuning(api.Tune.TAIL, 0)
                 r.timing_enable(True)
                 for form, t25 in (("one", -1), ("two", 0)):
-                    r.tuning(25, t25)
+                    r.tuning(api.Tune.FUSE_RAYCAST, t25)
                     acc = []
                     for _ in range(24):
                         frame[n] += 1
@@ -84,7 +84,7 @@ def main():
                         row.update(stage0=round(float(m[0] + m[1]), 4), spatial=round(float(m[2:5].mean()), 4), resolve=round(float(m[5]), 4), frame_events=round(float(m[6]), 4))
                     else:
                         row.update(raycast=round(float(m[0]), 4), generate=round(float(m[1]), 4))
-                r.tuning(25, -1)
+                r.tuning(api.Tune.FUSE_RAYCAST, -1)
                 r.timing_enable(False)
                 res[n].append(row)
                 print(f"{W}x{H} rep {rep} {n}: {json.dumps(row)}", flush=True)

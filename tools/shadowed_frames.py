@@ -17,7 +17,7 @@ r = api.Renderer(W, H)
 r.set_scene(scenes.make_blocks_restir())
 r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
 r.set_options(bench_options(use_shadowed_target_function=1))
-r.tuning(14, 0)  # per-kernel numbers: no overlap between frames
+r.tuning(api.Tune.SPEC, 0)  # per-kernel numbers: no overlap between frames
 for f in range(1, n + 1):
     r.frame(f)
 r.sync()

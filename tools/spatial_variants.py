@@ -32,9 +32,9 @@ for name, key4, key8, key9 in CASES:
     r.set_scene(tris)
     r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
     r.set_options(bench_options())
-    r.tuning(4, key4)
-    r.tuning(8, key8)
-    r.tuning(9, key9)
+    r.tuning(api.Tune.SPATIAL_LDS, key4)
+    r.tuning(api.Tune.SPATIAL_VARIANT, key8)
+    r.tuning(api.Tune.SPATIAL_WAVES, key9)
     for f in range(1, 6):
         r.frame(f)
     r.timing_enable(True)

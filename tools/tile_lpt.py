@@ -22,8 +22,8 @@ r = api.Renderer(W, H, exp=True)
 r.set_scene(scenes.make_blocks_restir())
 r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
 r.set_options(bench_options())
-r.tuning(14, 0)
-r.tuning(17, 0)
+r.tuning(api.Tune.SPEC, 0)
+r.tuning(api.Tune.TAIL, 0)
 clock = r.L.rt_exp_wave_clock
 clock.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
 clock.restype = C.c_int

@@ -62,11 +62,11 @@ def report(name, mode, rays, live):
     print(f"{name}: per-wave passes {q(wave)}   (slowest / mean = {wave.max() / wave.mean():.1f})", flush=True)
 
 
-report("shadow rays (any hit)", 4, shadow, sh)
-report("primary rays (closest)", 0, prim, np.ones(len(prim), bool))
+report("shadow rays (any hit)", api.TraceMode.WIDE_ANY, shadow, sh)
+report("primary rays (closest)", api.TraceMode.WIDE, prim, np.ones(len(prim), bool))
 
 # the work-sharing walk (occluded_ws): passes per wavefront and steals
-r.trace_mode(5)
+r.trace_mode(api.TraceMode.OCCLUDED_WS)
 st = r.trace_stats(shadow)  # masked to 16 bits by the binding: use the raw call
 import ctypes as C
 raw = np.zeros((len(shadow), 2), dtype=np.uint32)
@@ -85,10 +85,9 @@ wave = wave[keep]
 print("work-sharing shadow rays: per-wave passes mean %.1f p50 %d p90 %d p99 %d max %d; steals per wavefront %.1f; inner records per lane mean %.1f (sum over a wave / 64 = %.1f)" % (
     wave.mean(), *np.percentile(wave, [50, 90, 99]).astype(int), wave.max(), steals.reshape(-1, 64).sum(1).mean(), steps[sh].mean(), steps.reshape(-1, 64).sum(1).mean() / 64), flush=True)
 
-# device time of the same shadow rays from a list: persistent lane-refill queue (3), 256-thread workgroups one lane per
-# ray (4), one-wavefront workgroups with the work-sharing walk (5) and without (6)
-for mode, name in ((3, "persistent queue, lanes refilled with new rays"), (4, "one lane per ray, 256-thread workgroups"),
-                   (6, "one lane per ray, one-wavefront workgroups"), (5, "work-sharing walk, one-wavefront workgroups")):
+# device time of the same shadow rays from a list
+for mode, name in ((api.TraceMode.QUEUE_ANY, "persistent queue, lanes refilled with new rays"), (api.TraceMode.WIDE_ANY, "one lane per ray, 256-thread workgroups"),
+                   (api.TraceMode.OCCLUDED_LANE, "one lane per ray, one-wavefront workgroups"), (api.TraceMode.OCCLUDED_WS, "work-sharing walk, one-wavefront workgroups")):
     r.trace_mode(mode)
     ts = []
     for _ in range(5):

@@ -27,8 +27,8 @@ r = api.Renderer(W, H, rows=rows, halo=87 if rows else 0, exp=True)
 r.set_scene(scenes.make_blocks_restir())
 r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
 r.set_options(bench_options())
-r.tuning(14, 0)
-r.tuning(17, 0)
+r.tuning(api.Tune.SPEC, 0)
+r.tuning(api.Tune.TAIL, 0)
 for kv in args:
     k, v = kv.split("=")
     r.tuning(int(k), int(v))
