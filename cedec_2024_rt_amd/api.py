@@ -43,7 +43,7 @@ INTERNAL_EXPORTS = [
     "rt_mg_load_error", "rt_mg_hub_create", "rt_mg_hub_destroy", "rt_mg_frame_begin", "rt_mg_frame_step", "rt_mg_reset_stats",
     "rt_mg_selftest_rccl", "rt_visibility_rays_walked", "rt_walk_stats_enable", "rt_walk_stats", "rt_stage0_one_launch",
     "rt_row_shaded", "rt_spatial_bytes", "rt_trace_closest", "rt_trace_stats", "rt_bvh_config", "rt_bvh_info", "rt_build_ms",
-    "rt_trace_mode", "rt_trace_time", "rt_tuning", "rt_tuning_get", "rt_math_eval",
+    "rt_trace_mode", "rt_trace_time", "rt_tuning", "rt_tuning_get", "rt_math_eval", "rt_gbuffer_reuse", "rt_primary_launches",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -175,6 +175,10 @@ def load_library(exp=False, path=None):
     L.rt_build_id.restype = C.c_char_p
     L.rt_row_shaded.argtypes = [vp, vp]
     L.rt_stage0_one_launch.argtypes = [vp, vp]
+    # r13; an older build of the library (RT_LIB_PATH: A/B runs against the parent commit) has neither: it traces every frame
+    if hasattr(L, "rt_gbuffer_reuse"):
+        L.rt_gbuffer_reuse.argtypes = [vp, ci]
+        L.rt_primary_launches.argtypes = [vp, vp]
     L.rt_visibility_rays_walked.argtypes = [vp, vp]
     L.rt_state_epoch.argtypes = [vp, vp]
     L.rt_get_stream.argtypes = [vp, vp]
@@ -380,6 +384,10 @@ class Renderer:
         for kv in filter(None, os.environ.get("RT_TUNING", "").split(",")):
             k, v = kv.split("=")
             self._ck(self.L.rt_tuning(self.h, int(k), int(v)))
+        # A/B runs: RT_GBUFFER_REUSE=0 makes every frame of every context trace its primary rays (rt_gbuffer_reuse; a library
+        # without the call does that anyway)
+        if os.environ.get("RT_GBUFFER_REUSE", "") == "0" and hasattr(self.L, "rt_gbuffer_reuse"):
+            self._ck(self.L.rt_gbuffer_reuse(self.h, 0))
         a, b = C.c_int(), C.c_int()
         self._ck(self.L.rt_local_rows(self.h, C.byref(a), C.byref(b)))
         self.local_row0, self.local_rows = a.value, b.value
@@ -712,6 +720,23 @@ class Renderer:
         v = C.c_int()
         self._ck(self.L.rt_stage0_one_launch(self.h, C.byref(v)))
         return bool(v.value)
+
+    def gbuffer_reuse(self, on=True):
+        """stage 0 of a staged frame launches no primary rays while the G-buffer traced under the current camera / scene / options
+        is still there (default on; whole-frame contexts only). A library without the call traces every frame: on=False is then a
+        no-op and on=True an error."""
+        if not hasattr(self.L, "rt_gbuffer_reuse"):
+            if on:
+                raise RtError("this build of librestir_rt has no rt_gbuffer_reuse: every frame traces its primary rays")
+            return
+        self._ck(self.L.rt_gbuffer_reuse(self.h, int(bool(on))))
+
+    def primary_launches(self):
+        """launches so far that traced primary rays over the context's rows (rt_raycast, stage-0 raycasts, the one-launch stage 0,
+        look-ahead raycasts)"""
+        v = C.c_uint64()
+        self._ck(self.L.rt_primary_launches(self.h, C.byref(v)))
+        return v.value
 
     def build_id(self):
         """rt_build_id() of the library THIS context runs (product or experiments)"""

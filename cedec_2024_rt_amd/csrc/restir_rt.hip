@@ -195,6 +195,14 @@ struct rt_ctx
                                 the marks are not on the frame's critical chain and their total work is the same. Default off. */
     int tune_mark_cache = 1; /* rt_tuning key 21 (r05): the shaded-bit rows of the halo marks are built once per epoch */
     uint64_t mark_bits_epoch = 0, gbuf_epoch = 0; /* epoch d_mark_bits was built under (0: not cached) / the current G-buffer was traced under */
+    /* r13, rt_gbuffer_reuse: the primary ray of a pixel has no jitter and no frame number in it (frame_kernels.h, shoot(xi / W, yi / H)),
+     * so Visibility / g0 / g1 are a function of camera, scene and image size: of `epoch`. A staged frame of a whole-frame context whose
+     * current set was traced over all owned rows under the current epoch launches its candidates on that set and no primary rays
+     * (gbuffer_reusable). gbuf_traced_epoch: the epoch under which ALL owned rows of set gcur were traced by a raycast launch or the
+     * one-launch stage 0 (0 = never; an upload bumps `epoch` and does not set it: k_gbuffer_from_vis is not a trace).
+     * gbuf_spec_ordered: spec_stream is known to be behind the launch that wrote the set (the look-ahead candidates read it there). */
+    bool gbuf_reuse = true, gbuf_spec_ordered = false, spec_reuse = false;
+    uint64_t gbuf_traced_epoch = 0, primary_launches = 0;
     hipEvent_t ev_mark_bits = nullptr;
     bool mark_bits_event_valid = false, mark_bits_rebuilt = false;
     int tune_fuse_tonemap = 1; /* rt_tuning key 20 (r05): the staged frame's resolve kernel tone-maps its own pixel */
@@ -1482,6 +1490,22 @@ static void launch_raycast(rt_ctx* c, const Launch& L)
     if (use_ws_primary(c, g)) k_raycast<true><<<g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), P, L.vis, L.g0, L.g1);
     else k_raycast<false><<<g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), P, L.vis, L.g0, L.g1);
 }
+/* a launch on L.stream has traced primary rays into the CURRENT G-buffer set (rt_primary_launches counts it): over all owned rows it
+ * makes the set the answer for `epoch` (gbuffer_reusable); over a sub-range it leaves gbuf_traced_epoch alone — either the set was
+ * the answer already and the rows got the same bytes, or it is of an older epoch, which never comes back */
+static void note_primary_launch(rt_ctx* c, const Launch& L, uint64_t epoch)
+{
+    ++c->primary_launches;
+    if (L.row0 == c->row_begin && L.row1 == c->row_end && L.rowb1 <= L.rowb0) c->gbuf_traced_epoch = epoch;
+    if (L.stream != c->spec_stream) c->gbuf_spec_ordered = false;
+}
+/* r13 (rt_gbuffer_reuse): stage 0 of a staged frame needs no primary rays — the current set holds what they would write. Whole-frame
+ * contexts only (a strip's marks wait for the raycast's event, and r05 bounded the gain there at 0-9 % of a strip's frame); not while
+ * rt_walk_stats counts (the counters of slot 0 are the raycast's). */
+static bool gbuffer_reusable(const rt_ctx* c)
+{
+    return c->gbuf_reuse && c->row_begin == 0 && c->row_end == c->H && !c->walk_on && c->has_gbuffer && c->gbuf_traced_epoch == c->epoch;
+}
 /* rt_raycast over the launch's rows, with everything it does to the context's state */
 static int raycast_rows(rt_ctx* c, const Launch& L)
 {
@@ -1494,6 +1518,7 @@ static int raycast_rows(rt_ctx* c, const Launch& L)
     c->has_gbuffer = true;
     ++c->gbuf_serial;
     c->gbuf_epoch = c->epoch;
+    note_primary_launch(c, L, c->epoch);
     c->shaded_bits_stale = true;
     /* halo rows of the G-buffer keep the neighbours' shaded flags: they stay valid until the camera,
      * the scene or the options change (halo_flags_epoch), which is when the neighbours' G-buffers change */
@@ -1551,8 +1576,12 @@ static int launch_next_raycast(rt_ctx* c, int frame)
     c->spec_gen_valid = false;
     if (!use_next_raycast(c, c->timing)) { c->spec_valid = false; return RT_OK; }
     const bool next_generate = use_next_generate(c, c->timing);
+    /* r13: the set the running frame reads is the next frame's too (gbuffer_reusable): the look-ahead is the candidates alone, reading
+     * set gcur; set o is neither written nor, in a steady run, ever allocated, and the take does not rotate gcur */
+    const bool reuse = gbuffer_reusable(c);
+    if (reuse && !(next_generate && c->n_lights > 0)) { c->spec_valid = false; return RT_OK; } /* nothing to run ahead */
     const size_t n = local_pixels(c);
-    const int o = (c->gcur + 1) % rt_ctx::NGSET;
+    const int o = reuse ? c->gcur : (c->gcur + 1) % rt_ctx::NGSET;
     bool fresh_set = false;
     if (!c->d_gset[o][0])
     {
@@ -1567,10 +1596,12 @@ static int launch_next_raycast(rt_ctx* c, int frame)
      * buffer overwritten below were last read two resolves ago (r05) — the look-ahead runs on, beside whatever the main and the
      * tail stream are doing. (r04 waited here for the main stream, i.e. for the previous frame's passes, and for the previous
      * frame's resolve: raycast(f+2) could not start before resolve(f) had ended.) */
-    if (!c->gen_taken || fresh_set || !spec_free(c))
+    /* r13: candidates that read the current set wait for the main stream also where a launch there wrote that set last */
+    if (!c->gen_taken || fresh_set || !spec_free(c) || (reuse && !c->gbuf_spec_ordered))
     {
         RT_HIP(c, hipEventRecord(c->ev_spec_go, c->stream));
         RT_HIP(c, hipStreamWaitEvent(c->spec_stream, c->ev_spec_go, 0));
+        c->gbuf_spec_ordered = true; /* whatever wrote set gcur was enqueued before this point */
     }
     /* the G-buffer set and the spare reservoir buffer written below: last read by the resolve before the latest one (the set of
      * frame f-2; the buffer that left the roles when frame f-1 was taken) — or earlier */
@@ -1581,18 +1612,22 @@ static int launch_next_raycast(rt_ctx* c, int frame)
     /* the invariants the free-running look-ahead rests on, checked where it writes (cheap integer tests, every build): the set it
      * overwrites is not the one the running frame reads, and the candidates' buffer has no role in the running frame nor is it
      * what the tail in flight reads */
-    if (o == c->gcur) RT_FAIL(c, RT_ERR_STATE, "look-ahead stage 0 would overwrite the running frame's G-buffer set %d", o);
+    if (!reuse && o == c->gcur) RT_FAIL(c, RT_ERR_STATE, "look-ahead stage 0 would overwrite the running frame's G-buffer set %d", o);
     if (next_generate && (c->spare == c->fX || c->spare == c->fY || c->spare == c->fZ || c->spare == c->quarantine ||
                                  (spec_free(c) && c->tail_pending_main && c->spare == c->tail_phys))) /* r04's dependencies hand the tail's buffer over and wait for the latest resolve above */
         RT_FAIL(c, RT_ERR_STATE, "look-ahead candidates' buffer %d is in use (X %d Y %d Z %d quarantine %d tail %d)", c->spare, c->fX, c->fY, c->fZ, c->quarantine, c->tail_pending_main ? c->tail_phys : -1);
     Launch spec = whole_launch(c); /* all owned rows, on the stream of its own, into set o */
     spec.stream = c->spec_stream; spec.vis = c->d_gset[o][0]; spec.g0 = c->d_gset[o][1]; spec.g1 = c->d_gset[o][2];
-    if (c->timing) hipEventRecord(c->ev_spec_t[o][0], spec.stream);
-    const bool one_launch = next_generate && use_fused_stage0(c); /* the candidates' launch below traces the primary rays too */
-    if (!one_launch) launch_raycast(c, spec);
-    RT_HIP(c, hipGetLastError());
-    if (c->timing) hipEventRecord(c->ev_spec_t[o][1], spec.stream);
-    c->spec_timed[o] = c->timing;
+    const bool one_launch = !reuse && next_generate && use_fused_stage0(c); /* the candidates' launch below traces the primary rays too */
+    if (!reuse)
+    {
+        if (c->timing) hipEventRecord(c->ev_spec_t[o][0], spec.stream);
+        if (!one_launch) launch_raycast(c, spec);
+        RT_HIP(c, hipGetLastError());
+        if (c->timing) hipEventRecord(c->ev_spec_t[o][1], spec.stream);
+        c->spec_timed[o] = c->timing;
+        ++c->primary_launches; /* into set o: it becomes the current set, and gbuf_traced_epoch its epoch, at the take */
+    }
     if (next_generate && c->n_lights > 0)
     {
         /* candidates (+ temporal merge) of frame + 1: G-buffer = the set just traced, history = the buffer this frame's
@@ -1617,19 +1652,27 @@ static int launch_next_raycast(rt_ctx* c, int frame)
     RT_HIP(c, hipEventRecord(c->ev_spec_done, spec.stream));
     c->spec_outstanding = true;
     c->spec_valid = true;
+    c->spec_reuse = reuse;
     c->spec_epoch = c->epoch;
     return RT_OK;
 }
 /* stage 0's raycast over all owned rows: the G-buffer traced beside the previous frame if it is still the right one */
 /* L: the stage's launch; a take moves it to the taken G-buffer set and, with the candidates, to their tag */
-static int raycast_or_take(rt_ctx* c, Launch& L, bool whole, int frame, bool may_defer = false, bool* deferred = nullptr)
+/* r13: *reused = the stage launches no primary rays at all, the current set is still the answer (gbuffer_reusable) */
+static int raycast_or_take(rt_ctx* c, Launch& L, bool whole, int frame, bool may_defer, bool* deferred, bool* reused)
 {
     c->timed_spec_set = -1;
     c->gen_taken = false;
-    if (whole && use_next_raycast(c, L.timed) && c->spec_valid && c->spec_epoch == c->epoch)
+    /* a look-ahead that read the current set (spec_reuse) is good for as long as that set is */
+    if (whole && use_next_raycast(c, L.timed) && c->spec_valid && c->spec_epoch == c->epoch && (!c->spec_reuse || gbuffer_reusable(c)))
     {
-        c->gcur = (c->gcur + 1) % rt_ctx::NGSET;
-        L.vis = c->d_vis = c->d_gset[c->gcur][0]; L.g0 = c->d_g0 = c->d_gset[c->gcur][1]; L.g1 = c->d_g1 = c->d_gset[c->gcur][2];
+        const bool traced = !c->spec_reuse; /* the look-ahead traced set gcur + 1; otherwise only its candidates are taken */
+        if (traced)
+        {
+            c->gcur = (c->gcur + 1) % rt_ctx::NGSET;
+            L.vis = c->d_vis = c->d_gset[c->gcur][0]; L.g0 = c->d_g0 = c->d_gset[c->gcur][1]; L.g1 = c->d_g1 = c->d_gset[c->gcur][2];
+        }
+        else *reused = true;
         RT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_spec_done, 0));
         c->spec_outstanding = false;
         if (c->spec_gen_valid && use_next_generate(c, L.timed) && c->spec_gen_frame == frame && c->spec_res_epoch == c->res_epoch &&
@@ -1657,9 +1700,12 @@ static int raycast_or_take(rt_ctx* c, Launch& L, bool whole, int frame, bool may
         }
         c->spec_gen_valid = false;
         c->spec_valid = false;
+        if (!traced) return RT_OK; /* the same set, its serial and its shaded bits; the candidates carry its serial (launch_generate) */
         c->has_gbuffer = true;
         ++c->gbuf_serial;
         c->gbuf_epoch = c->spec_epoch; /* == c->epoch (checked above) */
+        c->gbuf_traced_epoch = c->spec_epoch; /* all owned rows, on spec_stream (counted when it was launched) */
+        c->gbuf_spec_ordered = true;
         if (c->gen_taken) c->rec_gserial[c->fY] = c->gbuf_serial; /* the candidates were made from this G-buffer set */
         c->shaded_bits_stale = true;
         if (c->spec_timed[c->gcur]) c->timed_spec_set = c->gcur;
@@ -1667,6 +1713,15 @@ static int raycast_or_take(rt_ctx* c, Launch& L, bool whole, int frame, bool may
     }
     c->spec_valid = false;
     c->spec_gen_valid = false;
+    if (gbuffer_reusable(c))
+    {
+        /* nothing is written: the tail may go on reading the set; a look-ahead that was not taken may still be running on the
+         * history and the spare buffer */
+        const int rc = join_spec(c, L);
+        if (rc != RT_OK) return rc;
+        *reused = true;
+        return RT_OK;
+    }
     if (may_defer)
     {
         /* rt_raycast without its launch: the candidates' kernel of this stage traces the primary rays (use_fused_stage0) */
@@ -1676,6 +1731,7 @@ static int raycast_or_take(rt_ctx* c, Launch& L, bool whole, int frame, bool may
         c->has_gbuffer = true;
         ++c->gbuf_serial;
         c->gbuf_epoch = c->epoch;
+        note_primary_launch(c, L, c->epoch); /* the candidates' launch of this stage, all owned rows (may_defer) */
         c->shaded_bits_stale = true;
         *deferred = true;
         return RT_OK;
@@ -2412,8 +2468,12 @@ static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part,
         if (part != 2 && c->f_clear) rc = clear_rows(c, L);
         mark(1);
         bool deferred = false; /* the primary rays are traced by the candidates' launch */
-        if (part != 2 && rc == RT_OK) rc = raycast_or_take(c, L, whole, frame, part == 0 && whole && use_fused_stage0(c), &deferred);
-        if (part != 2) c->stage0_one_launch = deferred;
+        bool reused = false;   /* r13: by nobody, the current G-buffer set is still the answer */
+        const bool may_defer = part == 0 && whole && use_fused_stage0(c);
+        if (part != 2 && rc == RT_OK) rc = raycast_or_take(c, L, whole, frame, may_defer, &deferred, &reused);
+        /* a reuse frame answers what a tracing frame would under the same tuning: its stage 0 on this stream is the candidates' launch
+         * either way, and the bracket where the raycast launch would be is empty either way */
+        if (part != 2) c->stage0_one_launch = deferred || (reused && !c->gen_taken && may_defer);
         if (part != 2 && rc == RT_OK && row0 == c->row_begin && row1 == c->row_end && !deferred) rc = refresh_shaded_bits(c, L);
         mark(2);
         if (part != 1 && rc == RT_OK && !c->gen_taken)
@@ -2626,6 +2686,26 @@ int rt_stage0_one_launch(rt_ctx* c, int* one_launch)
     RT_CHECK_CTX(c);
     if (!one_launch) return RT_ERR_ARG;
     *one_launch = c->stage0_one_launch ? 1 : 0;
+    return RT_OK;
+}
+
+/* r13. A switch of its own and not an rt_tuning key: tests/golden/tuning_matrix.json pins keys 29 and 30 as unknown, and TUNING has
+ * one row per key, in order. */
+int rt_gbuffer_reuse(rt_ctx* c, int on)
+{
+    RT_CHECK_CTX(c);
+    if (on && (c->row_begin != 0 || c->row_end != c->H))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_gbuffer_reuse: strip contexts trace their primary rays every frame");
+    c->gbuf_reuse = on != 0;
+    /* a look-ahead enqueued under the other setting is not taken: the next frame runs its own stage 0 */
+    c->spec_valid = false; c->spec_gen_valid = false;
+    return RT_OK;
+}
+int rt_primary_launches(rt_ctx* c, uint64_t* n)
+{
+    RT_CHECK_CTX(c);
+    if (!n) return RT_ERR_ARG;
+    *n = c->primary_launches;
     return RT_OK;
 }
 

@@ -226,8 +226,24 @@ int rt_walk_stats_enable(rt_ctx* ctx, int on);
 int rt_walk_stats(rt_ctx* ctx, uint64_t out[16]);
 /* whether stage 0 of the last staged frame (rt_frame) ran as ONE launch — primary ray + candidates + temporal merge, rt_tuning
  * key 25 — on the context's stream. rt_timing then reports that launch as ms[2] and ms[1] is the empty bracket where the
- * raycast launch would have been (bench.py: `kernel_ms.stage0`). A look-ahead stage 0 (key 14) does not count. */
+ * raycast launch would have been (bench.py: `kernel_ms.stage0`). A look-ahead stage 0 (key 14) does not count. A frame that reuses
+ * its G-buffer (rt_gbuffer_reuse) answers what a tracing frame would under the current tuning: its stage 0 on the stream is the
+ * candidates' launch and ms[1] the empty bracket in either form. */
 int rt_stage0_one_launch(rt_ctx* ctx, int* one_launch);
+/* (r13) The primary ray of a pixel has no jitter and no frame number in it, so the G-buffer (RT_BUF_VISIBILITY and the two records
+ * derived from it) is a function of camera, scene and image size. on = 1 (default on whole-frame contexts): stage 0 of a staged frame
+ * (rt_frame, rt_frame_stage*) launches no primary rays while the current G-buffer set was traced over all owned rows, by stage 0 or
+ * rt_raycast, under the current rt_state_epoch, and runs the candidates on that set; the look-ahead stage 0 (key 14) is then the
+ * candidates alone. The first frame after rt_scene_set / rt_scene_update / a camera call / rt_options_set / an upload of
+ * RT_BUF_VISIBILITY traces as before (an uploaded G-buffer is not a traced one). Bit-identical results: the skipped launch would
+ * write the bytes the set holds. Always traced: rt_raycast, strip contexts, frames while rt_walk_stats_enable is on. on = 0: every
+ * frame traces (A/B runs; tools that arm a clock or a permutation on the frame's raycast). on = 1 on a strip context:
+ * RT_ERR_UNSUPPORTED. Not an rt_tuning key: tests/golden/tuning_matrix.json pins keys 29 and 30 as unknown and the table has one row
+ * per key. */
+int rt_gbuffer_reuse(rt_ctx* ctx, int on);
+/* launches so far that traced primary rays over the context's rows: rt_raycast, stage-0 raycasts, the one-launch stage 0 and
+ * look-ahead raycasts (counted when launched, taken or not). How the tests see reuse without timing anything. */
+int rt_primary_launches(rt_ctx* ctx, uint64_t* n);
 /* shaded pixels of each owned storage row (row_end - row_begin counters): the row cost of rt_mg_partition */
 int rt_row_shaded(rt_ctx* ctx, uint32_t* counts);
 /* ALGORITHMIC bytes (reference record sizes) of the spatial_resampling launch

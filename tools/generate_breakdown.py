@@ -23,6 +23,7 @@ for label, kw in (("full", {}), ("ris 16", dict(ris_sample_count=16)), ("ris 1",
     r.set_scene(tris)
     r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
     r.set_options(bench_options(**kw))
+    r.gbuffer_reuse(False)  # `raycast` below is the launch's time, not the empty bracket of a steady frame
     r.timing_enable(True)
     rows = []
     for f in range(1, 41):

@@ -31,6 +31,7 @@ for case in sys.argv[1:] or ["1920x1080:135", "1920x1080:270", "1920x1080:1080",
     r.set_scene(tris)
     r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
     r.set_options(bench_options())
+    r.gbuffer_reuse(False)  # rt_raycast always traces; said here so that a frame added to this loop would too
     ref = None
     line = []
     for name, keys in FORMS:

@@ -24,6 +24,7 @@ r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
 r.set_options(bench_options())
 r.tuning(api.Tune.SPEC, 0)
 r.tuning(api.Tune.TAIL, 0)
+r.gbuffer_reuse(False)  # every frame traces: the clock and the permutation are armed on the frame's raycast / one-launch stage 0
 clock = r.L.rt_exp_wave_clock
 clock.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
 clock.restype = C.c_int

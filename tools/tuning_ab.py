@@ -12,6 +12,8 @@ out = {}
 for W, H in ((1920, 1080), (3840, 2160)):
     r = api.Renderer(W, H, exp=True)  # the A/B forms live in librestir_rt_exp.so
     r.set_scene(tris); r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT); r.set_options(bench_options())
+    if key in (api.Tune.TILE_RAYCAST, api.Tune.WS_PRIMARY, api.Tune.HALF_RAYCAST, api.Tune.FUSE_RAYCAST):
+        r.gbuffer_reuse(False)  # keys of the primary rays: a steady frame traces none, the A/B would compare nothing
     for v in values * 2:
         r.tuning(key, v)
         r.timing_enable(False)

@@ -29,6 +29,7 @@ r.lookat(scenes.BLOCKS_RESTIR_EYE, scenes.BLOCKS_RESTIR_LOOKAT)
 r.set_options(bench_options())
 r.tuning(api.Tune.SPEC, 0)
 r.tuning(api.Tune.TAIL, 0)
+r.gbuffer_reuse(False)  # every frame traces: a steady frame would leave the raycast's clock words empty
 for kv in args:
     k, v = kv.split("=")
     r.tuning(int(k), int(v))
