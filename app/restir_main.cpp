@@ -243,7 +243,8 @@ static std::vector<rt_triangle> load_tris(const std::string& path)
 
 /* ---- --move-lights dx dy dz (--example 10): before frame f >= 2 every emissive triangle moves by (dx, dy, dz) from where it
  * was (one float add per coordinate, as scenes.move_triangles) and rt_scene_update refits the scene over the span from the
- * lowest to the highest emissive index; with --accumulate 1 that frame clears the accumulation (as after a camera move) ---- */
+ * lowest to the highest emissive index; with --accumulate 1 that frame clears the accumulation (as after a camera move). After
+ * the last update the app prints rt_bvh_cost's now / at_build ---- */
 struct LightMove
 {
     bool on = false;
@@ -276,6 +277,14 @@ static double move_lights(rt_ctx* ctx, std::vector<rt_triangle>& tris, const Lig
     const int rc = rt_scene_update(ctx, tris.data() + mv.first, mv.first, mv.count);
     if (rc != RT_OK) die(ctx, "rt_scene_update", rc);
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+/* after the last update: what the refits have cost the tree (rt_bvh_cost: now / at build; rebuilding is the caller's decision) */
+static void print_bvh_cost(rt_ctx* ctx)
+{
+    double now = 0.0, at_build = 0.0;
+    const int rc = rt_bvh_cost(ctx, &now, &at_build);
+    if (rc != RT_OK) die(ctx, "rt_bvh_cost", rc);
+    printf("bvh cost now / at build: %.4f / %.4f = %.3f\n", now, at_build, at_build > 0.0 ? now / at_build : 1.0);
 }
 
 /* ---- --ranks N: one process per GPU over the native strip driver ---- */
@@ -364,6 +373,7 @@ static int rank_main(int rank, int ranks, bool mirror, bool shm, bool equal_stri
         {
             const double ms = move_lights(ctx, moving, mv);
             if (rank == 0) printf("frame %d scene update: %.3f ms (%u triangles)\n", frame, ms, mv.count);
+            if (rank == 0 && frame == frames) print_bvh_cost(ctx);
             clear = opt.accumulate ? 1 : 0;
         }
         rc = rt_mg_frame(mg, frame, clear);
@@ -597,6 +607,7 @@ int main(int argc, char** argv)
         {
             const double ms = move_lights(ctx, triangles, mv);
             printf("frame %d scene update: %.3f ms (%u triangles)\n", frame, ms, mv.count);
+            if (frame == frames) print_bvh_cost(ctx);
             clear = opt.accumulate ? 1 : 0;
         }
         if (orbit && frame >= 2)

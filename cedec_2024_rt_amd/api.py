@@ -42,7 +42,7 @@ INTERNAL_EXPORTS = [
     "rt_side_stream", "rt_copy_parts", "rt_wire_delay", "rt_geometry", "rt_res_region", "rt_lane", "rt_mg_bands",
     "rt_mg_load_error", "rt_mg_hub_create", "rt_mg_hub_destroy", "rt_mg_frame_begin", "rt_mg_frame_step", "rt_mg_reset_stats",
     "rt_mg_selftest_rccl", "rt_visibility_rays_walked", "rt_walk_stats_enable", "rt_walk_stats", "rt_stage0_one_launch",
-    "rt_row_shaded", "rt_spatial_bytes", "rt_trace_closest", "rt_trace_stats", "rt_bvh_config", "rt_bvh_info", "rt_build_ms",
+    "rt_row_shaded", "rt_spatial_bytes", "rt_trace_closest", "rt_trace_stats", "rt_bvh_config", "rt_bvh_info", "rt_bvh_cost", "rt_build_ms",
     "rt_trace_mode", "rt_trace_time", "rt_tuning", "rt_tuning_get", "rt_math_eval", "rt_gbuffer_reuse", "rt_primary_launches",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
@@ -176,6 +176,8 @@ def load_library(exp=False, path=None):
     L.rt_row_shaded.argtypes = [vp, vp]
     L.rt_stage0_one_launch.argtypes = [vp, vp]
     # r13; an older build of the library (RT_LIB_PATH: A/B runs against the parent commit) has neither: it traces every frame
+    if hasattr(L, "rt_bvh_cost"):  # r14; likewise absent from an older build
+        L.rt_bvh_cost.argtypes = [vp, vp, vp]
     if hasattr(L, "rt_gbuffer_reuse"):
         L.rt_gbuffer_reuse.argtypes = [vp, ci]
         L.rt_primary_launches.argtypes = [vp, vp]
@@ -809,6 +811,13 @@ class Renderer:
         a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._ck(self.L.rt_bvh_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(references=a.value, wide_records=b.value, wide_height=c.value)
+
+    def bvh_cost(self):
+        """(now, at_build): rt_bvh_cost, the SAH cost of the 4-wide tree as it stands and as set_scene left it. Their ratio
+        says what refits (update_scene) have cost the tree; rebuilding (set_scene) is the caller's decision."""
+        now, at_build = C.c_double(), C.c_double()
+        self._ck(self.L.rt_bvh_cost(self.h, C.byref(now), C.byref(at_build)))
+        return now.value, at_build.value
 
     def math_eval(self, fn, x):
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -20,47 +20,15 @@
 #include <rocprim/rocprim.hpp>
 
 #include "bvh.h"
+#include "bvh_fragment.h"
 
 namespace rt
 {
 
 /* ------------------------------------------------------------------ 1. early split clipping */
-struct DevPoly
-{
-    int n;
-    float v[12][3];
-};
-RT_DEV void dpoly_bounds(const DevPoly& p, float* lo, float* hi)
-{
-    for (int a = 0; a < 3; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; }
-    for (int i = 0; i < p.n; ++i)
-        for (int a = 0; a < 3; ++a)
-        {
-            lo[a] = fminf(lo[a], p.v[i][a]);
-            hi[a] = fmaxf(hi[a], p.v[i][a]);
-        }
-}
-RT_DEV void dpoly_clip(const DevPoly& p, int a, float s, int sign, DevPoly& o)
-{
-    o.n = 0;
-    for (int i = 0; i < p.n; ++i)
-    {
-        const float* c = p.v[i];
-        const float* d = p.v[(i + 1) % p.n];
-        const bool cin = sign > 0 ? c[a] >= s : c[a] <= s;
-        const bool din = sign > 0 ? d[a] >= s : d[a] <= s;
-        if (cin && o.n < 12) { o.v[o.n][0] = c[0]; o.v[o.n][1] = c[1]; o.v[o.n][2] = c[2]; o.n++; }
-        if (cin != din && o.n < 12)
-        {
-            const float t = (s - c[a]) / (d[a] - c[a]);
-            for (int k = 0; k < 3; ++k) o.v[o.n][k] = c[k] + (d[k] - c[k]) * t;
-            o.v[o.n][a] = s;
-            o.n++;
-        }
-    }
-}
-constexpr int SPLIT_STACK = 20;
-/* EMIT = false: counts[i] = fragments of triangle i; EMIT = true: writes them at offsets[i] */
+/* The clip, the split recursion and the fragment polygons are bvh_fragment.h's (shared with the refit and the CPU tests).
+ * EMIT = false: counts[i] = fragments of triangle i; EMIT = true: writes them at offsets[i] */
+constexpr int SPLIT_STACK = FRAG_SPLIT_STACK;
 template <bool EMIT>
 __global__ void k_split_refs(const float* __restrict__ tris /* 15 floats each */, int n, float L, float pad,
                              const uint32_t* __restrict__ offsets, uint32_t* __restrict__ counts,
@@ -68,57 +36,38 @@ __global__ void k_split_refs(const float* __restrict__ tris /* 15 floats each */
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    DevPoly stack[SPLIT_STACK];
-    int sp = 0;
-    {
-        const float* t = tris + 15 * (size_t)i;
-        stack[0].n = 3;
-        for (int k = 0; k < 3; ++k)
-            for (int a = 0; a < 3; ++a) stack[0].v[k][a] = t[3 * k + a];
-        sp = 1;
-    }
-    uint32_t emitted = 0;
     const uint32_t base = EMIT ? offsets[i] : 0u;
-    while (sp > 0)
-    {
-        const DevPoly q = stack[--sp];
-        float lo[3], hi[3];
-        dpoly_bounds(q, lo, hi);
-        int a = 0;
-        for (int k = 1; k < 3; ++k)
-            if (hi[k] - lo[k] > hi[a] - lo[a]) a = k;
-        const float ext = hi[a] - lo[a];
-        bool split = L > 0.0f && ext > L && emitted + (uint32_t)sp < 4096u && q.n >= 3 && sp + 2 <= SPLIT_STACK;
-        float s = 0.0f;
-        if (split)
-        {
-            /* split plane on the global L-grid so that fragments of neighbours line up */
-            const float mid = 0.5f * (lo[a] + hi[a]);
-            s = L * floorf(mid / L + 0.5f);
-            if (!(s > lo[a] + 0.01f * ext && s < hi[a] - 0.01f * ext)) s = mid;
-            if (!(s > lo[a] && s < hi[a])) split = false;
-        }
-        if (split)
-        {
-            DevPoly l, r;
-            dpoly_clip(q, a, s, -1, l);
-            dpoly_clip(q, a, s, +1, r);
-            if (l.n >= 3 && r.n >= 3)
-            {
-                stack[sp++] = l;
-                stack[sp++] = r;
-                continue;
-            }
-        }
+    const uint32_t emitted = frag_split<false>(tris + 15 * (size_t)i, L, [&](uint32_t j, const FragPoly<false>&, const float* lo, const float* hi) {
         if (EMIT)
         {
-            float* b = boxes + 6 * (size_t)(base + emitted);
+            float* b = boxes + 6 * (size_t)(base + j);
             for (int k = 0; k < 3; ++k) { b[k] = lo[k] - pad; b[3 + k] = hi[k] + pad; }
-            ref_tri[base + emitted] = i;
+            ref_tri[base + j] = i;
         }
-        ++emitted;
-    }
+    });
     if (!EMIT) counts[i] = emitted;
+}
+
+/* Fragment identity for the refit (bvh_refit.h). leaf_frag[2 * node + side] = 1 + the fragment's number within its triangle
+ * for a leaf child whose triangle was split, 0 otherwise; k_collapse_level copies it into word 10 of the leaf's record,
+ * which no walk uses. */
+__global__ void k_leaf_frags(int n, const uint32_t* __restrict__ ids, const int* __restrict__ ref_tri, const uint32_t* __restrict__ offsets,
+                             const uint32_t* __restrict__ counts, const int2* __restrict__ children, uint32_t* __restrict__ leaf_frag)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n - 1) return;
+    const int2 ch = children[i];
+    uint32_t f[2] = {0u, 0u};
+    for (int s = 0; s < 2; ++s)
+    {
+        const int c = s ? ch.y : ch.x;
+        if (c >= 0) continue;
+        const uint32_t r = ids[~c];
+        const int t = ref_tri[r];
+        if (counts[t] > 1u) f[s] = r - offsets[t] + 1u;
+    }
+    leaf_frag[2 * (size_t)i] = f[0];
+    leaf_frag[2 * (size_t)i + 1] = f[1];
 }
 
 /* largest box extent per triangle (for the median that sets the fragment length) + scene bounds */
@@ -813,11 +762,14 @@ struct CollapseState
 struct DevChild
 {
     int bin;
+    uint32_t frag; /* leaf: word 10 of its record (k_leaf_frags) */
     float lo[3], hi[3];
 };
-RT_DEV void dev_bin_children(const BvhNode& n, DevChild out[2])
+RT_DEV void dev_bin_children(const BvhNode& n, const uint32_t* __restrict__ leaf_frag, int node, DevChild out[2])
 {
     out[0].bin = n.d.x; out[1].bin = n.d.y;
+    out[0].frag = (leaf_frag && n.d.x < 0) ? leaf_frag[2 * (size_t)node] : 0u;
+    out[1].frag = (leaf_frag && n.d.y < 0) ? leaf_frag[2 * (size_t)node + 1] : 0u;
     out[0].lo[0] = n.a.x; out[0].lo[1] = n.a.y; out[0].lo[2] = n.a.z;
     out[0].hi[0] = n.b.x; out[0].hi[1] = n.b.y; out[0].hi[2] = n.b.z;
     out[1].lo[0] = n.a.w; out[1].lo[1] = n.b.w; out[1].lo[2] = n.c.w;
@@ -837,7 +789,8 @@ __global__ void k_collapse_init(CollapseState* st, CollapseItem* q0)
  * (ascending box area) and conservative quantisation as bvh_build_host.h::collapse_wide. */
 __global__ void k_collapse_level(const BvhNode* __restrict__ bin, const float* __restrict__ tris /* 15 floats */, int level,
                                  CollapseState* __restrict__ st, const CollapseItem* __restrict__ in, CollapseItem* __restrict__ out,
-                                 uint32_t* __restrict__ recs /* 12 words per record, 4 * WIDE_STRIDE apart */)
+                                 uint32_t* __restrict__ recs /* 12 words per record, 4 * WIDE_STRIDE apart */,
+                                 const uint32_t* __restrict__ leaf_frag /* k_leaf_frags, or nullptr */)
 {
     const unsigned int t = blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned int n_in = st->count[level & 1];
@@ -846,7 +799,7 @@ __global__ void k_collapse_level(const BvhNode* __restrict__ bin, const float* _
     const CollapseItem wk = in[t];
     DevChild ch[4];
     int n = 2;
-    dev_bin_children(bin[wk.bin], ch);
+    dev_bin_children(bin[wk.bin], leaf_frag, wk.bin, ch);
     while (n < 4)
     {
         int pick = -1;
@@ -859,7 +812,7 @@ __global__ void k_collapse_level(const BvhNode* __restrict__ bin, const float* _
             }
         if (pick < 0) break;
         DevChild two[2];
-        dev_bin_children(bin[ch[pick].bin], two);
+        dev_bin_children(bin[ch[pick].bin], leaf_frag, ch[pick].bin, two);
         ch[pick] = two[0];
         ch[n++] = two[1];
     }
@@ -902,7 +855,8 @@ __global__ void k_collapse_level(const BvhNode* __restrict__ bin, const float* _
             uint32_t* Lr = recs + 4 * WIDE_STRIDE * (size_t)(base + (unsigned int)k);
             for (int i = 0; i < 9; ++i) Lr[i] = __float_as_uint(tv[i]);
             Lr[9] = (uint32_t)ti;
-            Lr[10] = Lr[11] = 0u;
+            Lr[10] = ch[k].frag;
+            Lr[11] = 0u;
         }
     }
     uint32_t* R = recs + 4 * WIDE_STRIDE * (size_t)wk.out;

@@ -141,6 +141,16 @@ struct rt_ctx
     float* d_refit_box = nullptr;
     unsigned int* d_refit_bounds = nullptr;
     std::vector<uint32_t> refit_off;
+    /* fragments of pre-split triangles (bvh_refit.h): frag_pending = the device build left fragment numbers in the leaves and
+     * the table is still to be made (at the first update, from the build's triangles, fragment length and pad); then the
+     * vertex-major (u, v) table and the vertex counts of n_frags fragments. cost_at_build: rt_bvh_cost of the tree before
+     * its first refit (< 0: not taken yet) */
+    bool frag_pending = false;
+    float frag_L = 0.0f, frag_pad = 0.0f;
+    float* d_frag_uv = nullptr;
+    uint8_t* d_frag_n = nullptr;
+    uint32_t n_frags = 0;
+    double cost_at_build = -1.0;
     bool bin_stale = false; /* the binary tree (d_nodes, trace mode 1 of the experiments library) predates an update */
 
     float4 *d_vis = nullptr, *d_g0 = nullptr, *d_g1 = nullptr, *d_accum = nullptr;
@@ -447,6 +457,9 @@ static void free_scene(rt_ctx* c)
     hipFree(c->d_tris); hipFree(c->d_tv); hipFree(c->d_nodes); hipFree(c->d_trimat); hipFree(c->d_lights); hipFree(c->d_light_ke); hipFree(c->d_wide);
     hipFree(c->d_light_ids); hipFree(c->d_refit_list); hipFree(c->d_refit_box); hipFree(c->d_refit_bounds);
     c->d_light_ids = nullptr; c->d_refit_list = nullptr; c->d_refit_box = nullptr; c->d_refit_bounds = nullptr;
+    if (c->d_frag_uv) hipFree(c->d_frag_uv); /* only a scene that was updated has them: a static scene's rt_scene_set makes no call for them */
+    if (c->d_frag_n) hipFree(c->d_frag_n);
+    c->d_frag_uv = nullptr; c->d_frag_n = nullptr; c->n_frags = 0; c->frag_pending = false; c->cost_at_build = -1.0;
     c->h_lights.clear(); c->refit_off.clear();
     c->bin_stale = false;
     c->d_light_ke = nullptr;
@@ -850,6 +863,15 @@ static int build_bvh_device(rt_ctx* c, int n_tris)
     BD_HIP(hipMalloc(&c->d_nodes, (size_t)(n - 1) * sizeof(BvhNode)));
     k_bvh_emit<<<grid, 256, 0, st>>>(n, d_leaf_ids, d_ref_tri, d_boxes, d_children, d_parent, d_node_boxes, c->d_nodes);
     BD_HIP(hipGetLastError());
+    /* which fragment of its triangle a leaf holds, for the refit (only where something was split). The 2 (n - 1) words take
+     * the place of the binary nodes' boxes (6 n floats), which k_bvh_emit was the last to read: no allocation for it */
+    uint32_t* d_leaf_frag = nullptr;
+    if (n > n_tris)
+    {
+        d_leaf_frag = (uint32_t*)d_node_boxes;
+        k_leaf_frags<<<grid, 256, 0, st>>>(n, d_leaf_ids, d_ref_tri, d_off, d_cnt, d_children, d_leaf_frag);
+        BD_HIP(hipGetLastError());
+    }
     /* 5. wide collapse, level by level */
     const size_t rec_cap = (size_t)n * 2 + 8;
     BD_HIP(hipMalloc(&c->d_wide, rec_cap * 16 * WIDE_STRIDE));
@@ -860,7 +882,7 @@ static int build_bvh_device(rt_ctx* c, int n_tris)
     const int max_levels = (WIDE_LDS_STACK + WIDE_OVF_STACK - 1) / 3 + 1;
     for (int level = 0; level <= max_levels; ++level)
     {
-        k_collapse_level<<<grid, 256, 0, st>>>(c->d_nodes, c->d_tris, level, d_cs, d_q[level & 1], d_q[(level + 1) & 1], (uint32_t*)c->d_wide);
+        k_collapse_level<<<grid, 256, 0, st>>>(c->d_nodes, c->d_tris, level, d_cs, d_q[level & 1], d_q[(level + 1) & 1], (uint32_t*)c->d_wide, d_leaf_frag);
         k_collapse_swap<<<1, 1, 0, st>>>(level, d_cs);
     }
     BD_HIP(hipGetLastError());
@@ -888,6 +910,9 @@ static int build_bvh_device(rt_ctx* c, int n_tris)
     c->bvh_height = bh;
     c->n_wide = (int)cs.n_rec;
     c->wide_height = (int)cs.height;
+    c->frag_pending = d_leaf_frag != nullptr;
+    c->frag_L = L;
+    c->frag_pad = pad;
     cleanup();
 #undef BD_FAIL
 #undef BD_HIP
@@ -1124,7 +1149,7 @@ static int refit_topology(rt_ctx* c)
     c->d_refit_list = nullptr; c->d_refit_box = nullptr; c->d_refit_bounds = nullptr;
     RT_HIP(c, hipMalloc(&c->d_refit_list, (size_t)cap * 4));
     RT_HIP(c, hipMalloc(&c->d_refit_box, (size_t)cap * 24));
-    RT_HIP(c, hipMalloc(&c->d_refit_bounds, 24));
+    RT_HIP(c, hipMalloc(&c->d_refit_bounds, 48)); /* 6 bound keys; from byte 32: the two doubles of k_bvh_cost */
     uint32_t* d_off = nullptr;
     RT_HIP(c, hipMalloc(&d_off, (size_t)(levels + 2) * 4));
     std::vector<uint32_t> off((size_t)levels + 2, 0u);
@@ -1160,6 +1185,125 @@ static int refit_topology(rt_ctx* c)
     return RT_OK;
 }
 
+/* rt_bvh_cost of the tree as it stands: k_bvh_cost over the level lists, its two doubles behind the refit's bounds.
+ * bvh_cost_launch enqueues, bvh_cost_read reads them back once the stream has been synchronised. */
+static double* bvh_cost_words(rt_ctx* c) { return (double*)(c->d_refit_bounds + 8); }
+static int bvh_cost_launch(rt_ctx* c, double h[2])
+{
+    hipStream_t st = c->stream;
+    const uint32_t n_inner = c->refit_off.back();
+    RT_HIP(c, hipMemsetAsync(bvh_cost_words(c), 0, 16, st));
+    k_bvh_cost<<<(n_inner + 255) / 256, 256, 0, st>>>(c->d_refit_list, n_inner, (const uint32_t*)c->d_wide, bvh_cost_words(c));
+    RT_HIP(c, hipGetLastError());
+    RT_HIP(c, hipMemcpyAsync(h, bvh_cost_words(c), 16, hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+static double bvh_cost_read(const double h[2]) { return h[1] > 0.0 ? h[0] / h[1] : 0.0; }
+
+int rt_bvh_cost(rt_ctx* c, double* now, double* at_build)
+{
+    RT_CHECK_CTX(c);
+    if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "rt_bvh_cost before rt_scene_set");
+    RT_HIP(c, hipSetDevice(c->device));
+    double cost = 0.0;
+    if (c->d_wide && c->n_wide >= 1) /* else: an empty scene */
+    {
+        if (c->refit_off.empty()) { const int rc = refit_topology(c); if (rc != RT_OK) return rc; }
+        double h[2] = {0.0, 0.0};
+        { const int rc = bvh_cost_launch(c, h); if (rc != RT_OK) return rc; }
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+        cost = bvh_cost_read(h);
+    }
+    if (now) *now = cost;
+    if (at_build) *at_build = c->cost_at_build >= 0.0 ? c->cost_at_build : cost; /* no update yet: the tree is the build's */
+    return RT_OK;
+}
+
+/* A scene's first update, before the refit writes a record and while d_tris still holds the triangles the build split: the
+ * cost of the tree as built, and the fragment table of bvh_refit.h. One host round trip (the cost and the table's size);
+ * the table's kernels run ahead of the refit on the stream. The table is an optimisation: if it cannot be made (out of
+ * memory, counts that do not match) the update goes on and this scene refits with whole-triangle boxes, which is exact.
+ * frag_pending is dropped first: the leaves' words are rewritten at most once. */
+static int refit_first_update(rt_ctx* c)
+{
+    hipStream_t st = c->stream;
+    double h[2] = {0.0, 0.0};
+    { const int rc = bvh_cost_launch(c, h); if (rc != RT_OK) return rc; }
+    const bool want_table = c->frag_pending;
+    c->frag_pending = false;
+    const int n_tris = c->n_tris;
+    const uint32_t n_inner = c->refit_off.back();
+    const int gt = (n_tris + 255) / 256;
+    const unsigned gi = (n_inner + 255) / 256;
+    /* one scratch allocation: fragments per triangle, those of split triangles and their offsets; fragment leaves per inner
+     * record and their offsets; the scans' workspace */
+    size_t sb0 = 0, sb1 = 0;
+    uint32_t* d_tmp = nullptr;
+    uint32_t *d_cnt = nullptr, *d_fc = nullptr, *d_foff = nullptr, *d_per = nullptr, *d_sbase = nullptr;
+    void* d_scan = nullptr;
+    bool table = want_table;
+    if (table)
+    {
+        table = rocprim::exclusive_scan(nullptr, sb0, d_fc, d_foff, 0u, (size_t)n_tris, rocprim::plus<uint32_t>(), st) == hipSuccess &&
+                rocprim::exclusive_scan(nullptr, sb1, d_per, d_sbase, 0u, (size_t)n_inner, rocprim::plus<uint32_t>(), st) == hipSuccess;
+        const size_t words = 3 * (size_t)n_tris + 2 * (size_t)n_inner + 64;
+        table = table && hipMalloc(&d_tmp, words * 4 + std::max(sb0, sb1)) == hipSuccess;
+        if (!table) (void)hipGetLastError();
+    }
+    uint32_t tail[4] = {0, 0, 0, 0};
+    if (table)
+    {
+        d_cnt = d_tmp; d_fc = d_cnt + n_tris; d_foff = d_fc + n_tris; d_per = d_foff + n_tris; d_sbase = d_per + n_inner;
+        d_scan = d_tmp + (((3 * (size_t)n_tris + 2 * (size_t)n_inner) + 63) & ~(size_t)63); /* 256-byte aligned */
+        /* fragments per split triangle, as the build counted them (same kernel, same triangles, same L) */
+        k_split_refs<false><<<gt, 256, 0, st>>>(c->d_tris, n_tris, c->frag_L, c->frag_pad, nullptr, d_cnt, nullptr, nullptr);
+        k_frag_counts<<<gt, 256, 0, st>>>(n_tris, d_cnt, d_fc);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = rocprim::exclusive_scan(d_scan, sb0, d_fc, d_foff, 0u, (size_t)n_tris, rocprim::plus<uint32_t>(), st);
+        /* fragment leaves per inner record, in the order the refit visits them */
+        if (e == hipSuccess) { k_frag_leaves<<<gi, 256, 0, st>>>(c->d_refit_list, n_inner, (const uint32_t*)c->d_wide, d_per); e = hipGetLastError(); }
+        if (e == hipSuccess) e = rocprim::exclusive_scan(d_scan, sb1, d_per, d_sbase, 0u, (size_t)n_inner, rocprim::plus<uint32_t>(), st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&tail[0], d_foff + n_tris - 1, 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&tail[1], d_fc + n_tris - 1, 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&tail[2], d_sbase + n_inner - 1, 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&tail[3], d_per + n_inner - 1, 4, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) { hipFree(d_tmp); RT_FAIL(c, RT_ERR_HIP, "fragment table: %s", hipGetErrorString(e)); }
+    }
+    { const hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) { hipFree(d_tmp); RT_FAIL(c, RT_ERR_HIP, "first update: %s", hipGetErrorString(e)); } }
+    c->cost_at_build = bvh_cost_read(h);
+    const uint32_t n_frags = tail[0] + tail[1];
+    /* every fragment of a split triangle has its leaf, or the records are not what this build left: no table then */
+    table = table && n_frags != 0 && tail[2] + tail[3] == n_frags;
+    uint32_t* d_slot_of = nullptr;
+    if (table)
+    {
+        table = hipMalloc(&d_slot_of, (size_t)n_frags * 4) == hipSuccess && hipMalloc(&c->d_frag_uv, (size_t)n_frags * FRAG_MAX_VERTS * 8) == hipSuccess &&
+                hipMalloc(&c->d_frag_n, (size_t)n_frags) == hipSuccess;
+        if (!table) (void)hipGetLastError();
+    }
+    if (table)
+    {
+        hipError_t e = hipMemsetAsync(d_slot_of, 0xff, (size_t)n_frags * 4, st);
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_frag_n, 0, (size_t)n_frags, st); /* a slot nobody fills: k_refit_level falls back */
+        if (e == hipSuccess)
+        {
+            k_frag_assign<<<gi, 256, 0, st>>>(c->d_refit_list, n_inner, (uint32_t*)c->d_wide, d_sbase, d_cnt, d_foff, n_frags, n_tris, d_slot_of);
+            k_frag_emit<<<gt, 256, 0, st>>>(c->d_tris, n_tris, c->frag_L, d_cnt, d_foff, d_slot_of, n_frags, c->d_frag_uv, c->d_frag_n);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) { hipFree(d_tmp); hipFree(d_slot_of); RT_FAIL(c, RT_ERR_HIP, "fragment table: %s", hipGetErrorString(e)); }
+        c->n_frags = n_frags;
+    }
+    else
+    {
+        hipFree(c->d_frag_uv); hipFree(c->d_frag_n);
+        c->d_frag_uv = nullptr; c->d_frag_n = nullptr; c->n_frags = 0;
+    }
+    hipFree(d_tmp); /* waits for the kernels above */
+    hipFree(d_slot_of);
+    return RT_OK;
+}
+
 int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uint32_t count)
 {
     RT_CHECK_CTX(c);
@@ -1192,6 +1336,7 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     }
     if (lights.size() > ((size_t)1 << 26)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "more than 2^26 emissive triangles (the light table is addressed by 32-bit byte offsets)");
     if (c->refit_off.empty()) { const int rc = refit_topology(c); if (rc != RT_OK) return rc; }
+    if (c->cost_at_build < 0.0) { const int rc = refit_first_update(c); if (rc != RT_OK) return rc; }
     /* per-triangle arrays of the span */
     RT_HIP(c, hipMemcpyAsync(c->d_tris + 15 * (size_t)first, triangles, (size_t)count * 60, hipMemcpyHostToDevice, st));
     const int gs = (int)((count + 255) / 256);
@@ -1223,7 +1368,8 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     for (int level = (int)c->refit_off.size() - 2; level >= 0; --level)
     {
         const uint32_t b = c->refit_off[(size_t)level], m = c->refit_off[(size_t)level + 1] - b;
-        k_refit_level<<<(m + 255) / 256, 256, 0, st>>>(c->d_refit_list + b, m, c->d_tris, c->d_refit_bounds, c->d_refit_box, (uint32_t*)c->d_wide);
+        k_refit_level<<<(m + 255) / 256, 256, 0, st>>>(c->d_refit_list + b, m, c->d_tris, c->d_refit_bounds, c->d_refit_box, (uint32_t*)c->d_wide,
+                                                        c->n_frags ? c->d_frag_uv : nullptr, c->d_frag_n, c->n_frags);
     }
     RT_HIP(c, hipGetLastError());
     RT_HIP(c, hipStreamSynchronize(st)); /* the caller's triangles and the light list are host memory */

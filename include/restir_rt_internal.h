@@ -31,7 +31,11 @@ int rt_path_trace_rays(rt_ctx* ctx, uint64_t* rays); /* raytrace() calls of the 
 /* ---- scene update: the counterpart of HIPRT's hiprtBuildGeometry with hiprtBuildOperationUpdate (a refit) ---- */
 /* Replace triangles [first, first + count) of the current scene (same total count, same index order).
  * Afterwards every result equals what rt_scene_set on the full new array would give. The tree keeps its topology
- * (rt_bvh_info does not change) and gets new boxes (a refit on the device); the per-triangle tables, the light table
+ * (rt_bvh_info does not change) and gets new boxes (a refit on the device): a triangle's leaf gets the triangle's box, and
+ * each box fragment the build cut out of a large triangle gets the box of its own piece of the moved triangle (the pieces
+ * are kept in barycentric coordinates, so they follow any deformation and do not drift over repeated updates). What a
+ * refit cannot repair is topology: geometry thrown far from where it was built leaves large inner boxes, rt_bvh_cost says
+ * how large, and rebuilding with rt_scene_set is the caller's decision. The per-triangle tables, the light table
  * and rt_scene_info's light count follow the new triangles. Any frame enqueued after the call sees the new scene: the
  * state epoch changes and the speculative next-frame work is dropped; accumulation is left alone (pass clear_first).
  * Synchronises the context's streams as rt_scene_set does. No scene: RT_ERR_STATE; a span beyond the scene or a NULL
@@ -262,6 +266,11 @@ int rt_trace_stats(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t* stats);
 int rt_bvh_config(rt_ctx* ctx, float split_factor);
 /* wide_height: levels of the 4-wide tree the kernels walk; a walk holds at most 3 stack entries per level */
 int rt_bvh_info(rt_ctx* ctx, uint32_t* n_references, uint32_t* n_wide_records, uint32_t* wide_height);
+/* SAH cost of the 4-wide tree as the walks see it: over all inner records and their occupied child slots,
+ * half-area(child box decoded as the walk decodes it, lo + q * scale) / half-area(root box), summed in float64.
+ * now: the tree as it stands; at_build: as rt_scene_set left it (equal to now until the first rt_scene_update).
+ * Synchronises. No scene: RT_ERR_STATE; either pointer may be NULL. */
+int rt_bvh_cost(rt_ctx* ctx, double* now, double* at_build);
 int rt_build_ms(rt_ctx* ctx, float* ms); /* wall time of the last rt_scene_set (upload + tables + BVH build), synchronised */
 /* which traversal rt_trace_closest / rt_trace_stats exercise. THE NUMBERS ARE FROZEN: tools, tests and every measurement log use
  * them. [exp] modes are A/B forms of librestir_rt_exp.so: the product library answers RT_ERR_UNSUPPORTED for them. Modes 4 .. 6

@@ -1,13 +1,14 @@
 """GPU. Cost of rt_scene_update (the refit of csrc/bvh_refit.h) on the blocks_restir stand-in at 1920x1080, bench options.
 
-Records, in profiles/r08_scene_update.json (--out-dir: elsewhere):
+Records, in profiles/r14_scene_update.json (--out-dir / --out-name: elsewhere; r08's run is profiles/r08_scene_update.json):
   * rt_scene_set: wall ms (rt_build_ms) of the first and of repeated calls;
   * rt_scene_update, each call synchronised (the call itself waits): the whole array, and the span from the lowest to the
     highest emissive index with every light moved (median / min / max over --reps calls; the first call of a scene also
     lists the tree's levels, so it is reported apart);
   * frame ms (host clock around rt_sync, --frames back-to-back rt_frames after a warm-up) right after a rebuild, after 60
     light-moving refits, and after one 4096-triangle span was moved by three scene extents: what the refitted tree costs
-    the walks (reported, not gated);
+    the walks (reported, not gated); beside each of the two refitted states rt_bvh_cost's now / at_build, the figure a caller
+    has for deciding on a rebuild, and the frame-time ratio to the rebuild of the same scene;
   * --rocprof: the refit kernels' device time from a SEPARATE child process under `rocprofv3 --kernel-trace --stats`
     (nothing else traced): --reps light-span updates.
 
@@ -32,7 +33,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 W, H = 1920, 1080
-REFIT_KERNELS = ("k_refit_level", "k_refit_topo", "k_refit_topo_next", "k_refit_bounds", "k_light_table", "k_trimat", "k_bvh_tv")
+REFIT_KERNELS = ("k_refit_level", "k_bvh_cost", "k_frag_", "k_refit_topo", "k_refit_topo_next", "k_refit_bounds", "k_light_table", "k_trimat", "k_bvh_tv")
 
 
 def setup():
@@ -72,6 +73,12 @@ def frame_ms(r, frames, start):
     return (time.perf_counter() - t0) * 1e3 / frames
 
 
+def cost(r):
+    """rt_bvh_cost after refits: what the tree costs now, what it cost as built, and the ratio a caller acts on"""
+    now, at_build = r.bvh_cost()
+    return {"now": round(now, 4), "at_build": round(at_build, 4), "ratio": round(now / at_build, 4)}
+
+
 def measure(reps, frames):
     from cedec_2024_rt_amd import scenes
 
@@ -100,8 +107,11 @@ def measure(reps, frames):
         light.append(timed_update(r, cur[lo:hi], lo))
     out["update_light_span"] = dict(stats(light), calls=len(light), triangles=hi - lo, bytes=(hi - lo) * 60)
     out["frame_ms_after_60_light_refits"] = round(frame_ms(r, frames, 1000), 4)
+    out["bvh_cost_after_60_light_refits"] = cost(r)
     r.set_scene(cur)
     out["frame_ms_after_rebuild_of_the_same_scene"] = round(frame_ms(r, frames, 2000), 4)
+    out["bvh_cost_after_rebuild_of_the_same_scene"] = cost(r)
+    out["frame_ratio_60_light_refits_to_rebuild"] = round(out["frame_ms_after_60_light_refits"] / out["frame_ms_after_rebuild_of_the_same_scene"], 3)
     v = cur["v"].reshape(-1, 3)
     ext = float((v.max(0) - v.min(0)).max())
     a = len(cur) // 2
@@ -110,8 +120,11 @@ def measure(reps, frames):
     far = scenes.move_triangles(cur, blk, (3.0 * ext, 0.0, 0.0))
     r.update_scene(far[a:a + 4096], a)
     out["frame_ms_after_far_block_refit"] = round(frame_ms(r, frames, 3000), 4)
+    out["bvh_cost_after_far_block_refit"] = cost(r)
     r.set_scene(far)
     out["frame_ms_after_far_block_rebuild"] = round(frame_ms(r, frames, 4000), 4)
+    out["bvh_cost_after_far_block_rebuild"] = cost(r)
+    out["frame_ratio_far_block_refit_to_rebuild"] = round(out["frame_ms_after_far_block_refit"] / out["frame_ms_after_far_block_rebuild"], 3)
     out["far_block"] = {"first": a, "count": 4096, "offset_x": round(3.0 * ext, 3)}
     r.close()
     return out
@@ -154,6 +167,7 @@ def main():
     ap.add_argument("--frames", type=int, default=30)
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--out-name", default="r14_scene_update.json")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
@@ -163,7 +177,7 @@ def main():
     if a.rocprof:
         res["refit_kernels"] = rocprof(a.reps)
     os.makedirs(a.out_dir, exist_ok=True)
-    json.dump(res, open(os.path.join(a.out_dir, "r08_scene_update.json"), "w"), indent=1)
+    json.dump(res, open(os.path.join(a.out_dir, a.out_name), "w"), indent=1)
     print(json.dumps({k: v for k, v in res.items() if k not in ("what",)}, indent=1)[:6000])
 
 
