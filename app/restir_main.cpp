@@ -10,7 +10,7 @@
  *              [--shadowed 0|1] [--visreuse 0|1] [--accumulate 0|1] [--by-kernel]
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
- *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy]
+ *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
  * image rows (cedec_2024_rt_amd/csrc/host_path.h: brute-force closest hit, 64 ambient-occlusion rays per pixel,
@@ -20,6 +20,8 @@
  * --denoise N (--example 10, 7, 8, 9; one GPU): after every frame rt_denoise with N a-trous iterations (0..8) and the default
  * parameters; --ppm / --png / --rgba then write its tone-mapped image and --pfm its HDR image (RT_BUF_DENOISED).
  * --denoise-temporal (with --denoise N): rt_denoise_temporal (default alphas) in place of rt_denoise, one call per frame.
+ * --unbiased (--example 10, one GPU): rt_spatial_unbiased, the spatial passes normalise by 1/Z; not with
+ * --shadowed 1.
  * --orbit dx dy (one GPU): before every frame from the second on, rt_camera_orbit(dx, dy) (a left-button drag); with
  * --accumulate 1 that frame starts a new accumulation, as the example clears on a camera update.
  * --move-lights dx dy dz (--example 10, also with --ranks): before every frame from the second on, the emissive triangles move
@@ -434,7 +436,7 @@ int main(int argc, char** argv)
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
-    bool denoise_temporal = false, orbit = false;
+    bool denoise_temporal = false, orbit = false, unbiased = false;
     float orbit_d[2] = {0.0f, 0.0f};
     LightMove mv;
     rt_options opt;
@@ -479,6 +481,7 @@ int main(int argc, char** argv)
         else if (a == "--threads") threads = atoi(argv[++i]);
         else if (a == "--denoise") denoise = atoi(argv[++i]);
         else if (a == "--denoise-temporal") denoise_temporal = true;
+        else if (a == "--unbiased") unbiased = true;
         else if (a == "--orbit") { orbit_d[0] = f(1); orbit_d[1] = f(2); i += 2; orbit = true; }
         else if (a == "--move-lights") { mv.d[0] = f(1); mv.d[1] = f(2); mv.d[2] = f(3); i += 3; mv.on = true; }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -487,6 +490,7 @@ int main(int argc, char** argv)
     if (denoise >= 0 && ranks > 1) { fprintf(stderr, "--denoise runs on one GPU (whole-frame contexts), not with --ranks\n"); return 2; }
     if (denoise > 8) { fprintf(stderr, "--denoise: 0..8 iterations\n"); return 2; }
     if (denoise_temporal && denoise < 0) { fprintf(stderr, "--denoise-temporal needs --denoise N\n"); return 2; }
+    if (unbiased && (ranks > 1 || example != 10)) { fprintf(stderr, "--unbiased applies to one GPU and --example 10\n"); return 2; }
     if (orbit && (ranks > 1 || example == 4 || example == 6)) { fprintf(stderr, "--orbit applies to one GPU and --example 10, 7, 8 and 9\n"); return 2; }
     std::vector<rt_triangle> triangles = !obj.empty() ? load_obj(obj) : load_tris(tris_path);
     if (triangles.empty()) { fprintf(stderr, "no triangles (use --obj or --tris)\n"); return 2; }
@@ -597,6 +601,7 @@ int main(int argc, char** argv)
     printf("triangles: %u\nlights: %u\nbvh height: %u\n", nt, nl, bh); /* cf. 10_restir_di.cpp:206 */
     CK(rt_camera_lookat(ctx, eye, lookat, up, 3.14159265358979323846f / 4.0f)); /* :242-251 */
     CK(rt_options_set(ctx, &opt));
+    if (unbiased) CK(rt_spatial_unbiased(ctx, 1));
     CK(rt_timing_enable(ctx, 1));
     CK(rt_clear(ctx)); /* :222-226 */
 

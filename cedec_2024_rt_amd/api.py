@@ -44,6 +44,7 @@ INTERNAL_EXPORTS = [
     "rt_mg_selftest_rccl", "rt_visibility_rays_walked", "rt_walk_stats_enable", "rt_walk_stats", "rt_stage0_one_launch",
     "rt_row_shaded", "rt_spatial_bytes", "rt_trace_closest", "rt_trace_stats", "rt_bvh_config", "rt_bvh_info", "rt_bvh_cost", "rt_build_ms",
     "rt_trace_mode", "rt_trace_time", "rt_tuning", "rt_tuning_get", "rt_math_eval", "rt_gbuffer_reuse", "rt_primary_launches",
+    "rt_spatial_unbiased", "rt_spatial_unbiased_get",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -181,6 +182,9 @@ def load_library(exp=False, path=None):
     if hasattr(L, "rt_gbuffer_reuse"):
         L.rt_gbuffer_reuse.argtypes = [vp, ci]
         L.rt_primary_launches.argtypes = [vp, vp]
+    if hasattr(L, "rt_spatial_unbiased"):  # r15; likewise (Renderer.spatial_unbiased raises on such a build)
+        L.rt_spatial_unbiased.argtypes = [vp, ci]
+        L.rt_spatial_unbiased_get.argtypes = [vp, vp]
     L.rt_visibility_rays_walked.argtypes = [vp, vp]
     L.rt_state_epoch.argtypes = [vp, vp]
     L.rt_get_stream.argtypes = [vp, vp]
@@ -694,7 +698,10 @@ class Renderer:
         self._ck(self.L.rt_walk_stats_enable(self.h, int(bool(on))))
 
     def walk_stats(self):
-        """per kernel: reference rays / walked through the BVH / settled by the self-occlusion test / not evaluated"""
+        """per kernel: reference rays / walked through the BVH / settled by the self-occlusion test / not evaluated; the last three
+        sum to the first. While spatial_unbiased is on, the spatial slot counts the pass's own rays instead: 0 reference rays (the
+        reference's unshadowed pass has none), the neighbours' and own rays walked, those the origin's triangle settled, and as
+        not_evaluated the own rays an earlier kernel of the frame had answered."""
         a = np.zeros(16, dtype=np.uint64)
         self._ck(self.L.rt_walk_stats(self.h, _p(a)))
         return {k: dict(reference_rays=int(a[4 * i]), walked=int(a[4 * i + 1]), self_test=int(a[4 * i + 2]), not_evaluated=int(a[4 * i + 3]))
@@ -732,6 +739,18 @@ class Renderer:
                 raise RtError("this build of librestir_rt has no rt_gbuffer_reuse: every frame traces its primary rays")
             return
         self._ck(self.L.rt_gbuffer_reuse(self.h, int(bool(on))))
+
+    def spatial_unbiased(self, on=None):
+        """rt_spatial_unbiased: the spatial passes normalise by 1/Z (only the contributors that could have produced the selected
+        sample count) instead of the reference's 1/M. Default off. on=None queries; returns the state. Whole-frame contexts,
+        unshadowed target function, at most 5 neighbours per pass."""
+        if not hasattr(self.L, "rt_spatial_unbiased"):  # an older build through RT_LIB_PATH: the mode is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_spatial_unbiased")
+        if on is not None:
+            self._ck(self.L.rt_spatial_unbiased(self.h, int(bool(on))))
+        v = C.c_int()
+        self._ck(self.L.rt_spatial_unbiased_get(self.h, C.byref(v)))
+        return bool(v.value)
 
     def primary_launches(self):
         """launches so far that traced primary rays over the context's rows (rt_raycast, stage-0 raycasts, the one-launch stage 0,

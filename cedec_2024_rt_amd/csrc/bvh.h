@@ -1383,17 +1383,19 @@ RT_DEV bool check_visibility_wide(const WideView& bvh, uint32_t* __restrict__ ld
  * soon as its current one is settled (refill pass, batched like the leaf pass: when at least
  * RT_BATCH_REFILL lanes wait or nobody walks), so the lanes of a wavefront stay busy for the SUM of
  * their ray lengths instead of 6 times the longest (used by the shadowed-target passes, where one
- * pixel needs up to 6 independent rays). Per-ray steps and results are those of trace_wide<true>. */
+ * pixel needs up to 6 independent rays). Per-ray steps and results are those of trace_wide<true>.
+ * The walk itself takes a ray source: next_ray.origin() before the loop and next_ray(k, ro, rd), which the refill pass
+ * calls for ray k. RaysFromPoint (occluded_batch_*) sets the direction tgt[k] - p0 and leaves the origin, RaysFromPoints
+ * (occluded_rays) sets both. */
 #ifndef RT_BATCH_REFILL
 #define RT_BATCH_REFILL 1
 #endif
-template <int NR, int STRIDE = BLOCK_THREADS>
-RT_DEV uint32_t occluded_batch_plain(const WideView& bvh, uint32_t* __restrict__ lds_stack, f3 p0, f3 n0, const f3 (&tgt)[NR],
-                                     uint32_t need)
+template <int NR, int STRIDE, class NextRay>
+RT_DEV uint32_t occluded_walk_plain(const WideView& bvh, uint32_t* __restrict__ lds_stack, const NextRay next_ray, uint32_t need)
 {
     if (bvh.n_tris <= 0) return 0u;
     constexpr uint32_t NONE = 0x7fffffffu;
-    const f3 ro = p0 + 0.001f * n0;
+    f3 ro = next_ray.origin();
     const float tmin = 0.0f, tmax = 0.99f;
     const int lane_slot = threadIdx.x;
     uint32_t occluded = 0u;
@@ -1435,11 +1437,7 @@ RT_DEV uint32_t occluded_batch_plain(const WideView& bvh, uint32_t* __restrict__
                 const int k = __ffs((int)need) - 1;
                 ray_bit = 1u << k;
                 need &= ~ray_bit;
-                f3 t = tgt[0];
-#pragma unroll
-                for (int j = 1; j < NR; ++j)
-                    if (k == j) t = tgt[j];
-                rd = t - p0;
+                next_ray(k, ro, rd);
                 inv = F3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
                 inv.x = fminf(fmaxf(inv.x, -1e30f), 1e30f);
                 inv.y = fminf(fmaxf(inv.y, -1e30f), 1e30f);
@@ -1659,8 +1657,8 @@ RT_DEV int occluded_count_refill(const WideView& bvh, uint32_t* __restrict__ lds
 #ifndef RT_BATCH_WS
 #define RT_BATCH_WS 1
 #endif
-template <int NR, int STRIDE = BLOCK_THREADS>
-RT_DEV uint32_t occluded_batch_ws(const WideView& bvh, uint32_t* __restrict__ lds_generic, f3 p0, f3 n0, const f3 (&tgt)[NR], uint32_t need)
+template <int NR, int STRIDE, class NextRay>
+RT_DEV uint32_t occluded_walk_ws(const WideView& bvh, uint32_t* __restrict__ lds_generic, const NextRay next_ray, uint32_t need)
 {
     if (bvh.n_tris <= 0) return 0u;
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
@@ -1670,7 +1668,7 @@ RT_DEV uint32_t occluded_batch_ws(const WideView& bvh, uint32_t* __restrict__ ld
     volatile lds_u32* s_hit = lds_stack + WIDE_LDS_STACK * STRIDE;         /* [slot]: mask of occluded rays of the lane that owns them */
     volatile lds_u32* s_match = lds_stack + (WIDE_LDS_STACK + 1) * STRIDE;
     s_hit[slot] = 0u;
-    f3 ro = p0 + 0.001f * n0;
+    f3 ro = next_ray.origin();
     const float tmin = 0.0f, tmax = 0.99f;
     uint32_t ovf[WIDE_OVF_STACK];
     int sp = 0, base = 0;
@@ -1714,11 +1712,7 @@ RT_DEV uint32_t occluded_batch_ws(const WideView& bvh, uint32_t* __restrict__ ld
                 const int k = __ffs((int)need) - 1;
                 ray_bit = 1u << k;
                 need &= ~ray_bit;
-                f3 t = tgt[0];
-#pragma unroll
-                for (int j = 1; j < NR; ++j)
-                    if (k == j) t = tgt[j];
-                rd = t - p0;
+                next_ray(k, ro, rd);
                 inv = F3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
                 inv.x = fminf(fmaxf(inv.x, -1e30f), 1e30f);
                 inv.y = fminf(fmaxf(inv.y, -1e30f), 1e30f);
@@ -1844,6 +1838,44 @@ RT_DEV uint32_t occluded_batch_ws(const WideView& bvh, uint32_t* __restrict__ ld
     }
     return s_hit[slot];
 }
+/* the ray sources of the two walks. From a common surface point: the origin is fixed, ray k heads for tgt[k] */
+template <int NR>
+RT_DEV f3 batch_pick(const f3 (&a)[NR], int k)
+{
+    f3 t = a[0];
+#pragma unroll
+    for (int j = 1; j < NR; ++j)
+        if (k == j) t = a[j];
+    return t;
+}
+template <int NR>
+struct RaysFromPoint
+{
+    const f3 p0, n0;
+    const f3 (&tgt)[NR];
+    RT_DEV f3 origin() const { return p0 + 0.001f * n0; }
+    RT_DEV void operator()(int k, f3&, f3& rd) const { rd = batch_pick<NR>(tgt, k) - p0; }
+};
+/* an origin per ray, taken at the refill pass beside the direction */
+template <int NR>
+struct RaysFromPoints
+{
+    const f3 (&org)[NR];
+    const f3 (&dir)[NR];
+    RT_DEV f3 origin() const { return F3(0.0f, 0.0f, 0.0f); }
+    RT_DEV void operator()(int k, f3& ro, f3& rd) const { ro = batch_pick<NR>(org, k); rd = batch_pick<NR>(dir, k); }
+};
+template <int NR, int STRIDE = BLOCK_THREADS>
+RT_DEV uint32_t occluded_batch_plain(const WideView& bvh, uint32_t* __restrict__ lds_stack, f3 p0, f3 n0, const f3 (&tgt)[NR],
+                                     uint32_t need)
+{
+    return occluded_walk_plain<NR, STRIDE>(bvh, lds_stack, RaysFromPoint<NR>{p0, n0, tgt}, need);
+}
+template <int NR, int STRIDE = BLOCK_THREADS>
+RT_DEV uint32_t occluded_batch_ws(const WideView& bvh, uint32_t* __restrict__ lds_generic, f3 p0, f3 n0, const f3 (&tgt)[NR], uint32_t need)
+{
+    return occluded_walk_ws<NR, STRIDE>(bvh, lds_generic, RaysFromPoint<NR>{p0, n0, tgt}, need);
+}
 template <int NR, int STRIDE = BLOCK_THREADS>
 RT_DEV uint32_t occluded_batch(const WideView& bvh, uint32_t* __restrict__ lds_stack, f3 p0, f3 n0, const f3 (&tgt)[NR], uint32_t need,
                                const float4* __restrict__ tv = nullptr, const int own_tri = -1)
@@ -1855,6 +1887,22 @@ RT_DEV uint32_t occluded_batch(const WideView& bvh, uint32_t* __restrict__ lds_s
     return self | occluded_batch_ws<NR, STRIDE>(bvh, lds_stack, p0, n0, tgt, need);
 #else
     return self | occluded_batch_plain<NR, STRIDE>(bvh, lds_stack, p0, n0, tgt, need);
+#endif
+}
+
+/* The same for up to NR shadow rays of ONE lane that start at a point each (the unbiased spatial pass: the pixel's selected
+ * light sample seen from the surface points of the <= 5 neighbours that were merged, and from its own): ray k has origin
+ * org[k], direction dir[k], t in [0, 0.99], and is traced iff bit k of `need` is set; returns the mask of occluded rays.
+ * The same two walks, with the origin taken at the refill pass beside the direction (the work-sharing form hands the origin
+ * to a helper with the rest of the ray anyway). The self-occlusion pre-test is the caller's: every ray has a triangle of its
+ * own to start from (self_occluded). */
+template <int NR, int STRIDE = BLOCK_THREADS>
+RT_DEV uint32_t occluded_rays(const WideView& bvh, uint32_t* __restrict__ lds_stack, const f3 (&org)[NR], const f3 (&dir)[NR], uint32_t need)
+{
+#if RT_BATCH_WS
+    return occluded_walk_ws<NR, STRIDE>(bvh, lds_stack, RaysFromPoints<NR>{org, dir}, need);
+#else
+    return occluded_walk_plain<NR, STRIDE>(bvh, lds_stack, RaysFromPoints<NR>{org, dir}, need);
 #endif
 }
 

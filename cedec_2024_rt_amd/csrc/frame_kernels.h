@@ -1263,6 +1263,164 @@ __global__ __launch_bounds__(TRACE_BLOCK, RT_SHSPATIAL_WAVES) void k_spatial(Sce
     spatial_pixel<true, TRACE_BLOCK>(S, P, F, s_stack, x, row, g0, g1, in_rec, in_rad, out_rec, out_rad);
 }
 
+/* ------------------------------------------------- unbiased spatial_resampling
+ * rt_spatial_unbiased: the pass with the 1/Z normalisation of Bitterli et al. 2020, Alg. 6, instead of the
+ * reference's 1/M. The merge chain is the reference's (same draws, same rejections: rt_halo_mark and rt_spatial_bytes replay
+ * it), with three differences: the own weight is recomputed, a neighbour's M is scaled by the rejection heuristics between the
+ * two G-BUFFER surfaces (not the travelling sample origin: Mk must not depend on what was selected), and afterwards every
+ * contributor is asked whether its own target function is positive at the selected sample y: geometry term > 0 from its surface
+ * point and, under visibility reuse, y visible from there. Z sums the M of those that say yes.
+ * The form is spatial_wave_shadowed's: one-wavefront workgroups on 8 x 8 tiles, the record traffic four lanes per 64-B record
+ * through the walk's LDS, every lane stays to the end and helps the others' walks. New against it: (a) the <= 6 rays of a pixel
+ * start at a surface point each and end at one target (occluded_rays, bvh.h; the self-occlusion pre-test runs per origin
+ * triangle), (b) a neighbour's G-buffer entry (32 B) is fetched beside its record, (c) two phases: the rays depend on the sample
+ * the merge chain selected. A ray is left unwalked only where its answer is held: the own ray, if the own sample survived and
+ * a kernel of this staged frame has walked it (own-visibility flags, rt_device.h). A neighbour record's visibility flag is no
+ * such proof: it may come from a frame of the biased mode. Whole-frame contexts only (no halo lists); unshadowed target; <= 5
+ * neighbours. */
+#ifndef RT_UNBIASED_WAVES
+#define RT_UNBIASED_WAVES 4 /* register budget in wavefronts per SIMD: five neighbour surfaces (p, n, triangle, Mk) stay live across the merge chain */
+#endif
+template <int TB>
+RT_DEV void spatial_wave_unbiased(const SceneView& S, const FrameParams& P, uint32_t* s_stack, const float4* __restrict__ g0,
+                                  const float4* __restrict__ g1, const float4* __restrict__ in_rec, const float4* __restrict__ in_rad,
+                                  float4* __restrict__ out_rec, float4* __restrict__ out_rad)
+{
+    float4* s_img = reinterpret_cast<float4*>(s_stack);
+    const int lane = (int)(threadIdx.x & 63);
+    int x = 0, row = P.lrow0;
+    const bool in_image = tile_pixel<TB>(P, x, row);
+    const int yi = P.H - 1 - row;
+    const size_t li = in_image ? (size_t)x + (size_t)(row - P.lrow0) * P.W : 0;
+    float4 G0 = make_float4(0.0f, 0.0f, 0.0f, as_float(-1)), G1 = make_float4(0.0f, 1.0f, 0.0f, 0.0f);
+    if (in_image) { G0 = g0[li]; G1 = g1[li]; }
+    const bool active = in_image && (as_uint(G1.w) & GB_SHADED);
+    const f3 sp = F3(G0.x, G0.y, G0.z), sn = F3(G1.x, G1.y, G1.z);
+    PCG rng = pcg_init(hashPCG4((uint32_t)x, (uint32_t)yi, (uint32_t)P.frame, (uint32_t)(2 + P.pass)), 0);
+    float4 q0, q1, q2, q3;
+    wave_gather_records_at(in_rec, (uint32_t)li, s_img, lane, q0, q1, q2, q3);
+    bool own_shaded;
+    Res r = res_from_parts(q0, q1, q2, q3, own_shaded);
+    uint32_t sel = (uint32_t)li; /* pixel whose radiance side record goes with the selected sample */
+
+    /* phase 1: the merge chain. Index 5 of the surface arrays is the pixel itself. */
+    f3 np[6], nn[6];
+    int ntri[6], Mk[5];
+    np[5] = sp; nn[5] = sn; ntri[5] = active ? as_int(G0.w) : -1;
+    r.w_sum = unbiased_weight(sp, sn, r.hit_p, r.hit_n, r.lum, 1.0f, r.ucw, r.M);
+    int Z = r.M;
+    const float scale = P.spatial_radius / 1.96f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+    {
+        np[k] = sp; nn[k] = sn; ntri[k] = -1; Mk[k] = 0;
+        if (k < P.spatial_count) /* wave-uniform */
+        {
+            uint32_t nidx = (uint32_t)li;
+            bool have = false;
+            if (active)
+            {
+                const float rv0 = rng.uniformf();
+                const float rv1 = rng.uniformf();
+                const float radius = sqrt_guarded(fmax_dev(-2.0f * pm_logf(rv0), 0.0f));
+                const float phi = 2.0f * kPI * rv1;
+                float sn_phi, cs_phi;
+                pm_sincosf(phi, &sn_phi, &cs_phi);
+                const float gx = radius * cs_phi, gy = radius * sn_phi;
+                const int nx = f2i_sat((float)x + scale * gx);
+                const int ny = f2i_sat((float)yi + scale * gy);
+                const int lr = P.H - 1 - ny - P.lrow0;
+                have = !(nx < 0 || nx >= P.W || ny < 0 || ny >= P.H) && !(nx == x && ny == yi) && !(lr < 0 || lr >= P.lrows);
+                if (have) nidx = (uint32_t)nx + (uint32_t)lr * (uint32_t)P.W;
+            }
+            const float4 N0 = g0[nidx], N1 = g1[nidx]; /* the neighbour's surface: on its way while the records are exchanged */
+            wave_gather_records_at(in_rec, nidx, s_img, lane, q0, q1, q2, q3);
+            if (have && (as_uint(q1.w) & RES_SHADED_BIT))
+            {
+                bool n_shaded;
+                const Res nr = res_from_parts(q0, q1, q2, q3, n_shaded);
+                np[k] = F3(N0.x, N0.y, N0.z); nn[k] = F3(N1.x, N1.y, N1.z); ntri[k] = as_int(N0.w);
+                Mk[k] = scale_M(nr.M, rejection_heuristics(sp, sn, np[k], nn[k], P.eye));
+                const float weight = unbiased_weight(sp, sn, nr.hit_p, nr.hit_n, nr.lum, (P.vis_reuse && !nr.vis) ? 0.0f : 1.0f, nr.ucw, Mk[k]);
+                const float u = rng.uniformf();
+                r.w_sum += weight;
+                r.M += Mk[k];
+                if (reservoir_accept(u, weight, r.w_sum))
+                {
+                    res_take_sample(r, nr);
+                    sel = nidx;
+                }
+            }
+        }
+    }
+
+    /* phase 2: who could have produced the selected sample? */
+    const f3 y = r.hit_p, yn = r.hit_n;
+    uint32_t need = 0u;
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (Mk[k] > 0 && unbiased_in_support(np[k], nn[k], y, yn))
+        {
+            if (P.vis_reuse) need |= 1u << k;
+            else Z += Mk[k];
+        }
+    const float4 rq = in_rad[sel];
+    /* the own ray: walked already if the own sample survived and a kernel of this staged frame says so */
+    const uint32_t own_flags = sel == (uint32_t)li ? ownv_trusted(P.ownv_tag, as_uint(rq.w)) : 0u;
+    if (active && P.vis_reuse && !(own_flags & OWNV_KNOWN)) need |= 1u << 5;
+    f3 org[6], dir[6];
+    uint32_t occl = 0u;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+    {
+        org[k] = np[k] + 0.001f * nn[k];
+        dir[k] = y - np[k];
+        /* rays that head below their surface: the triangle they start from first (bvh.h, self_occluded) */
+        if (self_occluded(S.bvh.tv, ntri[k], org[k], dir[k], nn[k], ((need >> k) & 1u) != 0u)) occl |= 1u << k;
+    }
+    if (P.stats)
+    {
+        /* the reference's unshadowed pass traces nothing here: 0 reference rays; walked / settled by the origin's own triangle /
+         * the own ray an earlier kernel of the frame has answered */
+        const uint32_t n_self = (uint32_t)__popc(occl), skipped = (active && P.vis_reuse && (own_flags & OWNV_KNOWN)) ? 1u : 0u;
+        count_walk_counts(P.stats + 4 * WALK_SPATIAL, 0u, (uint32_t)__popc(need) - n_self, n_self, skipped);
+    }
+    occl |= occluded_rays<6, TB>(S.wide, s_stack, org, dir, need & ~occl);
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (((need >> k) & 1u) && !((occl >> k) & 1u)) Z += Mk[k];
+    const float p_hat = target_unshadowed(sp, sn, y, yn, r.lum);
+    r.ucw = unbiased_ucw(r.w_sum, Z, p_hat);
+    if (active)
+    {
+        r.rad = F3(rq.x, rq.y, rq.z);
+        r.ownv = sel == (uint32_t)li ? as_uint(rq.w) : 0u; /* without visibility reuse no ray from here was walked: what is known stays */
+        if (P.vis_reuse)
+        {
+            /* the flag now means "visible from THIS pixel" whoever the sample came from */
+            const bool visible = (own_flags & OWNV_KNOWN) ? (own_flags & OWNV_VISIBLE) != 0u : !((occl >> 5) & 1u);
+            r.vis = visible;
+            r.ownv = ownv_of(P.ownv_tag, visible);
+        }
+    }
+    else
+        r = res_zero(); /* the reference stores nothing here (:275-287); we keep the shaded bit valid */
+    const uint32_t mbits = ((uint32_t)r.M & RES_M_MASK) | (r.vis ? RES_VIS_BIT : 0u) | (active ? RES_SHADED_BIT : 0u);
+    wave_scatter_records<false>(out_rec, in_image ? (int)li : -1, s_img, lane, make_float4(r.hit_p.x, r.hit_p.y, r.hit_p.z, r.ucw),
+                         make_float4(r.hit_n.x, r.hit_n.y, r.hit_n.z, as_float(mbits)), make_float4(r.org_p.x, r.org_p.y, r.org_p.z, r.lum),
+                         make_float4(r.org_n.x, r.org_n.y, r.org_n.z, r.w_sum));
+    if (in_image) store_stream<0>(out_rad + li, make_float4(r.rad.x, r.rad.y, r.rad.z, as_float(r.ownv)));
+}
+__global__ __launch_bounds__(TRACE_BLOCK, RT_UNBIASED_WAVES) void k_spatial_unbiased(SceneView S, FrameParams P, const float4* __restrict__ g0,
+                                                    const float4* __restrict__ g1, const float4* __restrict__ in_rec,
+                                                    const float4* __restrict__ in_rad, float4* __restrict__ out_rec,
+                                                    float4* __restrict__ out_rad)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_stack[WIDE_LDS_ROWS * TRACE_BLOCK];
+    static_assert(sizeof(s_stack) >= 4096, "the record image needs 64 x 64 B");
+    spatial_wave_unbiased<TRACE_BLOCK>(S, P, s_stack, g0, g1, in_rec, in_rad, out_rec, out_rad);
+}
+
 /* Unshadowed target function = the roofline kernel: no rays, five dependent 64-B record gathers per pixel.
  * The register allocation can be told to admit at most WAVES wavefronts per SIMD (template parameter; rt_tuning key 9;
  * round 1 did this with a dummy 32 KB LDS allocation, and rt_tuning key 4 still adds LDS for A/B runs, default 0): the

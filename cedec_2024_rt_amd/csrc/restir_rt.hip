@@ -198,6 +198,7 @@ struct rt_ctx
     int tune_half_raycast = 0; /* rt_tuning key 24 (r05, experiments build): half-density raycast with helper lanes */
     int tune_fuse_final = -1; /* rt_tuning key 23 (r05): last spatial pass + resolve in one kernel: -1 auto, 0 never, 1 always, 2 = A/B without the pass's stores */
     bool final_fused = false; /* the running frame's last pass has resolved its rows */
+    bool spatial_unbiased = false; /* rt_spatial_unbiased: the spatial passes normalise by 1/Z (k_spatial_unbiased) */
     int tune_spec_free = -1; /* rt_tuning key 22 (r05): the look-ahead stage 0 free of the main stream and of the latest resolve: -1 auto = strips */
     int tune_mark_split = 0; /* rt_tuning key 26 (r06): k_halo_mark as one workgroup per (tile, pass) instead of per tile. Measured, no gain: rank 4 of
                                 8, WIRE_MODEL 0.3286 / 0.3314 (on) against 0.3310 / 0.3293 ms (off) at 1080p, 0.915 / 0.910 against 0.923 / 0.916 at 4K,
@@ -2020,6 +2021,7 @@ static int halo_rows_needed(const rt_options& o)
 static bool use_lds_spatial(const rt_ctx* c)
 {
     return (c->tune_spatial_variant == 1 || c->tune_spatial_variant == 3) && c->opt.use_spatial_resampling && !c->opt.use_shadowed_target_function &&
+           !c->spatial_unbiased &&
            halo_rows_needed(c->opt) <= SPL_HALO && c->opt.spatial_resampling_sample_count <= 5 &&
            c->row_begin == 0 && c->row_end == c->H;
 }
@@ -2053,11 +2055,24 @@ static bool use_fused_final(const rt_ctx* c)
 #endif
     const bool whole = c->row_begin == 0 && c->row_end == c->H;
     const int want = c->tune_fuse_final < 0 ? (whole ? RT_FUSE_FINAL_AUTO : 0) : c->tune_fuse_final;
-    return want != 0 && !c->opt.use_shadowed_target_function && c->opt.use_spatial_resampling && c->tune_spatial_variant == 2 && !c->tune_stream &&
+    return want != 0 && !c->opt.use_shadowed_target_function && c->opt.use_spatial_resampling && !c->spatial_unbiased && c->tune_spatial_variant == 2 && !c->tune_stream &&
            c->opt.spatial_resampling_passes >= 1;
+}
+/* rt_spatial_unbiased: does the 1/Z pass run for the current options, and can it? (with use_spatial_resampling = 0 the pass copies its
+ * input in either mode) */
+static bool unbiased_applies(const rt_ctx* c) { return c->spatial_unbiased && c->opt.use_spatial_resampling; }
+static int unbiased_check(rt_ctx* c)
+{
+    if (!unbiased_applies(c)) return RT_OK;
+    if (c->opt.use_shadowed_target_function)
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_spatial_unbiased: the shadowed target function is not built for the 1/Z pass");
+    if (c->opt.spatial_resampling_sample_count > 5)
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_spatial_unbiased: %d neighbours per pass, the 1/Z pass takes at most 5", c->opt.spatial_resampling_sample_count);
+    return RT_OK;
 }
 static int launch_spatial(rt_ctx* c, const Launch& L, int frame, int pass, int in_phys, int out_phys, bool fuse_final = false)
 {
+    { const int rc = unbiased_check(c); if (rc != RT_OK) return rc; }
     const int need = halo_rows_needed(c->opt);
     if ((c->row_begin > 0 && c->row_begin - c->lrow0 < (need < c->row_begin ? need : c->row_begin)) ||
         (c->row_end < c->H && c->lrow0 + c->lrows - c->row_end < (need < c->H - c->row_end ? need : c->H - c->row_end)))
@@ -2068,7 +2083,10 @@ static int launch_spatial(rt_ctx* c, const Launch& L, int frame, int pass, int i
     const bool lds_variant = use_lds_spatial(c);
     (void)lds_variant; /* the product build has no LDS-staged form */
     c->rec_gserial[out_phys] = c->gbuf_serial;
-    if (c->opt.use_shadowed_target_function)
+    if (unbiased_applies(c))
+        /* one kernel whatever keys 8 and 23 say: the A/B forms restate the reference's pass */
+        k_spatial_unbiased<<<trace_grid(c, L), TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys]);
+    else if (c->opt.use_shadowed_target_function)
     {
         /* the cooperative record traffic of key 8 = 2 applies to the <= 5 neighbour form (spatial_wave_shadowed) */
         if (c->tune_spatial_variant >= 2 && c->opt.use_spatial_resampling && c->opt.spatial_resampling_sample_count <= 5)
@@ -2526,6 +2544,7 @@ int rt_frame_stage_begin(rt_ctx* c, int frame, int stage, int clear_first)
 {
     RT_CHECK_CTX(c);
     NEED_SCENE(c);
+    if (stage == 0 && c->opt.spatial_resampling_passes > 0) { const int rc = unbiased_check(c); if (rc != RT_OK) return rc; } /* before the frame starts */
     c->last_frame = frame;
     /* a spatial stage reads the shaded-bit rows from both lanes: (re)built here, on the main stream, if the halo flags
      * arrived after the raycast (cold frame of a strip) */
@@ -2845,6 +2864,24 @@ int rt_gbuffer_reuse(rt_ctx* c, int on)
     c->gbuf_reuse = on != 0;
     /* a look-ahead enqueued under the other setting is not taken: the next frame runs its own stage 0 */
     c->spec_valid = false; c->spec_gen_valid = false;
+    return RT_OK;
+}
+/* The spatial passes with the 1/Z normalisation (k_spatial_unbiased). Changes results, so not an rt_tuning key either; counts as an option
+ * change (rt_state_epoch). Touches no buffer: history written under the other setting stays and fades with the M cap. */
+int rt_spatial_unbiased(rt_ctx* c, int on)
+{
+    RT_CHECK_CTX(c);
+    if (c->row_begin != 0 || c->row_end != c->H)
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_spatial_unbiased: strip contexts hold no traced G-buffer in their halo rows");
+    c->spatial_unbiased = on != 0;
+    ++c->epoch;
+    return RT_OK;
+}
+int rt_spatial_unbiased_get(rt_ctx* c, int* on)
+{
+    RT_CHECK_CTX(c);
+    if (!on) return RT_ERR_ARG;
+    *on = c->spatial_unbiased ? 1 : 0;
     return RT_OK;
 }
 int rt_primary_launches(rt_ctx* c, uint64_t* n)

@@ -309,6 +309,22 @@ RT_HD int f2i_sat(float f)
 /* `M *= w` for int M, float w (10_restir_di.cu:211-212, 362-363) [parity] */
 RT_HD int scale_M(int M, float w) { return f2i_sat((float)M * w); }
 
+/* ---- unbiased spatial reuse (rt_spatial_unbiased; Bitterli et al. 2020, Alg. 6): the arithmetic the kernel
+ * (frame_kernels.h, k_spatial_unbiased) and its CPU restatement (tests/restir_unbiased_ref.py) share, binary32 in this order.
+ * A contributor's RIS weight p-hat_q(its sample) * its ucw * its M, with p-hat the unshadowed target at the MERGING pixel q
+ * times the contributor's own visibility flag where visibility reuse is on (`vis`: 1.0f or 0.0f; the own term passes 1.0f:
+ * its weight is recomputed from ucw and M because the stored w_sum is no longer p-hat * ucw * M once Z != M). */
+RT_HD float unbiased_weight(f3 sp, f3 sn, f3 hp, f3 hn, float lum, float vis, float ucw, int M)
+{
+    const float p_hat = target_unshadowed(sp, sn, hp, hn, lum) * vis;
+    return p_hat * ucw * (float)M;
+}
+/* does the contributor at surface (np, nn) count in Z for the selected sample (y, ny), as far as geometry says: its own
+ * unshadowed target is positive there (luminance > 0 for every light sample) */
+RT_HD bool unbiased_in_support(f3 np, f3 nn, f3 y, f3 ny) { return geometry_term(np, nn, y, ny) > 0.0f; }
+/* W = w_sum / (Z p-hat): Z = the M of the contributors that could have produced the selected sample */
+RT_HD float unbiased_ucw(float w_sum, int Z, float p_hat) { return (p_hat > 0.0f && Z > 0) ? w_sum / ((float)Z * p_hat) : 0.0f; }
+
 /* common/core.hpp:45-68 on raw vertices [parity] */
 RT_HD f3 tri_normal(f3 v0, f3 v1, f3 v2) { return normalize(cross(v1 - v0, v2 - v0)); }
 RT_HD float tri_area(f3 v0, f3 v1, f3 v2) { return 0.5f * length(cross(v1 - v0, v2 - v0)); }

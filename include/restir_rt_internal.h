@@ -245,6 +245,22 @@ int rt_stage0_one_launch(rt_ctx* ctx, int* one_launch);
  * RT_ERR_UNSUPPORTED. Not an rt_tuning key: tests/golden/tuning_matrix.json pins keys 29 and 30 as unknown and the table has one row
  * per key. */
 int rt_gbuffer_reuse(rt_ctx* ctx, int on);
+/* Unbiased spatial reuse, default off: every byte is then what it was without the call. While on,
+ * rt_spatial_resampling, rt_frame and rt_frame_stage* run the spatial pass with the 1/Z normalisation of Bitterli et al. 2020 (Alg. 6)
+ * whenever use_spatial_resampling = 1: Z counts only the contributors (the pixel and the merged neighbours) whose own target function
+ * is positive at the selected light sample - geometry term from their G-buffer surface and, under use_visibility_reuse, one shadow
+ * ray each - a neighbour's M is scaled by the rejection heuristics between the two G-buffer surfaces, and the record's visibility
+ * flag is re-evaluated from the pixel itself, so that the record is valid as a neighbour in the next pass. Candidates, the temporal
+ * merge, resolve and tone mapping are unchanged. Not built yet, RT_ERR_UNSUPPORTED at the launching call:
+ * use_shadowed_target_function = 1, spatial_resampling_sample_count > 5. Strip contexts (and so rt_mg_frame): RT_ERR_UNSUPPORTED
+ * from the toggle itself, their halo rows hold no traced G-buffer. The call changes rt_state_epoch, as rt_options_set does, and
+ * touches no buffer. The temporal history needs no restart on either switch: it is saved before the spatial passes and never holds
+ * a spatial pass's output. The [exp] spatial variants (rt_tuning keys 8 and 23) do not apply while the mode is on. rt_ray_count
+ * keeps counting the reference's rays (none in an unshadowed pass). rt_walk_stats' spatial slot then reports 0 reference rays, the
+ * rays walked, those the origin's own triangle settled and, as not_evaluated, the own rays an earlier kernel of the frame had
+ * answered: the slot's sum is the pass's own rays, not the reference's. Not an rt_tuning key: tuning keys never change results. */
+int rt_spatial_unbiased(rt_ctx* ctx, int on);
+int rt_spatial_unbiased_get(rt_ctx* ctx, int* on);
 /* launches so far that traced primary rays over the context's rows: rt_raycast, stage-0 raycasts, the one-launch stage 0 and
  * look-ahead raycasts (counted when launched, taken or not). How the tests see reuse without timing anything. */
 int rt_primary_launches(rt_ctx* ctx, uint64_t* n);

@@ -26,6 +26,7 @@ BUDGET = [
     (r"^k_spatial_coop<6, true, 256>", 0, 5),                                 # strips: halo lists read / written in the pass
     (r"^k_resolve<", 0, 8),
     (r"^k_spatial<true, true>", 80, 7),
+    (r"^k_spatial_unbiased", 0, 4),      # r15 rt_spatial_unbiased: 124 VGPRs, no spill at 4 wavefronts per SIMD (5 / 6 / 7: 93 / 171 / 164 spilled)
     (r"^k_tone_mapping", 0, 8),
     (r"^k_halo_mark<", 0, 8),
     (r"^k_ao<0>", 0, 7),   # r07 ambient occlusion, pixel-major (default): 8 wavefronts per SIMD (RT_AO_WAVES=8) measured no faster
