@@ -24,6 +24,7 @@
 
 #include "../../include/restir_rt_internal.h"
 #include "bvh.h"
+#include "frame_roles.h"
 #include "rt_device.h"
 
 using namespace rt;
@@ -35,6 +36,7 @@ static_assert(sizeof(rt_options) == 48, "Options layout (common/options.hpp:4-22
 static_assert(offsetof(rt_options, use_shadowed_target_function) == 44, "Options layout");
 static_assert(sizeof(rt_raygen) == 36, "RayGenerator layout (common/camera.hpp:5-9)");
 static_assert(sizeof(BvhNode) == 64, "BVH node");
+static_assert(ROLE_RES_0 == RT_RES_0 && ROLE_RES_1 == RT_RES_1 && ROLE_RES_TEMPORAL == RT_RES_TEMPORAL, "frame_roles.h names the reservoir buffers as restir_rt.h does");
 
 #include "frame_kernels.h"
 #include "host_path.h"
@@ -59,23 +61,46 @@ struct rt_ctx
      * (HBM-bound) and the halo exchanges of frame f and frame f+1 starts at generate_candidate. The result is used only
      * if nothing it depends on changed meanwhile (epoch: camera, scene, options); otherwise frame f+1 traces its
      * primary rays as usual. rt_tuning key 14. */
-    hipStream_t spec_stream = nullptr;
-    hipEvent_t ev_spec_go = nullptr, ev_spec_done = nullptr, ev_spec_t[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+    struct
+    {
+        hipStream_t stream = nullptr;
+        hipEvent_t ev_go = nullptr, ev_done = nullptr, ev_t[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+        int timed_set = -1;
+        bool valid = false, timed[3] = {false, false, false};
+        bool outstanding = false; /* work recorded by ev_done that the main stream has not waited for yet */
+        bool reuse = false;       /* it read the current G-buffer set (gbuffer_reusable): candidates only, no primary rays */
+        /* its candidates (pipelined stage 0, further down): for which frame, from which history buffer, under which tag (below) */
+        bool gen_valid = false;
+        int gen_frame = 0, gen_hist = -1;
+        uint32_t gen_tag = 0;
+        uint64_t epoch = 0, res_epoch = 0; /* `epoch` / `res_epoch` of the context when it was launched */
+    } ahead;
     /* r05: THREE G-buffer sets (frame f reads set f mod 3): the pipelined stage 0 of frame f+1 overwrites the set of frame f-2,
      * whose last reader — resolve(f-2) — is two tails back, not the set resolve(f-1) may still be reading (with two sets every
      * look-ahead raycast waited for the previous frame's resolve: the one edge that made a strip's frame a dependency chain
      * instead of three streams of independent work, profiles/r05_strip_timelines.txt) */
     static constexpr int NGSET = 3;
-    float4* d_gset[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; /* [set]{vis, g0, g1}; d_vis/d_g0/d_g1 = set gcur */
-    int gcur = 0, timed_spec_set = -1;
-    bool spec_valid = false, spec_timed[3] = {false, false, false};
-    bool spec_outstanding = false; /* work recorded by ev_spec_done that the main stream has not waited for yet */
-    uint64_t spec_epoch = 0;
+    struct
+    {
+        float4* set[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; /* [set]{vis, g0, g1}; vis/g0/g1 = set cur */
+        int cur = 0;
+        float4 *vis = nullptr, *g0 = nullptr, *g1 = nullptr;
+        bool valid = false, shaded_bits_stale = true; /* a G-buffer has been traced or uploaded / d_shaded_bits predates it */
+        /* which G-buffer a reservoir buffer's shaded bits belong to (k_refresh_shaded, rec_gserial): serial counts G-buffer writes; epoch: the one the current G-buffer was traced under */
+        uint64_t serial = 0, epoch = 0;
+        /* r13, rt_gbuffer_reuse: the primary ray of a pixel has no jitter and no frame number in it (frame_kernels.h, shoot(xi / W, yi / H)),
+         * so Visibility / g0 / g1 are a function of camera, scene and image size: of `epoch`. A staged frame of a whole-frame context whose
+         * current set was traced over all owned rows under the current epoch launches its candidates on that set and no primary rays
+         * (gbuffer_reusable). traced_epoch: the epoch under which ALL owned rows of set cur were traced by a raycast launch or the
+         * one-launch stage 0 (0 = never; an upload bumps `epoch` and does not set it: k_gbuffer_from_vis is not a trace).
+         * ahead_ordered: ahead.stream is known to be behind the launch that wrote the set (the look-ahead candidates read it there). */
+        bool reuse = true, ahead_ordered = false;
+        uint64_t traced_epoch = 0, primary_launches = 0;
+    } gbuf;
     /* tags of the own-visibility flags (rt_device.h): one number per staged frame and per pipelined stage 0; the launches of
-     * a staged frame carry frame_tag (Launch::tag), the per-kernel entry points carry 0 */
-    uint32_t ownv_serial = 0, frame_tag = 0, spec_gen_tag = 0;
-    /* which G-buffer a reservoir buffer's shaded bits belong to (k_refresh_shaded): gbuf_serial counts G-buffer writes */
-    uint64_t gbuf_serial = 0, rec_gserial[5] = {0, 0, 0, 0, 0};
+     * a staged frame carry frame.tag (Launch::tag), the per-kernel entry points carry 0 */
+    uint32_t ownv_serial = 0;
+    uint64_t rec_gserial[5] = {0, 0, 0, 0, 0}; /* gbuf.serial of the G-buffer each reservoir buffer's shaded bits belong to */
     unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters */
     bool walk_on = false;
     int tune_ws_primary = -1; /* rt_tuning key 16: primary rays with the work-sharing closest-hit walk: -1 auto (r04) = launches of at
@@ -104,7 +129,6 @@ struct rt_ctx
                                      per pass), none for the LDS-staged kernel (0.181 ms unbounded, 0.188 at 4) — profiles/r02_spatial_variants.json */
     uint32_t* d_shaded_bits = nullptr;
     uint32_t* d_mark_bits = nullptr; /* rt_halo_mark (key 19): shaded bits of all local rows, rebuilt per mark */
-    bool shaded_bits_stale = true;
     /* deferred visibility-reuse rays of the fused candidate kernel (frame_kernels.h, DEFER): one queue per lane
      * (main / second stream), its counter, and the last count that reached the host (sizes the next launch) */
     int tune_defer_vis = 0; /* rt_tuning key 11 */
@@ -153,36 +177,34 @@ struct rt_ctx
     double cost_at_build = -1.0;
     bool bin_stale = false; /* the binary tree (d_nodes, trace mode 1 of the experiments library) predates an update */
 
-    float4 *d_vis = nullptr, *d_g0 = nullptr, *d_g1 = nullptr, *d_accum = nullptr;
+    float4* d_accum = nullptr;
     uint32_t* d_pixels = nullptr;
-    /* three reservoir buffers carry the reference's names (res_map); a fourth, allocated when the pipelined stage 0 is
-     * first used, receives the NEXT frame's candidates while this frame's passes still read the other three */
-    /* r05: and a fifth. The buffer the previous frame's resolve reads ("quarantine") is not handed to the look-ahead candidates
-     * until one more frame has passed: they get the buffer that left the roles a frame earlier (last reader: two tails back). */
-    float4* d_rec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float4* d_rec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; /* the five reservoir buffers; their roles: frame (frame_roles.h) */
     float4* d_rad[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int res_map[3] = {0, 1, 2};
     /* Pipelined stage 0 (rt_tuning key 14 = 2, r03): frame f+1's generate_candidate(+temporal_resampling) depends on frame
      * f only through the temporal history, and the reference saves that history right after temporal_resampling, BEFORE
      * the spatial passes (10_restir_di.cpp:314-321) — so stage 0 of frame f+1 (primary rays, candidates, temporal merge)
-     * can run beside the spatial passes, halo exchanges and resolve of frame f. It is launched on spec_stream behind
+     * can run beside the spatial passes, halo exchanges and resolve of frame f. It is launched on ahead.stream behind
      * stage 0 of frame f, reads the history frame f just wrote, writes the spare buffer, and frame f+1 takes it if it
      * is frame f+1 indeed and nothing it read has changed meanwhile (epoch: camera / scene / options / uploads;
      * res_epoch: any call that writes a reservoir buffer outside the staged frame). Same launches, same results. */
     /* Tail stream (rt_tuning key 17, r03): resolve + tone_mapping of frame f read only frame f's final reservoirs and
      * G-buffer, so a strip's main stream does not wait for them — it goes on with frame f+1's first halo exchange while
-     * they run on a stream of their own. Whatever could overwrite what they read waits for ev_tail first: the next frame's
+     * they run on a stream of their own. Whatever could overwrite what they read waits for tail.ev first: the next frame's
      * first spatial pass (its output buffer can be this frame's final one), the next-but-one frame's pipelined stage 0 (same
      * G-buffer set, spare reservoir buffer), and every call outside the staged frame (join_tail). */
-    hipStream_t tail_stream = nullptr;
-    hipEvent_t ev_tail_go = nullptr, ev_tail = nullptr;
-    /* ev_resolved[0] = behind the latest staged frame's resolve (+ tone mapping) on whatever stream it ran, [1] = the one before:
-     * what the pipelined stage 0 waits for before it overwrites the G-buffer set and the reservoir buffer of two frames ago */
-    hipEvent_t ev_resolved[2] = {nullptr, nullptr};
-    int n_resolved = 0;
-    bool resolve_on_tail = false;
-    bool tail_pending_main = false;
-    int tail_phys = -1; /* reservoir buffer the tail in flight reads (the frame's final one) */
+    struct
+    {
+        hipStream_t stream = nullptr;
+        hipEvent_t ev_go = nullptr, ev = nullptr;
+        /* ev_resolved[0] = behind the latest staged frame's resolve (+ tone mapping) on whatever stream it ran, [1] = the one before:
+         * what the pipelined stage 0 waits for before it overwrites the G-buffer set and the reservoir buffer of two frames ago */
+        hipEvent_t ev_resolved[2] = {nullptr, nullptr};
+        int n_resolved = 0;
+        bool resolve_on = false; /* the running frame's resolve went to the tail stream */
+        bool pending_main = false;
+        int phys = -1; /* reservoir buffer the tail in flight reads (the frame's final one) */
+    } tail;
     int tune_tail = -1; /* -1 auto = on, 0 never, 1 always */
     int tune_mark_quick = 1; /* rt_tuning key 18: quick reject in k_halo_mark */
     int tune_mark_window = 1; /* rt_tuning key 19 (r04): k_halo_mark collects a workgroup's marks in LDS first */
@@ -193,11 +215,9 @@ struct rt_ctx
     unsigned long long* d_wave_clock = nullptr; /* rt_exp_wave_clock (experiments library): two words per wavefront of one kernel */
     size_t wave_clock_words = 0;
     int wave_clock_kernel = -1, wave_clock_pass = 0;
-    bool stage0_one_launch = false; /* the last staged frame's stage 0 on the main stream traced its primary rays in the candidates' launch */
     int tune_fuse_raycast = -1; /* rt_tuning key 25 (r05): stage 0 as ONE launch (primary ray, then candidates + temporal merge): -1 auto */
     int tune_half_raycast = 0; /* rt_tuning key 24 (r05, experiments build): half-density raycast with helper lanes */
     int tune_fuse_final = -1; /* rt_tuning key 23 (r05): last spatial pass + resolve in one kernel: -1 auto, 0 never, 1 always, 2 = A/B without the pass's stores */
-    bool final_fused = false; /* the running frame's last pass has resolved its rows */
     bool spatial_unbiased = false; /* rt_spatial_unbiased: the spatial passes normalise by 1/Z (k_spatial_unbiased) */
     int tune_spec_free = -1; /* rt_tuning key 22 (r05): the look-ahead stage 0 free of the main stream and of the latest resolve: -1 auto = strips */
     int tune_mark_split = 0; /* rt_tuning key 26 (r06): k_halo_mark as one workgroup per (tile, pass) instead of per tile. Measured, no gain: rank 4 of
@@ -205,26 +225,22 @@ struct rt_ctx
                                 MIRROR 0.292 / 0.288 against 0.287 / 0.283 and 0.810 / 0.816 against 0.811 / 0.808 (profiles/r06_mark_split_ab.txt):
                                 the marks are not on the frame's critical chain and their total work is the same. Default off. */
     int tune_mark_cache = 1; /* rt_tuning key 21 (r05): the shaded-bit rows of the halo marks are built once per epoch */
-    uint64_t mark_bits_epoch = 0, gbuf_epoch = 0; /* epoch d_mark_bits was built under (0: not cached) / the current G-buffer was traced under */
-    /* r13, rt_gbuffer_reuse: the primary ray of a pixel has no jitter and no frame number in it (frame_kernels.h, shoot(xi / W, yi / H)),
-     * so Visibility / g0 / g1 are a function of camera, scene and image size: of `epoch`. A staged frame of a whole-frame context whose
-     * current set was traced over all owned rows under the current epoch launches its candidates on that set and no primary rays
-     * (gbuffer_reusable). gbuf_traced_epoch: the epoch under which ALL owned rows of set gcur were traced by a raycast launch or the
-     * one-launch stage 0 (0 = never; an upload bumps `epoch` and does not set it: k_gbuffer_from_vis is not a trace).
-     * gbuf_spec_ordered: spec_stream is known to be behind the launch that wrote the set (the look-ahead candidates read it there). */
-    bool gbuf_reuse = true, gbuf_spec_ordered = false, spec_reuse = false;
-    uint64_t gbuf_traced_epoch = 0, primary_launches = 0;
+    uint64_t mark_bits_epoch = 0; /* epoch d_mark_bits was built under (0: not cached) */
     hipEvent_t ev_mark_bits = nullptr;
     bool mark_bits_event_valid = false, mark_bits_rebuilt = false;
     int tune_fuse_tonemap = 1; /* rt_tuning key 20 (r05): the staged frame's resolve kernel tone-maps its own pixel */
     HaloFuse fuse = {};        /* rt_halo_fuse_set: halo lists read / written by the running stage's spatial pass itself */
-    int spare = 3;             /* physical buffer not named by res_map: the look-ahead candidates' */
-    int quarantine = 4;        /* the buffer that left the roles at the last take (the previous frame's final one, or a free one) */
-    bool spec_gen_valid = false, gen_taken = false;
-    int spec_gen_frame = 0, spec_gen_hist = -1;
-    uint64_t res_epoch = 1, spec_res_epoch = 0;
-    int fX = 0, fY = 1, fZ = 2, f_in = 0, f_out = 1, f_stage = 0, f_final = RT_RES_1, f_frame = 0;
-    bool f_clear = false;
+    uint64_t res_epoch = 1; /* bumped by every call that writes a reservoir buffer outside the staged frame */
+    /* the staged frame in flight: the reservoir buffers' roles (frame_roles.h) and what its stages hand each other */
+    struct : FrameRoles
+    {
+        int stage = 0, number = 0;
+        bool clear = false;
+        bool gen_taken = false;   /* stage 0 took its candidates from the look-ahead: no generate launch of its own */
+        bool final_fused = false; /* the running frame's last pass has resolved its rows */
+        uint32_t tag = 0;         /* own-visibility tag of the frame's launches (ownv_serial above) */
+        bool one_launch = false;  /* the last staged frame's stage 0 on the main stream traced its primary rays in the candidates' launch */
+    } frame;
     uint64_t halo_flags_epoch[2] = {0, 0}; /* epoch at which the neighbour's shaded flags were unpacked (valid while it is the current one) */
     unsigned long long* d_counter = nullptr;
     float4* d_paths[2] = {nullptr, nullptr}; /* wavefront path tracer: live-path lists (64 B per path) */
@@ -251,7 +267,7 @@ struct rt_ctx
     rt_options opt;
     rt_raygen rg;
     float eye[3] = {0, 0, 0};
-    bool has_camera = false, has_scene = false, has_gbuffer = false;
+    bool has_camera = false, has_scene = false;
     float cam_eye[3] = {8.0f, 8.0f, 8.0f}, cam_at[3] = {0.0f, 0.0f, 0.0f}, cam_fovy = 0.78539816339f; /* misc.hpp:217-218 */
     bool cam_updated = false;
     /* bumped by everything that can change the G-buffer or the spatial pass's neighbour choice (camera,
@@ -306,7 +322,12 @@ struct Launch
     float4 *vis, *g0, *g1;        /* G-buffer set */
 };
 /* the context's current stream, all owned rows, the current G-buffer set: what a per-kernel entry point launches */
-static Launch whole_launch(const rt_ctx* c) { return Launch{c->stream, c->row_begin, c->row_end, 0, 0, 0u, c->timing, c->d_vis, c->d_g0, c->d_g1}; }
+static Launch whole_launch(const rt_ctx* c) { return Launch{c->stream, c->row_begin, c->row_end, 0, 0, 0u, c->timing, c->gbuf.vis, c->gbuf.g0, c->gbuf.g1}; }
+/* the context owns the whole image (not a strip of it) / the launch covers all rows the context owns, in one range */
+static bool whole_frame(const rt_ctx* c) { return c->row_begin == 0 && c->row_end == c->H; }
+static bool covers_owned_rows(const rt_ctx* c, const Launch& L) { return L.row0 == c->row_begin && L.row1 == c->row_end && L.rowb1 <= L.rowb0; }
+/* the look-ahead is no longer good: the next staged frame runs its own stage 0 (ahead.gen_valid is read under ahead.valid only) */
+static void drop_look_ahead(rt_ctx* c) { c->ahead.valid = false; c->ahead.gen_valid = false; }
 
 enum { K_RAYCAST = 0, K_GENERATE = 1, K_SPATIAL = 2, K_RESOLVE = 3, K_OTHER = 4 };
 static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int pass, int kernel = K_OTHER)
@@ -334,7 +355,7 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
          * 8-rank 4K strip -7 % with its spatial launches interleaved too (a 1080p one +-0). The whole frame's spatial pass keeps
          * its bands: its neighbour window has to stay in one XCD's L2 (interleaved: 0.132 -> 0.199 ms), and cutting the bands by
          * cost instead of height gains nothing (profiles/r05_spatial_band_cuts.txt). */
-        const bool whole = c->row_begin == 0 && c->row_end == c->H;
+        const bool whole = whole_frame(c);
         /* the shadowed-target pass traces up to six rays per pixel: a tracing kernel first (runs of 16 tiles per XCD: 4.67 -> 3.83 ms
          * per frame; interleaved tile rows 3.91) */
         const int spatial = c->opt.use_shadowed_target_function ? 7 : (whole || c->row_end - c->row_begin >= 400 ? 1 : 4);
@@ -350,8 +371,7 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
 #ifdef RT_EXPERIMENTS
     P.wave_clock = c->d_wave_clock && kernel == c->wave_clock_kernel && (kernel != K_SPATIAL || pass == c->wave_clock_pass) ? c->d_wave_clock : nullptr;
     /* whole launches over the context's own rows only (the grid the permutation was checked against) */
-    const bool own_rows = L.row0 == c->row_begin && L.row1 == c->row_end && L.rowb1 <= L.rowb0;
-    P.tile_perm = (kernel == K_RAYCAST || kernel == K_GENERATE || kernel == K_RESOLVE) && own_rows ? c->d_tile_perm[kernel] : nullptr;
+    P.tile_perm = (kernel == K_RAYCAST || kernel == K_GENERATE || kernel == K_RESOLVE) && covers_owned_rows(c, L) ? c->d_tile_perm[kernel] : nullptr;
 #endif
     return P;
 }
@@ -414,24 +434,24 @@ int rt_create(int device, int width, int height, int row_begin, int row_end, int
      * meant to run beside (measured: the pipelined stage 0 on the main stream's queue, 0.39 -> 0.51 ms per frame at 1080p
      * in 8 strips, profiles/r03_hw_queue_mapping.txt). Order of importance: main, pipelined stage 0, tail, second lane. */
     RT_HIP(c, hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, stream_priority("RT_MAIN_PRIORITY", 0)));
-    RT_HIP(c, hipStreamCreateWithPriority(&c->spec_stream, hipStreamNonBlocking, stream_priority("RT_SPEC_PRIORITY", 0)));
-    RT_HIP(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, stream_priority("RT_TAIL_PRIORITY", 0)));
+    RT_HIP(c, hipStreamCreateWithPriority(&c->ahead.stream, hipStreamNonBlocking, stream_priority("RT_SPEC_PRIORITY", 0)));
+    RT_HIP(c, hipStreamCreateWithPriority(&c->tail.stream, hipStreamNonBlocking, stream_priority("RT_TAIL_PRIORITY", 0)));
     /* default priority: with the lowest priority the lane was starved in some exchanges (A/B in DESIGN.md §7) */
     RT_HIP(c, hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-    RT_HIP(c, hipEventCreateWithFlags(&c->ev_spec_go, hipEventDisableTiming));
-    RT_HIP(c, hipEventCreateWithFlags(&c->ev_spec_done, hipEventDisableTiming));
-    for (auto& es : c->ev_spec_t) for (auto& e : es) RT_HIP(c, hipEventCreate(&e));
-    RT_HIP(c, hipEventCreateWithFlags(&c->ev_tail_go, hipEventDisableTiming));
-    RT_HIP(c, hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
-    for (auto& e : c->ev_resolved) RT_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    RT_HIP(c, hipEventCreateWithFlags(&c->ahead.ev_go, hipEventDisableTiming));
+    RT_HIP(c, hipEventCreateWithFlags(&c->ahead.ev_done, hipEventDisableTiming));
+    for (auto& es : c->ahead.ev_t) for (auto& e : es) RT_HIP(c, hipEventCreate(&e));
+    RT_HIP(c, hipEventCreateWithFlags(&c->tail.ev_go, hipEventDisableTiming));
+    RT_HIP(c, hipEventCreateWithFlags(&c->tail.ev, hipEventDisableTiming));
+    for (auto& e : c->tail.ev_resolved) RT_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     RT_HIP(c, hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming));
     RT_HIP(c, hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming));
     RT_HIP(c, hipEventCreateWithFlags(&c->ev_mark_bits, hipEventDisableTiming));
     c->stream = c->own_stream;
     const size_t n = local_pixels(c);
-    RT_HIP(c, hipMalloc(&c->d_vis, n * 16));
-    RT_HIP(c, hipMalloc(&c->d_g0, n * 16));
-    RT_HIP(c, hipMalloc(&c->d_g1, n * 16));
+    RT_HIP(c, hipMalloc(&c->gbuf.vis, n * 16));
+    RT_HIP(c, hipMalloc(&c->gbuf.g0, n * 16));
+    RT_HIP(c, hipMalloc(&c->gbuf.g1, n * 16));
     RT_HIP(c, hipMalloc(&c->d_accum, n * 16));
     RT_HIP(c, hipMalloc(&c->d_pixels, n * 4));
     for (int k = 0; k < 3; ++k)
@@ -442,12 +462,12 @@ int rt_create(int device, int width, int height, int row_begin, int row_end, int
         RT_HIP(c, hipMemsetAsync(c->d_rec[k], 0, n * 64, c->stream));
         RT_HIP(c, hipMemsetAsync(c->d_rad[k], 0, n * 16, c->stream));
     }
-    RT_HIP(c, hipMemsetAsync(c->d_vis, 0, n * 16, c->stream));
-    RT_HIP(c, hipMemsetAsync(c->d_g0, 0, n * 16, c->stream));
-    RT_HIP(c, hipMemsetAsync(c->d_g1, 0, n * 16, c->stream));
+    RT_HIP(c, hipMemsetAsync(c->gbuf.vis, 0, n * 16, c->stream));
+    RT_HIP(c, hipMemsetAsync(c->gbuf.g0, 0, n * 16, c->stream));
+    RT_HIP(c, hipMemsetAsync(c->gbuf.g1, 0, n * 16, c->stream));
     RT_HIP(c, hipMemsetAsync(c->d_accum, 0, n * 16, c->stream));
     RT_HIP(c, hipMemsetAsync(c->d_pixels, 0, n * 4, c->stream));
-    c->d_gset[0][0] = c->d_vis; c->d_gset[0][1] = c->d_g0; c->d_gset[0][2] = c->d_g1;
+    c->gbuf.set[0][0] = c->gbuf.vis; c->gbuf.set[0][1] = c->gbuf.g0; c->gbuf.set[0][2] = c->gbuf.g1;
     RT_HIP(c, hipMalloc(&c->d_counter, 8));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     return RT_OK;
@@ -475,22 +495,22 @@ int rt_destroy(rt_ctx* c)
     hipSetDevice(c->device);
     if (c->stream && c->stream != c->own_stream) hipStreamSynchronize(c->stream);
     if (c->own_stream) hipStreamSynchronize(c->own_stream);
-    if (c->spec_stream) hipStreamSynchronize(c->spec_stream); /* may still read the scene: before free_scene */
-    if (c->tail_stream) { hipStreamSynchronize(c->tail_stream); hipStreamDestroy(c->tail_stream); }
-    if (c->ev_tail_go) hipEventDestroy(c->ev_tail_go);
-    if (c->ev_tail) hipEventDestroy(c->ev_tail);
-    for (auto& e : c->ev_resolved) if (e) hipEventDestroy(e);
-    c->spec_valid = false;
+    if (c->ahead.stream) hipStreamSynchronize(c->ahead.stream); /* may still read the scene: before free_scene */
+    if (c->tail.stream) { hipStreamSynchronize(c->tail.stream); hipStreamDestroy(c->tail.stream); }
+    if (c->tail.ev_go) hipEventDestroy(c->tail.ev_go);
+    if (c->tail.ev) hipEventDestroy(c->tail.ev);
+    for (auto& e : c->tail.ev_resolved) if (e) hipEventDestroy(e);
+    drop_look_ahead(c);
     if (c->aux_stream) { hipStreamSynchronize(c->aux_stream); hipStreamDestroy(c->aux_stream); }
     if (c->ev_stage) hipEventDestroy(c->ev_stage);
     if (c->ev_aux) hipEventDestroy(c->ev_aux);
     if (c->ev_mark_bits) hipEventDestroy(c->ev_mark_bits);
     free_scene(c);
-    if (c->spec_stream) { hipStreamSynchronize(c->spec_stream); hipStreamDestroy(c->spec_stream); }
-    if (c->ev_spec_go) hipEventDestroy(c->ev_spec_go);
-    if (c->ev_spec_done) hipEventDestroy(c->ev_spec_done);
-    for (auto& es : c->ev_spec_t) for (auto& e : es) if (e) hipEventDestroy(e);
-    for (auto& gs : c->d_gset) for (auto& p : gs) hipFree(p);
+    if (c->ahead.stream) { hipStreamSynchronize(c->ahead.stream); hipStreamDestroy(c->ahead.stream); }
+    if (c->ahead.ev_go) hipEventDestroy(c->ahead.ev_go);
+    if (c->ahead.ev_done) hipEventDestroy(c->ahead.ev_done);
+    for (auto& es : c->ahead.ev_t) for (auto& e : es) if (e) hipEventDestroy(e);
+    for (auto& gs : c->gbuf.set) for (auto& p : gs) hipFree(p);
     hipFree(c->d_accum); hipFree(c->d_pixels);
     for (int k = 0; k < 5; ++k) { hipFree(c->d_rec[k]); hipFree(c->d_rad[k]); }
     hipFree(c->d_shaded_bits); hipFree(c->d_mark_bits);
@@ -530,9 +550,9 @@ int rt_sync(rt_ctx* c)
 {
     RT_CHECK_CTX(c);
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->spec_stream) RT_HIP(c, hipStreamSynchronize(c->spec_stream)); /* the next frame's raycast is work of this call too */
-    if (c->tail_stream) RT_HIP(c, hipStreamSynchronize(c->tail_stream));
-    c->tail_pending_main = false;
+    if (c->ahead.stream) RT_HIP(c, hipStreamSynchronize(c->ahead.stream)); /* the next frame's raycast is work of this call too */
+    if (c->tail.stream) RT_HIP(c, hipStreamSynchronize(c->tail.stream));
+    c->tail.pending_main = false;
     return RT_OK;
 }
 
@@ -1093,11 +1113,11 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     if (!triangles && count) RT_FAIL(c, RT_ERR_ARG, "null triangles");
     RT_HIP(c, hipSetDevice(c->device));
     /* every stream that may still read the old scene: the caller's / own stream, the speculative next-frame raycast
-     * (spec_stream) and the second lane */
+     * (ahead.stream) and the second lane */
     { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
     if (c->own_stream && c->own_stream != c->stream) RT_HIP(c, hipStreamSynchronize(c->own_stream));
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
-    c->spec_valid = false;
+    drop_look_ahead(c);
     c->dt_valid = false; /* rt_denoise_temporal's history belongs to the old scene */
     const auto t_build0 = std::chrono::steady_clock::now();
     free_scene(c);
@@ -1318,8 +1338,7 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
     if (c->own_stream && c->own_stream != c->stream) RT_HIP(c, hipStreamSynchronize(c->own_stream));
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
-    c->spec_valid = false;
-    c->spec_gen_valid = false;
+    drop_look_ahead(c);
     ++c->epoch;
     c->bin_stale = true;
     hipStream_t st = c->stream;
@@ -1584,25 +1603,25 @@ static bool use_tail(const rt_ctx* c, bool timed)
 /* the stream about to be used waits for the previous frame's resolve + tone_mapping (no-op unless they are in flight) */
 static int join_tail(rt_ctx* c, const Launch& L)
 {
-    if (!c->tail_pending_main) return RT_OK;
-    RT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_tail, 0));
+    if (!c->tail.pending_main) return RT_OK;
+    RT_HIP(c, hipStreamWaitEvent(L.stream, c->tail.ev, 0));
     /* the second lane of a stage waits for itself; the main stream still has to */
-    if (L.stream != c->aux_stream) c->tail_pending_main = false;
+    if (L.stream != c->aux_stream) c->tail.pending_main = false;
     return RT_OK;
 }
 /* the entry points outside the staged frame: the context's current stream joins */
 #define JOIN_TAIL(c) do { const int _jt = join_tail(c, whole_launch(c)); if (_jt != RT_OK) return _jt; } while (0)
 /* a kernel of the staged frame that WRITES reservoir buffer `phys` (and reads only what the tail reads too): it waits for the
  * tail only if that is the buffer the tail reads */
-static int join_tail_for(rt_ctx* c, const Launch& L, int phys) { return (c->tail_pending_main && phys == c->tail_phys) ? join_tail(c, L) : RT_OK; }
-/* the pipelined stage 0 (spec_stream) may still be running when a call outside the staged frame — or a frame that does not
+static int join_tail_for(rt_ctx* c, const Launch& L, int phys) { return (c->tail.pending_main && phys == c->tail.phys) ? join_tail(c, L) : RT_OK; }
+/* the pipelined stage 0 (ahead.stream) may still be running when a call outside the staged frame — or a frame that does not
  * take its results — starts to write what it reads (the history buffer, the other G-buffer set) or reads what it writes: the
  * stream about to be used waits for it first (cheap: that work is behind already). ADVICE r03. */
 static int join_spec(rt_ctx* c, const Launch& L)
 {
-    if (!c->spec_outstanding) return RT_OK;
-    RT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_spec_done, 0));
-    if (L.stream != c->aux_stream) c->spec_outstanding = false;
+    if (!c->ahead.outstanding) return RT_OK;
+    RT_HIP(c, hipStreamWaitEvent(L.stream, c->ahead.ev_done, 0));
+    if (L.stream != c->aux_stream) c->ahead.outstanding = false;
     return RT_OK;
 }
 #define JOIN_SPEC(c) do { const int _js = join_spec(c, whole_launch(c)); if (_js != RT_OK) return _js; } while (0)
@@ -1637,21 +1656,29 @@ static void launch_raycast(rt_ctx* c, const Launch& L)
     if (use_ws_primary(c, g)) k_raycast<true><<<g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), P, L.vis, L.g0, L.g1);
     else k_raycast<false><<<g, TRACE_BLOCK, 0, L.stream>>>(make_scene(c), P, L.vis, L.g0, L.g1);
 }
-/* a launch on L.stream has traced primary rays into the CURRENT G-buffer set (rt_primary_launches counts it): over all owned rows it
- * makes the set the answer for `epoch` (gbuffer_reusable); over a sub-range it leaves gbuf_traced_epoch alone — either the set was
- * the answer already and the rows got the same bytes, or it is of an older epoch, which never comes back */
-static void note_primary_launch(rt_ctx* c, const Launch& L, uint64_t epoch)
+/* The current G-buffer set has new content: its serial and its shaded bits are new, however it got there */
+enum { GBUF_TRACED = 0, GBUF_TAKEN = 1, GBUF_UPLOADED = 2 };
+static void gbuffer_written(rt_ctx* c, const Launch& L, int how)
 {
-    ++c->primary_launches;
-    if (L.row0 == c->row_begin && L.row1 == c->row_end && L.rowb1 <= L.rowb0) c->gbuf_traced_epoch = epoch;
-    if (L.stream != c->spec_stream) c->gbuf_spec_ordered = false;
+    c->gbuf.valid = c->gbuf.shaded_bits_stale = true;
+    ++c->gbuf.serial;
+    if (how == GBUF_UPLOADED) return; /* k_gbuffer_from_vis is not a trace: the caller bumps `epoch`, and no epoch here follows it */
+    c->gbuf.epoch = c->epoch;
+    /* taken: the look-ahead traced it under ahead.epoch == epoch (look_ahead_usable), all owned rows, on ahead.stream, and counted it when it was launched */
+    if (how == GBUF_TAKEN) { c->gbuf.traced_epoch = c->epoch; c->gbuf.ahead_ordered = true; return; }
+    /* a launch on L.stream has traced primary rays into the CURRENT G-buffer set (rt_primary_launches counts it): over all owned rows it
+     * makes the set the answer for `epoch` (gbuffer_reusable); over a sub-range it leaves gbuf.traced_epoch alone — either the set was
+     * the answer already and the rows got the same bytes, or it is of an older epoch, which never comes back */
+    ++c->gbuf.primary_launches;
+    if (covers_owned_rows(c, L)) c->gbuf.traced_epoch = c->epoch;
+    if (L.stream != c->ahead.stream) c->gbuf.ahead_ordered = false;
 }
 /* r13 (rt_gbuffer_reuse): stage 0 of a staged frame needs no primary rays — the current set holds what they would write. Whole-frame
  * contexts only (a strip's marks wait for the raycast's event, and r05 bounded the gain there at 0-9 % of a strip's frame); not while
  * rt_walk_stats counts (the counters of slot 0 are the raycast's). */
 static bool gbuffer_reusable(const rt_ctx* c)
 {
-    return c->gbuf_reuse && c->row_begin == 0 && c->row_end == c->H && !c->walk_on && c->has_gbuffer && c->gbuf_traced_epoch == c->epoch;
+    return c->gbuf.reuse && whole_frame(c) && !c->walk_on && c->gbuf.valid && c->gbuf.traced_epoch == c->epoch;
 }
 /* rt_raycast over the launch's rows, with everything it does to the context's state */
 static int raycast_rows(rt_ctx* c, const Launch& L)
@@ -1662,11 +1689,7 @@ static int raycast_rows(rt_ctx* c, const Launch& L)
     NEED_SCENE(c);
     launch_raycast(c, L);
     RT_HIP(c, hipGetLastError());
-    c->has_gbuffer = true;
-    ++c->gbuf_serial;
-    c->gbuf_epoch = c->epoch;
-    note_primary_launch(c, L, c->epoch);
-    c->shaded_bits_stale = true;
+    gbuffer_written(c, L, GBUF_TRACED);
     /* halo rows of the G-buffer keep the neighbours' shaded flags: they stay valid until the camera,
      * the scene or the options change (halo_flags_epoch), which is when the neighbours' G-buffers change */
     return RT_OK;
@@ -1685,7 +1708,7 @@ static bool use_next_raycast(const rt_ctx* c, bool timed)
     if (c->tune_spec >= 0) return c->tune_spec != 0;
     /* auto: strips always; whole frames too (r03: with the candidates pipelined as well a 1080p frame gains 3 %), except
      * while rt_timing brackets the kernels of a frame with events — then they run back to back on one stream */
-    return (c->row_begin != 0 || c->row_end != c->H) || !timed;
+    return !whole_frame(c) || !timed;
 }
 /* the next frame's generate_candidate(+temporal) too. Not while per-kernel timing is on (rt_timing attributes events of the
  * main stream to kernels) and not with the deferred-visibility queue (its counters live per lane of the main frame). */
@@ -1697,7 +1720,7 @@ static bool use_next_generate(const rt_ctx* c, bool timed)
 /* r05, rt_tuning key 22. auto: strips — their kernels are launches of one to three generations of wavefronts and what fills the GPU
  * is running several of them side by side (rank 4 of 8: 1080p 0.306 -> 0.287 ms, 4K 0.889 -> 0.870, profiles/r05_spec_free_ab.txt);
  * a whole frame's kernels fill the GPU alone and only take slots from each other (pipelined 1080p frame 1.277 -> 1.296 ms) */
-static bool spec_free(const rt_ctx* c) { return c->tune_spec_free < 0 ? (c->row_begin != 0 || c->row_end != c->H) : c->tune_spec_free != 0; }
+static bool spec_free(const rt_ctx* c) { return c->tune_spec_free < 0 ? !whole_frame(c) : c->tune_spec_free != 0; }
 static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis = nullptr);
 /* r05, rt_tuning key 25: raycast + generate_candidate (+ temporal merge) of a frame in ONE launch — the candidates need the primary ray
  * of their own pixel only, and two launches on a stream cost the first one's ramp-down (its last wavefront starts at 216 of 257 us).
@@ -1705,8 +1728,7 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
  * auto = whole-frame contexts (a strip's marks wait for the G-buffer alone). */
 static bool use_fused_stage0(const rt_ctx* c)
 {
-    const bool whole = c->row_begin == 0 && c->row_end == c->H;
-    const int want = c->tune_fuse_raycast < 0 ? (whole ? 1 : 0) : c->tune_fuse_raycast;
+    const int want = c->tune_fuse_raycast < 0 ? (whole_frame(c) ? 1 : 0) : c->tune_fuse_raycast;
     /* r06: also while rt_timing brackets the kernels — the events then bracket the ONE launch the headline frames run
      * (ms[1] = the empty bracket where the raycast launch would be, ms[2] = the launch; rt_stage0_one_launch says which
      * form the timed frame ran). rt_tuning 25 = 0 times the two kernels. */
@@ -1720,21 +1742,21 @@ static bool use_fused_stage0(const rt_ctx* c)
 /* the next frame's primary rays, behind everything enqueued on the main stream so far, on the stream of their own */
 static int launch_next_raycast(rt_ctx* c, int frame)
 {
-    c->spec_gen_valid = false;
-    if (!use_next_raycast(c, c->timing)) { c->spec_valid = false; return RT_OK; }
+    c->ahead.gen_valid = false;
+    if (!use_next_raycast(c, c->timing)) { drop_look_ahead(c); return RT_OK; }
     const bool next_generate = use_next_generate(c, c->timing);
     /* r13: the set the running frame reads is the next frame's too (gbuffer_reusable): the look-ahead is the candidates alone, reading
-     * set gcur; set o is neither written nor, in a steady run, ever allocated, and the take does not rotate gcur */
+     * set cur; set o is neither written nor, in a steady run, ever allocated, and the take does not rotate cur */
     const bool reuse = gbuffer_reusable(c);
-    if (reuse && !(next_generate && c->n_lights > 0)) { c->spec_valid = false; return RT_OK; } /* nothing to run ahead */
+    if (reuse && !(next_generate && c->n_lights > 0)) { drop_look_ahead(c); return RT_OK; } /* nothing to run ahead */
     const size_t n = local_pixels(c);
-    const int o = reuse ? c->gcur : (c->gcur + 1) % rt_ctx::NGSET;
+    const int o = reuse ? c->gbuf.cur : (c->gbuf.cur + 1) % rt_ctx::NGSET;
     bool fresh_set = false;
-    if (!c->d_gset[o][0])
+    if (!c->gbuf.set[o][0])
     {
-        for (int k = 0; k < 3; ++k) RT_HIP(c, hipMalloc(&c->d_gset[o][k], n * 16));
+        for (int k = 0; k < 3; ++k) RT_HIP(c, hipMalloc(&c->gbuf.set[o][k], n * 16));
         /* halo rows of g1 hold the neighbours' shaded flags (rt_halo_flags_unpack keeps every set current from here on) */
-        for (int k = 0; k < 3; ++k) RT_HIP(c, hipMemcpyAsync(c->d_gset[o][k], c->d_gset[c->gcur][k], n * 16, hipMemcpyDeviceToDevice, c->stream));
+        for (int k = 0; k < 3; ++k) RT_HIP(c, hipMemcpyAsync(c->gbuf.set[o][k], c->gbuf.set[c->gbuf.cur][k], n * 16, hipMemcpyDeviceToDevice, c->stream));
         fresh_set = true;
     }
     /* What this stage 0 needs from the main stream. If the current frame's stage 0 ran there (a cold frame, the first frames,
@@ -1744,130 +1766,112 @@ static int launch_next_raycast(rt_ctx* c, int frame)
      * tail stream are doing. (r04 waited here for the main stream, i.e. for the previous frame's passes, and for the previous
      * frame's resolve: raycast(f+2) could not start before resolve(f) had ended.) */
     /* r13: candidates that read the current set wait for the main stream also where a launch there wrote that set last */
-    if (!c->gen_taken || fresh_set || !spec_free(c) || (reuse && !c->gbuf_spec_ordered))
+    if (!c->frame.gen_taken || fresh_set || !spec_free(c) || (reuse && !c->gbuf.ahead_ordered))
     {
-        RT_HIP(c, hipEventRecord(c->ev_spec_go, c->stream));
-        RT_HIP(c, hipStreamWaitEvent(c->spec_stream, c->ev_spec_go, 0));
-        c->gbuf_spec_ordered = true; /* whatever wrote set gcur was enqueued before this point */
+        RT_HIP(c, hipEventRecord(c->ahead.ev_go, c->stream));
+        RT_HIP(c, hipStreamWaitEvent(c->ahead.stream, c->ahead.ev_go, 0));
+        c->gbuf.ahead_ordered = true; /* whatever wrote set cur was enqueued before this point */
     }
     /* the G-buffer set and the spare reservoir buffer written below: last read by the resolve before the latest one (the set of
      * frame f-2; the buffer that left the roles when frame f-1 was taken) — or earlier */
     /* With ONE resolve on record the free-running form waits for it too (that it need not rested on the main-stream
      * wait above being forced at that point — one frame of overlap, once, buys an invariant that does not depend on it). */
-    if (c->n_resolved >= 1)
-        RT_HIP(c, hipStreamWaitEvent(c->spec_stream, c->ev_resolved[(spec_free(c) && c->n_resolved >= 2) ? 1 : 0], 0));
+    if (c->tail.n_resolved >= 1)
+        RT_HIP(c, hipStreamWaitEvent(c->ahead.stream, c->tail.ev_resolved[(spec_free(c) && c->tail.n_resolved >= 2) ? 1 : 0], 0));
     /* the invariants the free-running look-ahead rests on, checked where it writes (cheap integer tests, every build): the set it
      * overwrites is not the one the running frame reads, and the candidates' buffer has no role in the running frame nor is it
      * what the tail in flight reads */
-    if (!reuse && o == c->gcur) RT_FAIL(c, RT_ERR_STATE, "look-ahead stage 0 would overwrite the running frame's G-buffer set %d", o);
-    if (next_generate && (c->spare == c->fX || c->spare == c->fY || c->spare == c->fZ || c->spare == c->quarantine ||
-                                 (spec_free(c) && c->tail_pending_main && c->spare == c->tail_phys))) /* r04's dependencies hand the tail's buffer over and wait for the latest resolve above */
-        RT_FAIL(c, RT_ERR_STATE, "look-ahead candidates' buffer %d is in use (X %d Y %d Z %d quarantine %d tail %d)", c->spare, c->fX, c->fY, c->fZ, c->quarantine, c->tail_pending_main ? c->tail_phys : -1);
+    if (!reuse && o == c->gbuf.cur) RT_FAIL(c, RT_ERR_STATE, "look-ahead stage 0 would overwrite the running frame's G-buffer set %d", o);
+    /* r04's dependencies (not spec_free) hand the tail's buffer over and wait for the latest resolve above */
+    if (next_generate && !roles_spare_free(c->frame, (spec_free(c) && c->tail.pending_main) ? c->tail.phys : -1))
+        RT_FAIL(c, RT_ERR_STATE, "look-ahead candidates' buffer %d is in use (X %d Y %d Z %d quarantine %d tail %d)", c->frame.spare, c->frame.X, c->frame.Y, c->frame.Z, c->frame.quarantine, c->tail.pending_main ? c->tail.phys : -1);
     Launch spec = whole_launch(c); /* all owned rows, on the stream of its own, into set o */
-    spec.stream = c->spec_stream; spec.vis = c->d_gset[o][0]; spec.g0 = c->d_gset[o][1]; spec.g1 = c->d_gset[o][2];
+    spec.stream = c->ahead.stream; spec.vis = c->gbuf.set[o][0]; spec.g0 = c->gbuf.set[o][1]; spec.g1 = c->gbuf.set[o][2];
     const bool one_launch = !reuse && next_generate && use_fused_stage0(c); /* the candidates' launch below traces the primary rays too */
     if (!reuse)
     {
-        if (c->timing) hipEventRecord(c->ev_spec_t[o][0], spec.stream);
+        if (c->timing) hipEventRecord(c->ahead.ev_t[o][0], spec.stream);
         if (!one_launch) launch_raycast(c, spec);
         RT_HIP(c, hipGetLastError());
-        if (c->timing) hipEventRecord(c->ev_spec_t[o][1], spec.stream);
-        c->spec_timed[o] = c->timing;
-        ++c->primary_launches; /* into set o: it becomes the current set, and gbuf_traced_epoch its epoch, at the take */
+        if (c->timing) hipEventRecord(c->ahead.ev_t[o][1], spec.stream);
+        c->ahead.timed[o] = c->timing;
+        ++c->gbuf.primary_launches; /* into set o: it becomes the current set, and gbuf.traced_epoch its epoch, at the take */
     }
     if (next_generate && c->n_lights > 0)
     {
         /* candidates (+ temporal merge) of frame + 1: G-buffer = the set just traced, history = the buffer this frame's
-         * stage 0 wrote (c->fY), output = the spare buffer; all owned rows, on the same stream behind the raycast */
-        const size_t npx = local_pixels(c);
-        if (!c->d_rec[c->spare])
+         * stage 0 wrote (c->frame.Y), output = the spare buffer; all owned rows, on the same stream behind the raycast */
+        if (!c->d_rec[c->frame.spare])
         {
-            RT_HIP(c, hipMalloc(&c->d_rec[c->spare], npx * 64));
-            RT_HIP(c, hipMalloc(&c->d_rad[c->spare], npx * 16));
-            RT_HIP(c, hipMemsetAsync(c->d_rec[c->spare], 0, npx * 64, spec.stream));
-            RT_HIP(c, hipMemsetAsync(c->d_rad[c->spare], 0, npx * 16, spec.stream));
+            RT_HIP(c, hipMalloc(&c->d_rec[c->frame.spare], n * 64));
+            RT_HIP(c, hipMalloc(&c->d_rad[c->frame.spare], n * 16));
+            RT_HIP(c, hipMemsetAsync(c->d_rec[c->frame.spare], 0, n * 64, spec.stream));
+            RT_HIP(c, hipMemsetAsync(c->d_rad[c->frame.spare], 0, n * 16, spec.stream));
         }
-        c->spec_gen_tag = next_ownv_tag(c); /* the frame that takes these candidates continues under their tag */
-        spec.tag = c->spec_gen_tag;
-        const int rc = launch_generate(c, spec, frame + 1, c->spare, c->fY, c->opt.use_temporal_resampling != 0, one_launch ? spec.vis : nullptr);
+        c->ahead.gen_tag = next_ownv_tag(c); /* the frame that takes these candidates continues under their tag */
+        spec.tag = c->ahead.gen_tag;
+        const int rc = launch_generate(c, spec, frame + 1, c->frame.spare, c->frame.Y, c->opt.use_temporal_resampling != 0, one_launch ? spec.vis : nullptr);
         if (rc != RT_OK) return rc;
-        c->spec_gen_valid = true;
-        c->spec_gen_frame = frame + 1;
-        c->spec_gen_hist = c->fY;
-        c->spec_res_epoch = c->res_epoch;
+        c->ahead.gen_valid = true;
+        c->ahead.gen_frame = frame + 1;
+        c->ahead.gen_hist = c->frame.Y;
+        c->ahead.res_epoch = c->res_epoch;
     }
-    RT_HIP(c, hipEventRecord(c->ev_spec_done, spec.stream));
-    c->spec_outstanding = true;
-    c->spec_valid = true;
-    c->spec_reuse = reuse;
-    c->spec_epoch = c->epoch;
+    RT_HIP(c, hipEventRecord(c->ahead.ev_done, spec.stream));
+    c->ahead.outstanding = true;
+    c->ahead.valid = true;
+    c->ahead.reuse = reuse;
+    c->ahead.epoch = c->epoch;
     return RT_OK;
+}
+/* what stage 0 learned: deferred = its primary rays are traced by the candidates' launch; reused (r13) = by nobody, the current G-buffer
+ * set is still the answer (gbuffer_reusable); taken = its candidates came from the look-ahead (frame.gen_taken keeps that for the later stages) */
+struct Stage0 { bool deferred = false, reused = false, taken = false; };
+/* is the look-ahead still the right one for this launch? One that read the current set (ahead.reuse) is good for as long as that set is */
+static bool look_ahead_usable(const rt_ctx* c, const Launch& L) { return covers_owned_rows(c, L) && use_next_raycast(c, L.timed) && c->ahead.valid && c->ahead.epoch == c->epoch && (!c->ahead.reuse || gbuffer_reusable(c)); }
+/* ... and its candidates: made for this frame, from the buffer that is this frame's history, and no reservoir buffer written outside since */
+static bool look_ahead_candidates_usable(const rt_ctx* c, const Launch& L, int frame) { return c->ahead.gen_valid && use_next_generate(c, L.timed) && c->ahead.gen_frame == frame && c->ahead.res_epoch == c->res_epoch && c->ahead.gen_hist == c->frame.X; }
+/* the set the look-ahead traced becomes the current one, the context's and the launch's */
+static void rotate_gbuffer_set(rt_ctx* c, Launch& L)
+{
+    c->gbuf.cur = (c->gbuf.cur + 1) % rt_ctx::NGSET;
+    L.vis = c->gbuf.vis = c->gbuf.set[c->gbuf.cur][0]; L.g0 = c->gbuf.g0 = c->gbuf.set[c->gbuf.cur][1]; L.g1 = c->gbuf.g1 = c->gbuf.set[c->gbuf.cur][2];
 }
 /* stage 0's raycast over all owned rows: the G-buffer traced beside the previous frame if it is still the right one */
 /* L: the stage's launch; a take moves it to the taken G-buffer set and, with the candidates, to their tag */
-/* r13: *reused = the stage launches no primary rays at all, the current set is still the answer (gbuffer_reusable) */
-static int raycast_or_take(rt_ctx* c, Launch& L, bool whole, int frame, bool may_defer, bool* deferred, bool* reused)
+static int raycast_or_take(rt_ctx* c, Launch& L, int frame, bool may_defer, Stage0& got)
 {
-    c->timed_spec_set = -1;
-    c->gen_taken = false;
-    /* a look-ahead that read the current set (spec_reuse) is good for as long as that set is */
-    if (whole && use_next_raycast(c, L.timed) && c->spec_valid && c->spec_epoch == c->epoch && (!c->spec_reuse || gbuffer_reusable(c)))
+    c->ahead.timed_set = -1;
+    c->frame.gen_taken = false;
+    if (look_ahead_usable(c, L))
     {
-        const bool traced = !c->spec_reuse; /* the look-ahead traced set gcur + 1; otherwise only its candidates are taken */
-        if (traced)
+        const bool traced = !c->ahead.reuse; /* the look-ahead traced set cur + 1; otherwise only its candidates are taken */
+        if (traced) rotate_gbuffer_set(c, L);
+        else got.reused = true;
+        RT_HIP(c, hipStreamWaitEvent(L.stream, c->ahead.ev_done, 0));
+        c->ahead.outstanding = false;
+        if (look_ahead_candidates_usable(c, L, frame))
         {
-            c->gcur = (c->gcur + 1) % rt_ctx::NGSET;
-            L.vis = c->d_vis = c->d_gset[c->gcur][0]; L.g0 = c->d_g0 = c->d_gset[c->gcur][1]; L.g1 = c->d_g1 = c->d_gset[c->gcur][2];
+            roles_take(c->frame, c->opt.spatial_resampling_passes, spec_free(c));
+            c->frame.gen_taken = got.taken = true;
+            c->frame.tag = c->ahead.gen_tag; /* own-visibility flags of the candidates were written under this tag */
+            L.tag = c->frame.tag;
         }
-        else *reused = true;
-        RT_HIP(c, hipStreamWaitEvent(L.stream, c->ev_spec_done, 0));
-        c->spec_outstanding = false;
-        if (c->spec_gen_valid && use_next_generate(c, L.timed) && c->spec_gen_frame == frame && c->spec_res_epoch == c->res_epoch &&
-            c->spec_gen_hist == c->fX)
-        {
-            /* this frame's candidates are in the spare buffer already: it becomes Y (stage 0's generate is skipped;
-             * rt_frame_stage_output / _end see the swapped roles). Of the two buffers the passes ping-pong through, the one the
-             * previous frame's resolve may still be reading on the tail stream (its final buffer) becomes the new spare — the
-             * pipelined stage 0 after next waits for the tail anyway — and pass 0 writes the other one, so that no spatial pass
-             * of this frame has to wait for the previous frame's resolve. With no spatial pass, logical RES_1 keeps its buffer
-             * (the reference resolves a buffer that frame did not write: its content must carry over). */
-            const int r0 = c->fY, r1 = c->fZ;
-            const int prev_final = c->res_map[c->f_final == RT_RES_1 ? RT_RES_1 : RT_RES_0];
-            c->fY = c->spare;
-            int freed = r0;
-            if (c->opt.spatial_resampling_passes >= 1 && prev_final == r1) { c->fZ = r0; freed = r1; }
-            /* r05: the freed buffer (the previous frame's final one, or one nobody reads) waits a frame in quarantine; the look-ahead
-             * candidates of the NEXT frame go to the buffer freed a frame earlier. RT_TUNING 22 = 0: the freed one at once (r04). */
-            if (spec_free(c)) { c->spare = c->quarantine; c->quarantine = freed; }
-            else c->spare = freed;
-            c->f_in = c->fY; c->f_out = c->fZ;
-            c->gen_taken = true;
-            c->frame_tag = c->spec_gen_tag; /* own-visibility flags of the candidates were written under this tag */
-            L.tag = c->frame_tag;
-        }
-        c->spec_gen_valid = false;
-        c->spec_valid = false;
+        drop_look_ahead(c);
         if (!traced) return RT_OK; /* the same set, its serial and its shaded bits; the candidates carry its serial (launch_generate) */
-        c->has_gbuffer = true;
-        ++c->gbuf_serial;
-        c->gbuf_epoch = c->spec_epoch; /* == c->epoch (checked above) */
-        c->gbuf_traced_epoch = c->spec_epoch; /* all owned rows, on spec_stream (counted when it was launched) */
-        c->gbuf_spec_ordered = true;
-        if (c->gen_taken) c->rec_gserial[c->fY] = c->gbuf_serial; /* the candidates were made from this G-buffer set */
-        c->shaded_bits_stale = true;
-        if (c->spec_timed[c->gcur]) c->timed_spec_set = c->gcur;
+        gbuffer_written(c, L, GBUF_TAKEN);
+        if (got.taken) c->rec_gserial[c->frame.Y] = c->gbuf.serial; /* the candidates were made from this G-buffer set */
+        if (c->ahead.timed[c->gbuf.cur]) c->ahead.timed_set = c->gbuf.cur;
         return RT_OK;
     }
-    c->spec_valid = false;
-    c->spec_gen_valid = false;
+    drop_look_ahead(c);
     if (gbuffer_reusable(c))
     {
         /* nothing is written: the tail may go on reading the set; a look-ahead that was not taken may still be running on the
          * history and the spare buffer */
         const int rc = join_spec(c, L);
-        if (rc != RT_OK) return rc;
-        *reused = true;
-        return RT_OK;
+        got.reused = rc == RT_OK;
+        return rc;
     }
     if (may_defer)
     {
@@ -1875,12 +1879,8 @@ static int raycast_or_take(rt_ctx* c, Launch& L, bool whole, int frame, bool may
         int rc = join_tail(c, L);
         if (rc == RT_OK) rc = join_spec(c, L);
         if (rc != RT_OK) return rc;
-        c->has_gbuffer = true;
-        ++c->gbuf_serial;
-        c->gbuf_epoch = c->epoch;
-        note_primary_launch(c, L, c->epoch); /* the candidates' launch of this stage, all owned rows (may_defer) */
-        c->shaded_bits_stale = true;
-        *deferred = true;
+        gbuffer_written(c, L, GBUF_TRACED); /* the candidates' launch of this stage, all owned rows (may_defer) */
+        got.deferred = true;
         return RT_OK;
     }
     return raycast_rows(c, L);
@@ -1894,7 +1894,7 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
     const FrameParams P = make_params(c, L, frame, 0, K_GENERATE);
     const bool sh = c->opt.use_shadowed_target_function;
     float4 *orec = c->d_rec[dst_phys], *orad = c->d_rad[dst_phys];
-    c->rec_gserial[dst_phys] = c->gbuf_serial;
+    c->rec_gserial[dst_phys] = c->gbuf.serial;
     const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
     const int g = trace_grid(c, L);
 #ifdef RT_EXPERIMENTS
@@ -1956,8 +1956,8 @@ int rt_generate_candidate(rt_ctx* c, int frame, int dst)
     NEED_SCENE(c);
     NEED_RES(c, dst);
     ++c->res_epoch; /* a reservoir buffer changes outside the staged frame: a pipelined stage 0 is stale */
-    if (!c->has_gbuffer) RT_FAIL(c, RT_ERR_STATE, "no G-buffer: call rt_raycast or upload RT_BUF_VISIBILITY first");
-    return launch_generate(c, whole_launch(c), frame, c->res_map[dst], 0, false);
+    if (!c->gbuf.valid) RT_FAIL(c, RT_ERR_STATE, "no G-buffer: call rt_raycast or upload RT_BUF_VISIBILITY first");
+    return launch_generate(c, whole_launch(c), frame, c->frame.res_map[dst], 0, false);
 }
 
 int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
@@ -1973,11 +1973,11 @@ int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
     const SceneView S = make_scene(c);
     const Launch L = whole_launch(c);
     const FrameParams P = make_params(c, L, frame, 0);
-    const int pp = c->res_map[prev], pi = c->res_map[inout];
+    const int pp = c->frame.res_map[prev], pi = c->frame.res_map[inout];
     if (c->opt.use_shadowed_target_function)
-        k_temporal<true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+        k_temporal<true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
     else
-        k_temporal<false><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->d_g0, c->d_g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+        k_temporal<false><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -1994,7 +1994,7 @@ int rt_save_temporal_reservoir(rt_ctx* c, int src, int dst)
     if (src == dst) return RT_OK;
     const size_t off = (size_t)(c->row_begin - c->lrow0) * c->W;
     const size_t n = (size_t)(c->row_end - c->row_begin) * c->W;
-    const int ps = c->res_map[src], pd = c->res_map[dst];
+    const int ps = c->frame.res_map[src], pd = c->frame.res_map[dst];
     c->rec_gserial[pd] = c->rec_gserial[ps];
     RT_HIP(c, hipMemcpyAsync(c->d_rec[pd] + 4 * off, c->d_rec[ps] + 4 * off, n * 64, hipMemcpyDeviceToDevice, c->stream));
     RT_HIP(c, hipMemcpyAsync(c->d_rad[pd] + off, c->d_rad[ps] + off, n * 16, hipMemcpyDeviceToDevice, c->stream));
@@ -2023,18 +2023,18 @@ static bool use_lds_spatial(const rt_ctx* c)
     return (c->tune_spatial_variant == 1 || c->tune_spatial_variant == 3) && c->opt.use_spatial_resampling && !c->opt.use_shadowed_target_function &&
            !c->spatial_unbiased &&
            halo_rows_needed(c->opt) <= SPL_HALO && c->opt.spatial_resampling_sample_count <= 5 &&
-           c->row_begin == 0 && c->row_end == c->H;
+           whole_frame(c);
 }
 /* shaded bit per pixel of all local rows, rebuilt on the launch's stream when the G-buffer or the halo flags changed.
  * rt_frame_stage does this right behind the raycast, on the main stream, so that a stage's two lanes only read it. */
 static int refresh_shaded_bits(rt_ctx* c, const Launch& L)
 {
-    if (!c->shaded_bits_stale || !c->has_gbuffer || !use_lds_spatial(c)) return RT_OK;
+    if (!c->gbuf.shaded_bits_stale || !c->gbuf.valid || !use_lds_spatial(c)) return RT_OK;
     const int words = (c->W + 31) / 32;
     if (!c->d_shaded_bits) RT_HIP(c, hipMalloc(&c->d_shaded_bits, (size_t)c->lrows * words * 4));
     k_shaded_bitmap<<<dim3((c->W + 255) / 256, c->lrows), 256, 0, L.stream>>>(c->W, c->lrows, L.g1, c->d_shaded_bits);
     RT_HIP(c, hipGetLastError());
-    c->shaded_bits_stale = false;
+    c->gbuf.shaded_bits_stale = false;
     return RT_OK;
 }
 /* register budget of the gather kernel when rt_tuning key 9 is -1. xnack-any code (until late r02) wanted 4 wavefronts per
@@ -2053,8 +2053,7 @@ static bool use_fused_final(const rt_ctx* c)
 #ifndef RT_EXPERIMENTS
     return false; /* k_spatial_resolve: measured slower (profiles/r05_fused_tail_ab.txt), experiments build only */
 #endif
-    const bool whole = c->row_begin == 0 && c->row_end == c->H;
-    const int want = c->tune_fuse_final < 0 ? (whole ? RT_FUSE_FINAL_AUTO : 0) : c->tune_fuse_final;
+    const int want = c->tune_fuse_final < 0 ? (whole_frame(c) ? RT_FUSE_FINAL_AUTO : 0) : c->tune_fuse_final;
     return want != 0 && !c->opt.use_shadowed_target_function && c->opt.use_spatial_resampling && !c->spatial_unbiased && c->tune_spatial_variant == 2 && !c->tune_stream &&
            c->opt.spatial_resampling_passes >= 1;
 }
@@ -2082,7 +2081,7 @@ static int launch_spatial(rt_ctx* c, const Launch& L, int frame, int pass, int i
     const FrameParams P = make_params(c, L, frame, pass, K_SPATIAL);
     const bool lds_variant = use_lds_spatial(c);
     (void)lds_variant; /* the product build has no LDS-staged form */
-    c->rec_gserial[out_phys] = c->gbuf_serial;
+    c->rec_gserial[out_phys] = c->gbuf.serial;
     if (unbiased_applies(c))
         /* one kernel whatever keys 8 and 23 say: the A/B forms restate the reference's pass */
         k_spatial_unbiased<<<trace_grid(c, L), TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys]);
@@ -2124,7 +2123,7 @@ static int launch_spatial(rt_ctx* c, const Launch& L, int frame, int pass, int i
         if (fused) { if (store) RT_SPR(true, true); else RT_SPR(true, false); }
         else { if (store) RT_SPR(false, true); else RT_SPR(false, false); }
 #undef RT_SPR
-        c->final_fused = true;
+        c->frame.final_fused = true;
     }
 #endif
 #ifdef RT_EXPERIMENTS
@@ -2178,7 +2177,7 @@ int rt_spatial_resampling(rt_ctx* c, int frame, int pass, int in, int out)
     if (in == out) RT_FAIL(c, RT_ERR_ARG, "in and out must differ");
     c->last_frame = frame;
     c->fuse = HaloFuse{};
-    if (c->rec_gserial[c->res_map[in]] != c->gbuf_serial)
+    if (c->rec_gserial[c->frame.res_map[in]] != c->gbuf.serial)
     {
         /* the G-buffer changed since `in` was written: its neighbour test must see the current shaded flags (frame_kernels.h) */
         /* own rows always; a strip's halo rows only where the neighbour's flags in g1 are of the current epoch (rt_halo_flags_unpack
@@ -2187,11 +2186,11 @@ int rt_spatial_resampling(rt_ctx* c, int frame, int pass, int in, int out)
         const int last_row = (c->lrow0 + c->lrows > c->row_end && c->halo_flags_epoch[1] != c->epoch) ? c->row_end : c->lrow0 + c->lrows;
         const size_t off = (size_t)(first_row - c->lrow0) * c->W;
         const int n = (last_row - first_row) * c->W;
-        k_refresh_shaded<<<(n + 255) / 256, 256, 0, c->stream>>>(n, c->d_g1 + off, c->d_rec[c->res_map[in]] + 4 * off);
+        k_refresh_shaded<<<(n + 255) / 256, 256, 0, c->stream>>>(n, c->gbuf.g1 + off, c->d_rec[c->frame.res_map[in]] + 4 * off);
         RT_HIP(c, hipGetLastError());
-        c->rec_gserial[c->res_map[in]] = c->gbuf_serial;
+        c->rec_gserial[c->frame.res_map[in]] = c->gbuf.serial;
     }
-    return launch_spatial(c, whole_launch(c), frame, pass, c->res_map[in], c->res_map[out]);
+    return launch_spatial(c, whole_launch(c), frame, pass, c->frame.res_map[in], c->frame.res_map[out]);
 }
 
 /* pixels: the staged frame maps each pixel in the resolve kernel itself (rt_tuning key 20, default on); NULL = resolve alone */
@@ -2219,7 +2218,7 @@ int rt_resolve(rt_ctx* c, int res)
     JOIN_TAIL(c);
     NEED_SCENE(c);
     NEED_RES(c, res);
-    return launch_resolve(c, whole_launch(c), c->res_map[res]);
+    return launch_resolve(c, whole_launch(c), c->frame.res_map[res]);
 }
 
 static int launch_tone_mapping(rt_ctx* c, const Launch& L)
@@ -2323,7 +2322,7 @@ int rt_path_trace_rays(rt_ctx* c, uint64_t* rays)
 /* what rt_denoise and rt_denoise_temporal share: the checks, the buffers, the guide pass and one a-trous level */
 static int denoise_begin(rt_ctx* c, const rt_denoise_params* params, rt_denoise_params& d, const char* name)
 {
-    if (c->row_begin != 0 || c->row_end != c->H)
+    if (!whole_frame(c))
         RT_FAIL(c, RT_ERR_UNSUPPORTED, "%s is for whole-frame contexts (rows [%d,%d) of %d)", name, c->row_begin, c->row_end, c->H);
     NEED_SCENE(c);
     d = rt_denoise_params{5, 4.0f, 1.0f, 7, 3};
@@ -2555,28 +2554,18 @@ int rt_frame_stage_begin(rt_ctx* c, int frame, int stage, int clear_first)
     const int passes = c->opt.spatial_resampling_passes;
     if (stage == 0)
     {
-        /* X = history, Y = candidates(+temporal) -> next history, Z = spatial ping-pong partner */
-        c->fX = c->res_map[RT_RES_TEMPORAL]; c->fY = c->res_map[RT_RES_0]; c->fZ = c->res_map[RT_RES_1];
-        c->f_in = c->fY; c->f_out = c->fZ;
-        c->f_clear = clear_first != 0;
-        c->f_stage = 0;
-        c->gen_taken = false;
-        c->final_fused = false;
-        c->f_frame = frame;
-        c->frame_tag = next_ownv_tag(c);
+        roles_begin(c->frame);
+        c->frame.clear = clear_first != 0;
+        c->frame.stage = 0;
+        c->frame.gen_taken = false;
+        c->frame.final_fused = false;
+        c->frame.number = frame;
+        c->frame.tag = next_ownv_tag(c);
         return RT_OK;
     }
-    if (stage != c->f_stage) RT_FAIL(c, RT_ERR_STATE, "rt_frame_stage: expected stage %d, got %d", c->f_stage, stage);
+    if (stage != c->frame.stage) RT_FAIL(c, RT_ERR_STATE, "rt_frame_stage: expected stage %d, got %d", c->frame.stage, stage);
     if (stage > passes + 1) RT_FAIL(c, RT_ERR_ARG, "bad stage %d", stage);
-    /* buffer roles are a pure function of the stage index, so a repeated _begin (retry after a failed
-     * _run) cannot swap the ping-pong pair twice: pass k reads what pass k-1 wrote (Y for k = 0) and
-     * writes Z for even k, X for odd k */
-    if (stage >= 1 && stage <= passes)
-    {
-        const int k = stage - 1;
-        c->f_in = (k == 0) ? c->fY : ((k & 1) ? c->fZ : c->fX);
-        c->f_out = (k & 1) ? c->fX : c->fZ;
-    }
+    if (stage >= 1 && stage <= passes) roles_pass(c->frame, stage - 1); /* a pure function of the stage index: a repeated _begin is harmless */
     return RT_OK;
 }
 
@@ -2612,7 +2601,7 @@ int rt_frame_stage_run_ranges(rt_ctx* c, int frame, int stage, int part, int n, 
 static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part, int row0, int row1, int rowb0, int rowb1)
 {
     NEED_SCENE(c);
-    if (stage != c->f_stage) RT_FAIL(c, RT_ERR_STATE, "rt_frame_stage_run: expected stage %d, got %d", c->f_stage, stage);
+    if (stage != c->frame.stage) RT_FAIL(c, RT_ERR_STATE, "rt_frame_stage_run: expected stage %d, got %d", c->frame.stage, stage);
     if (row0 < c->row_begin) row0 = c->row_begin;
     if (row1 > c->row_end) row1 = c->row_end;
     if (rowb0 < c->row_begin) rowb0 = c->row_begin;
@@ -2621,44 +2610,43 @@ static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part,
     if (row0 >= row1) { row0 = rowb0; row1 = rowb1; rowb0 = rowb1 = 0; }
     if (row0 >= row1) return RT_OK;
     L.row0 = row0; L.row1 = row1; L.rowb0 = rowb0; L.rowb1 = rowb1;
-    L.tag = c->frame_tag; /* launches of the staged frame write / trust own-visibility flags under the frame's tag */
+    L.tag = c->frame.tag; /* launches of the staged frame write / trust own-visibility flags under the frame's tag */
     const int passes = c->opt.spatial_resampling_passes;
-    const bool whole = row0 == c->row_begin && row1 == c->row_end && rowb0 >= rowb1;
+    const bool whole = covers_owned_rows(c, L);
     const bool T = L.timed && whole;
     auto mark = [&](int i) { if (T && i <= 8) hipEventRecord(c->ev[i], L.stream); };
     int rc = RT_OK;
     if (stage == 0)
     {
         mark(0);
-        if (part != 2 && c->f_clear) rc = clear_rows(c, L);
+        if (part != 2 && c->frame.clear) rc = clear_rows(c, L);
         mark(1);
-        bool deferred = false; /* the primary rays are traced by the candidates' launch */
-        bool reused = false;   /* r13: by nobody, the current G-buffer set is still the answer */
+        Stage0 got;
         const bool may_defer = part == 0 && whole && use_fused_stage0(c);
-        if (part != 2 && rc == RT_OK) rc = raycast_or_take(c, L, whole, frame, may_defer, &deferred, &reused);
+        if (part != 2 && rc == RT_OK) rc = raycast_or_take(c, L, frame, may_defer, got);
         /* a reuse frame answers what a tracing frame would under the same tuning: its stage 0 on this stream is the candidates' launch
          * either way, and the bracket where the raycast launch would be is empty either way */
-        if (part != 2) c->stage0_one_launch = deferred || (reused && !c->gen_taken && may_defer);
-        if (part != 2 && rc == RT_OK && row0 == c->row_begin && row1 == c->row_end && !deferred) rc = refresh_shaded_bits(c, L);
+        if (part != 2) c->frame.one_launch = got.deferred || (got.reused && !c->frame.gen_taken && may_defer);
+        if (part != 2 && rc == RT_OK && whole && !got.deferred) rc = refresh_shaded_bits(c, L);
         mark(2);
-        if (part != 1 && rc == RT_OK && !c->gen_taken)
+        if (part != 1 && rc == RT_OK && !c->frame.gen_taken)
         {
-            rc = join_tail_for(c, L, c->fY); /* this frame's candidates may go where the previous frame's resolve still reads */
-            if (rc == RT_OK) rc = launch_generate(c, L, frame, c->fY, c->fX, c->opt.use_temporal_resampling != 0, deferred ? L.vis : nullptr);
+            rc = join_tail_for(c, L, c->frame.Y); /* this frame's candidates may go where the previous frame's resolve still reads */
+            if (rc == RT_OK) rc = launch_generate(c, L, frame, c->frame.Y, c->frame.X, c->opt.use_temporal_resampling != 0, got.deferred ? L.vis : nullptr);
         }
-        if (deferred && rc == RT_OK) rc = refresh_shaded_bits(c, L);
+        if (got.deferred && rc == RT_OK) rc = refresh_shaded_bits(c, L);
         mark(3);
     }
     else if (stage <= passes)
     {
         const int k = stage - 1;
-        rc = join_tail_for(c, L, c->f_out); /* the pass's output buffer can be the one the previous frame's resolve reads */
+        rc = join_tail_for(c, L, c->frame.out); /* the pass's output buffer can be the one the previous frame's resolve reads */
         if (rc == RT_OK && k == passes - 1 && use_fused_final(c))
         {
             rc = join_tail(c, L); /* the kernel writes the accumulation buffer and the pixels the previous frame's tail writes */
-            if (rc == RT_OK) rc = launch_spatial(c, L, frame, k, c->f_in, c->f_out, true);
+            if (rc == RT_OK) rc = launch_spatial(c, L, frame, k, c->frame.in, c->frame.out, true);
         }
-        else if (rc == RT_OK) rc = launch_spatial(c, L, frame, k, c->f_in, c->f_out);
+        else if (rc == RT_OK) rc = launch_spatial(c, L, frame, k, c->frame.in, c->frame.out);
         if (k < 3) mark(4 + k);
     }
     else
@@ -2669,8 +2657,8 @@ static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part,
          * left there. Logical RT_RES_1 (physical Z) holds exactly that content here, frame by frame
          * (rt_frame_stage_end keeps the logical names on the reference's buffers), so the result is the
          * reference's, stale data included. */
-        const int final_phys = passes > 0 ? c->f_out : c->fZ;
-        if (c->final_fused)
+        const int final_phys = roles_final_phys(c->frame, passes);
+        if (c->frame.final_fused)
         {
             /* the last pass has shaded (and, key 20, tone-mapped) these rows already */
             mark(7);
@@ -2684,9 +2672,9 @@ static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part,
         {
             /* resolve + tone_mapping on the tail stream, behind everything enqueued so far (and behind the previous
              * frame's tail: same stream); the main stream does not wait for them */
-            RT_HIP(c, hipEventRecord(c->ev_tail_go, L.stream));
-            RT_HIP(c, hipStreamWaitEvent(c->tail_stream, c->ev_tail_go, 0));
-            R.stream = c->tail_stream;
+            RT_HIP(c, hipEventRecord(c->tail.ev_go, L.stream));
+            RT_HIP(c, hipStreamWaitEvent(c->tail.stream, c->tail.ev_go, 0));
+            R.stream = c->tail.stream;
         }
         else rc = join_tail(c, L);
         /* tone_mapping reads the pixel's own accumulation value only (common/kernels/common.cu:30-74): k_resolve maps what it
@@ -2698,11 +2686,11 @@ static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part,
         mark(8);
         if (tail && rc == RT_OK)
         {
-            RT_HIP(c, hipEventRecord(c->ev_tail, c->tail_stream));
-            c->tail_pending_main = true;
-            c->tail_phys = final_phys;
+            RT_HIP(c, hipEventRecord(c->tail.ev, c->tail.stream));
+            c->tail.pending_main = true;
+            c->tail.phys = final_phys;
         }
-        c->resolve_on_tail = tail;
+        c->tail.resolve_on = tail;
     }
     return rc;
 }
@@ -2738,7 +2726,7 @@ int rt_frame_stage_run(rt_ctx* c, int frame, int stage, int row0, int row1)
 int rt_frame_stage_end(rt_ctx* c, int stage)
 {
     RT_CHECK_CTX(c);
-    if (stage != c->f_stage) RT_FAIL(c, RT_ERR_STATE, "rt_frame_stage_end: expected stage %d, got %d", c->f_stage, stage);
+    if (stage != c->frame.stage) RT_FAIL(c, RT_ERR_STATE, "rt_frame_stage_end: expected stage %d, got %d", c->frame.stage, stage);
     if (c->aux_used)
     {
         RT_HIP(c, hipEventRecord(c->ev_aux, c->aux_stream));
@@ -2747,17 +2735,17 @@ int rt_frame_stage_end(rt_ctx* c, int stage)
     }
     const int passes = c->opt.spatial_resampling_passes;
     c->fuse = HaloFuse{};
-    if (stage == 0) { const int rc = launch_next_raycast(c, c->f_frame); if (rc != RT_OK) return rc; }
-    if (stage <= passes) { c->f_stage = stage + 1; return RT_OK; }
+    if (stage == 0) { const int rc = launch_next_raycast(c, c->frame.number); if (rc != RT_OK) return rc; }
+    if (stage <= passes) { c->frame.stage = stage + 1; return RT_OK; }
     {
         /* behind this frame's resolve (all its parts: the second lane has been joined above), on the stream it ran on: the
          * look-ahead stage 0 waits for the one before the latest */
-        std::swap(c->ev_resolved[0], c->ev_resolved[1]);
-        RT_HIP(c, hipEventRecord(c->ev_resolved[0], c->resolve_on_tail ? c->tail_stream : c->stream));
-        if (c->n_resolved < 2) ++c->n_resolved;
-        c->resolve_on_tail = false;
+        std::swap(c->tail.ev_resolved[0], c->tail.ev_resolved[1]);
+        RT_HIP(c, hipEventRecord(c->tail.ev_resolved[0], c->tail.resolve_on ? c->tail.stream : c->stream));
+        if (c->tail.n_resolved < 2) ++c->tail.n_resolved;
+        c->tail.resolve_on = false;
     }
-    const int X = c->fX, Y = c->fY, Z = c->fZ;
+    const int X = c->frame.X, Y = c->frame.Y;
     if (passes < 2)
     {
         /* logical RT_RES_0 still equals the post-temporal reservoirs: materialise the copy the
@@ -2768,22 +2756,13 @@ int rt_frame_stage_end(rt_ctx* c, int stage)
         RT_HIP(c, hipMemcpyAsync(c->d_rec[X], c->d_rec[Y], n * 64, hipMemcpyDeviceToDevice, c->stream));
         RT_HIP(c, hipMemcpyAsync(c->d_rad[X], c->d_rad[Y], n * 16, hipMemcpyDeviceToDevice, c->stream));
     }
-    const int final_phys = passes > 0 ? c->f_out : Z;
-    /* new logical names: TEMPORAL = Y; RES_1 = Z; RES_0 = X (pass-1 output / copy) */
-    c->res_map[RT_RES_TEMPORAL] = Y;
-    c->res_map[RT_RES_0] = X;
-    c->res_map[RT_RES_1] = Z;
-    c->f_final = (final_phys == Z) ? RT_RES_1 : RT_RES_0;
-    c->f_stage = 0;
+    roles_end(c->frame, passes);
+    c->frame.stage = 0;
     c->last_valid = c->timing;
     return RT_OK;
 }
 
-/* The frame as a sequence of stages, so that a strip context can exchange halos in between:
- *   stage 0            [clear] raycast, generate_candidate(+temporal) into the rotating buffers
- *   stage 1..passes    spatial pass stage-1      (its input buffer must have valid halos)
- *   stage passes+1     resolve, tone_mapping, buffer renaming
- * rt_frame runs them back to back. */
+/* one stage of the frame (the sequence of stages: see rt_frame_stage_begin); rt_frame runs them back to back */
 int rt_frame_stage(rt_ctx* c, int frame, int stage, int clear_first)
 {
     RT_CHECK_CTX(c);
@@ -2797,9 +2776,9 @@ int rt_frame_stage(rt_ctx* c, int frame, int stage, int clear_first)
 int rt_frame_stage_input(rt_ctx* c, int stage, int* phys)
 {
     RT_CHECK_CTX(c);
-    if (!phys || stage < 1 || stage != c->f_stage) RT_FAIL(c, RT_ERR_STATE, "no such pending stage %d", stage);
+    if (!phys || stage < 1 || stage != c->frame.stage) RT_FAIL(c, RT_ERR_STATE, "no such pending stage %d", stage);
     const int k = stage - 1;
-    *phys = (k == 0) ? c->f_in : c->f_out;
+    *phys = (k == 0) ? c->frame.in : c->frame.out;
     return RT_OK;
 }
 /* physical buffer the CURRENT stage (after its _begin) writes: stage 0 -> the candidates(+temporal)
@@ -2807,8 +2786,8 @@ int rt_frame_stage_input(rt_ctx* c, int stage, int* phys)
 int rt_frame_stage_output(rt_ctx* c, int stage, int* phys)
 {
     RT_CHECK_CTX(c);
-    if (!phys || stage != c->f_stage) RT_FAIL(c, RT_ERR_STATE, "stage %d is not running", stage);
-    *phys = (stage == 0) ? c->fY : c->f_out;
+    if (!phys || stage != c->frame.stage) RT_FAIL(c, RT_ERR_STATE, "stage %d is not running", stage);
+    *phys = (stage == 0) ? c->frame.Y : c->frame.out;
     return RT_OK;
 }
 
@@ -2816,7 +2795,7 @@ int rt_frame(rt_ctx* c, int frame, int clear_first, int* final_res)
 {
     RT_CHECK_CTX(c);
     NEED_SCENE(c);
-    if (c->row_begin != 0 || c->row_end != c->H)
+    if (!whole_frame(c))
         RT_FAIL(c, RT_ERR_STATE, "rt_frame is for single-strip contexts; strips run rt_frame_stage and exchange halos");
     const int passes = c->opt.spatial_resampling_passes;
     for (int st = 0; st <= passes + 1; ++st)
@@ -2824,7 +2803,7 @@ int rt_frame(rt_ctx* c, int frame, int clear_first, int* final_res)
         const int rc = rt_frame_stage(c, frame, st, clear_first);
         if (rc != RT_OK) return rc;
     }
-    if (final_res) *final_res = c->f_final;
+    if (final_res) *final_res = c->frame.final_res;
     return RT_OK;
 }
 
@@ -2838,10 +2817,10 @@ int rt_timing(rt_ctx* c, float ms[9])
     RT_HIP(c, hipEventElapsedTime(&ms[8], c->ev[0], c->ev[8]));
     /* the frame's primary rays were traced beside the previous frame (rt_tuning key 14): the duration of that launch,
      * which ran concurrently with other kernels and is not part of ms[8] */
-    if (c->timed_spec_set >= 0)
+    if (c->ahead.timed_set >= 0)
     {
-        RT_HIP(c, hipEventSynchronize(c->ev_spec_t[c->timed_spec_set][1]));
-        RT_HIP(c, hipEventElapsedTime(&ms[1], c->ev_spec_t[c->timed_spec_set][0], c->ev_spec_t[c->timed_spec_set][1]));
+        RT_HIP(c, hipEventSynchronize(c->ahead.ev_t[c->ahead.timed_set][1]));
+        RT_HIP(c, hipEventElapsedTime(&ms[1], c->ahead.ev_t[c->ahead.timed_set][0], c->ahead.ev_t[c->ahead.timed_set][1]));
     }
     return RT_OK;
 }
@@ -2850,7 +2829,7 @@ int rt_stage0_one_launch(rt_ctx* c, int* one_launch)
 {
     RT_CHECK_CTX(c);
     if (!one_launch) return RT_ERR_ARG;
-    *one_launch = c->stage0_one_launch ? 1 : 0;
+    *one_launch = c->frame.one_launch ? 1 : 0;
     return RT_OK;
 }
 
@@ -2859,11 +2838,11 @@ int rt_stage0_one_launch(rt_ctx* c, int* one_launch)
 int rt_gbuffer_reuse(rt_ctx* c, int on)
 {
     RT_CHECK_CTX(c);
-    if (on && (c->row_begin != 0 || c->row_end != c->H))
+    if (on && !whole_frame(c))
         RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_gbuffer_reuse: strip contexts trace their primary rays every frame");
-    c->gbuf_reuse = on != 0;
+    c->gbuf.reuse = on != 0;
     /* a look-ahead enqueued under the other setting is not taken: the next frame runs its own stage 0 */
-    c->spec_valid = false; c->spec_gen_valid = false;
+    drop_look_ahead(c);
     return RT_OK;
 }
 /* The spatial passes with the 1/Z normalisation (k_spatial_unbiased). Changes results, so not an rt_tuning key either; counts as an option
@@ -2871,7 +2850,7 @@ int rt_gbuffer_reuse(rt_ctx* c, int on)
 int rt_spatial_unbiased(rt_ctx* c, int on)
 {
     RT_CHECK_CTX(c);
-    if (c->row_begin != 0 || c->row_end != c->H)
+    if (!whole_frame(c))
         RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_spatial_unbiased: strip contexts hold no traced G-buffer in their halo rows");
     c->spatial_unbiased = on != 0;
     ++c->epoch;
@@ -2888,7 +2867,7 @@ int rt_primary_launches(rt_ctx* c, uint64_t* n)
 {
     RT_CHECK_CTX(c);
     if (!n) return RT_ERR_ARG;
-    *n = c->primary_launches;
+    *n = c->gbuf.primary_launches;
     return RT_OK;
 }
 
@@ -2910,7 +2889,7 @@ int rt_download(rt_ctx* c, int buf, void* dst, size_t bytes)
     {
         case RT_BUF_VISIBILITY:
             if (bytes != n * 16) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 16);
-            RT_HIP(c, hipMemcpyAsync(dst, c->d_vis, bytes, hipMemcpyDeviceToHost, c->stream));
+            RT_HIP(c, hipMemcpyAsync(dst, c->gbuf.vis, bytes, hipMemcpyDeviceToHost, c->stream));
             break;
         case RT_BUF_ACCUMULATION:
             if (bytes != n * 16) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 16);
@@ -2936,7 +2915,7 @@ int rt_download(rt_ctx* c, int buf, void* dst, size_t bytes)
         case RT_BUF_RES_TEMPORAL:
         {
             if (bytes != n * 76) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 76);
-            const int phys = c->res_map[buf - RT_BUF_RES_0];
+            const int phys = c->frame.res_map[buf - RT_BUF_RES_0];
             int rc = ensure_stage(c, n * 76);
             if (rc != RT_OK) return rc;
             k_res_to_ref<<<(int)((n + 255) / 256), 256, 0, c->stream>>>((int)n, c->d_rec[phys], c->d_rad[phys], (uint32_t*)c->d_stage);
@@ -2963,14 +2942,12 @@ int rt_upload(rt_ctx* c, int buf, const void* src, size_t bytes)
         {
             if (bytes != n * 16) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 16);
             NEED_SCENE(c);
-            RT_HIP(c, hipMemcpyAsync(c->d_vis, src, bytes, hipMemcpyHostToDevice, c->stream));
+            RT_HIP(c, hipMemcpyAsync(c->gbuf.vis, src, bytes, hipMemcpyHostToDevice, c->stream));
             FrameParams P = make_params(c, whole_launch(c), 0, 0);
             P.row0 = c->lrow0; P.row1 = c->lrow0 + c->lrows; /* all rows held, halos included */
-            k_gbuffer_from_vis<<<tile_grid(c->W, c->lrows), BLOCK, 0, c->stream>>>(make_scene(c), P, c->d_vis, c->d_g0, c->d_g1);
+            k_gbuffer_from_vis<<<tile_grid(c->W, c->lrows), BLOCK, 0, c->stream>>>(make_scene(c), P, c->gbuf.vis, c->gbuf.g0, c->gbuf.g1);
             RT_HIP(c, hipGetLastError());
-            c->has_gbuffer = true;
-            ++c->gbuf_serial;
-            c->shaded_bits_stale = true;
+            gbuffer_written(c, whole_launch(c), GBUF_UPLOADED);
             ++c->epoch;
             break;
         }
@@ -2983,10 +2960,10 @@ int rt_upload(rt_ctx* c, int buf, const void* src, size_t bytes)
         case RT_BUF_RES_TEMPORAL:
         {
             if (bytes != n * 76) RT_FAIL(c, RT_ERR_ARG, "size mismatch: want %zu", n * 76);
-            if (!c->has_gbuffer) RT_FAIL(c, RT_ERR_STATE, "upload RT_BUF_VISIBILITY (or rt_raycast) before reservoirs");
+            if (!c->gbuf.valid) RT_FAIL(c, RT_ERR_STATE, "upload RT_BUF_VISIBILITY (or rt_raycast) before reservoirs");
             ++c->res_epoch;
-            const int phys = c->res_map[buf - RT_BUF_RES_0];
-            c->rec_gserial[phys] = c->gbuf_serial;
+            const int phys = c->frame.res_map[buf - RT_BUF_RES_0];
+            c->rec_gserial[phys] = c->gbuf.serial;
             /* the record keeps M in 30 bits: refuse what it cannot hold rather than truncate */
             for (size_t i = 0; i < n; ++i)
             {
@@ -2996,7 +2973,7 @@ int rt_upload(rt_ctx* c, int buf, const void* src, size_t bytes)
             int rc = ensure_stage(c, n * 76);
             if (rc != RT_OK) return rc;
             RT_HIP(c, hipMemcpyAsync(c->d_stage, src, bytes, hipMemcpyHostToDevice, c->stream));
-            k_res_from_ref<<<(int)((n + 255) / 256), 256, 0, c->stream>>>((int)n, (const uint32_t*)c->d_stage, c->d_g1, c->d_rec[phys], c->d_rad[phys]);
+            k_res_from_ref<<<(int)((n + 255) / 256), 256, 0, c->stream>>>((int)n, (const uint32_t*)c->d_stage, c->gbuf.g1, c->d_rec[phys], c->d_rad[phys]);
             RT_HIP(c, hipGetLastError());
             break;
         }
@@ -3019,7 +2996,7 @@ static int halo_range(rt_ctx* c, int row0, int n_rows)
 static int halo_phys(rt_ctx* c, int res)
 {
     if (res >= RT_RES_PHYS && res < RT_RES_PHYS + 5 && c->d_rec[res - RT_RES_PHYS]) return res - RT_RES_PHYS;
-    if (res >= 0 && res <= 2) return c->res_map[res];
+    if (res >= 0 && res <= 2) return c->frame.res_map[res];
     return -1;
 }
 int rt_halo_pack(rt_ctx* c, int res, int row0, int n_rows, void* device_dst)
@@ -3072,7 +3049,7 @@ int rt_halo_flags_pack(rt_ctx* c, int row0, int n_rows, void* device_dst)
     int rc = halo_range(c, row0, n_rows);
     if (rc != RT_OK) return rc;
     const int n = n_rows * c->W;
-    k_halo_flags<true><<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_g1, (size_t)(row0 - c->lrow0) * c->W, n, (uint8_t*)device_dst);
+    k_halo_flags<true><<<(n + 255) / 256, 256, 0, c->stream>>>(c->gbuf.g1, (size_t)(row0 - c->lrow0) * c->W, n, (uint8_t*)device_dst);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -3084,10 +3061,10 @@ int rt_halo_flags_unpack(rt_ctx* c, int row0, int n_rows, const void* device_src
     if (row0 < c->row_end && row0 + n_rows > c->row_begin) RT_FAIL(c, RT_ERR_ARG, "flags may only be unpacked into halo rows");
     const int n = n_rows * c->W;
     for (int set = 0; set < rt_ctx::NGSET; ++set)
-        if (c->d_gset[set][2])
-            k_halo_flags<false><<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_gset[set][2], (size_t)(row0 - c->lrow0) * c->W, n, (uint8_t*)const_cast<void*>(device_src));
+        if (c->gbuf.set[set][2])
+            k_halo_flags<false><<<(n + 255) / 256, 256, 0, c->stream>>>(c->gbuf.set[set][2], (size_t)(row0 - c->lrow0) * c->W, n, (uint8_t*)const_cast<void*>(device_src));
     RT_HIP(c, hipGetLastError());
-    c->shaded_bits_stale = true; /* the LDS-staged spatial pass reads these rows' bits too */
+    c->gbuf.shaded_bits_stale = true; /* the LDS-staged spatial pass reads these rows' bits too */
     c->mark_bits_epoch = 0;      /* and the halo marks' cached rows */
     if (row0 == c->lrow0 && row0 + n_rows == c->row_begin) c->halo_flags_epoch[0] = c->epoch;
     if (row0 == c->row_end && row0 + n_rows == c->lrow0 + c->lrows) c->halo_flags_epoch[1] = c->epoch;
@@ -3098,7 +3075,7 @@ int rt_halo_flags_unpack(rt_ctx* c, int row0, int n_rows, const void* device_src
 int rt_halo_mark_sides(rt_ctx* c, int frame, int pass, int n_pass, void* bitmaps_side0, void* bitmaps_side1)
 {
     RT_CHECK_CTX(c);
-    if (!c->has_gbuffer) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
+    if (!c->gbuf.valid) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
     if (n_pass <= 0 || (!bitmaps_side0 && !bitmaps_side1)) return RT_OK;
     HaloRegions R = {};
     R.quick = c->tune_mark_quick;
@@ -3146,19 +3123,19 @@ int rt_halo_mark_sides(rt_ctx* c, int frame, int pass, int n_pass, void* bitmaps
          * from a G-buffer traced under it and kept (r04 rebuilt them in front of every mark: 13 us alone, 84 us beside a 4K
          * strip's raycast). A G-buffer of another epoch (marks before the first raycast after a change) is not cached.
          * Ordering: a mark that finds the cache valid may run on another stream than the mark that built it — ev_mark_bits. */
-        const bool cacheable = c->gbuf_epoch == c->epoch;
+        const bool cacheable = c->gbuf.epoch == c->epoch;
         if (!(cacheable && c->mark_bits_epoch == c->epoch) || !c->tune_mark_cache)
         {
             if (c->mark_bits_event_valid) RT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_mark_bits, 0)); /* earlier readers / writer */
-            k_shaded_bitmap<<<dim3((c->W + 255) / 256, c->lrows), 256, 0, c->stream>>>(c->W, c->lrows, c->d_g1, c->d_mark_bits);
+            k_shaded_bitmap<<<dim3((c->W + 255) / 256, c->lrows), 256, 0, c->stream>>>(c->W, c->lrows, c->gbuf.g1, c->d_mark_bits);
             RT_HIP(c, hipGetLastError());
             c->mark_bits_epoch = cacheable ? c->epoch : 0;
             c->mark_bits_rebuilt = true;
         }
         else RT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_mark_bits, 0)); /* the build (and every mark since) is in front of this one */
-        k_halo_mark<true><<<dim3(grid, c->tune_mark_split ? n_pass : 1), BLOCK, 0, c->stream>>>(P, c->d_g1, c->d_mark_bits, R, pass, n_pass);
+        k_halo_mark<true><<<dim3(grid, c->tune_mark_split ? n_pass : 1), BLOCK, 0, c->stream>>>(P, c->gbuf.g1, c->d_mark_bits, R, pass, n_pass);
     }
-    else k_halo_mark<false><<<dim3(grid, c->tune_mark_split ? n_pass : 1), BLOCK, 0, c->stream>>>(P, c->d_g1, nullptr, R, pass, n_pass);
+    else k_halo_mark<false><<<dim3(grid, c->tune_mark_split ? n_pass : 1), BLOCK, 0, c->stream>>>(P, c->gbuf.g1, nullptr, R, pass, n_pass);
     RT_HIP(c, hipGetLastError());
     if (window)
     {
@@ -3226,7 +3203,7 @@ int rt_halo_fuse_set(rt_ctx* c, const rt_halo_fuse* f)
     RT_CHECK_CTX(c);
     c->fuse = HaloFuse{};
     if (!f) return RT_OK;
-    if (c->f_stage < 1 || c->f_stage > c->opt.spatial_resampling_passes) RT_FAIL(c, RT_ERR_STATE, "rt_halo_fuse_set outside a spatial stage");
+    if (c->frame.stage < 1 || c->frame.stage > c->opt.spatial_resampling_passes) RT_FAIL(c, RT_ERR_STATE, "rt_halo_fuse_set outside a spatial stage");
     if (use_lds_spatial(c)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "the LDS-staged spatial variant reads halo rows, not lists");
     HaloFuse F = {};
     F.rows = c->halo;
@@ -3290,7 +3267,7 @@ int rt_side_stream(rt_ctx* c, int which, void** hip_stream)
 {
     RT_CHECK_CTX(c);
     if (!hip_stream || which != 0) RT_FAIL(c, RT_ERR_ARG, "which: 0 = tail stream");
-    *hip_stream = (void*)c->tail_stream;
+    *hip_stream = (void*)c->tail.stream;
     return RT_OK;
 }
 /* n <= 8 device-to-device copies in one launch on the current stream */
@@ -3403,9 +3380,9 @@ int rt_lane(rt_ctx* c, int second)
 int rt_ray_count(rt_ctx* c, uint64_t* rays, uint64_t* shaded_pixels)
 {
     RT_CHECK_CTX(c);
-    if (!c->has_gbuffer) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
+    if (!c->gbuf.valid) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
     RT_HIP(c, hipMemsetAsync(c->d_counter, 0, 8, c->stream));
-    k_count_shaded<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), 0, 0), c->d_g1, c->d_counter);
+    k_count_shaded<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), 0, 0), c->gbuf.g1, c->d_counter);
     RT_HIP(c, hipGetLastError());
     unsigned long long shaded = 0;
     RT_HIP(c, hipMemcpyAsync(&shaded, c->d_counter, 8, hipMemcpyDeviceToHost, c->stream));
@@ -3431,8 +3408,8 @@ int rt_ray_count(rt_ctx* c, uint64_t* rays, uint64_t* shaded_pixels)
             {
                 /* halo rows: G-buffer flags if the neighbours' were exchanged for this frame, else the records */
                 const bool g1_ok = (c->row_begin == c->lrow0 || c->halo_flags_epoch[0] == c->epoch) && (c->row_end == c->lrow0 + c->lrows || c->halo_flags_epoch[1] == c->epoch);
-                k_spatial_bytes<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), c->last_frame, k), c->d_g1,
-                                                                        c->d_rec[c->res_map[RT_RES_TEMPORAL]], d, g1_ok);
+                k_spatial_bytes<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), c->last_frame, k), c->gbuf.g1,
+                                                                        c->d_rec[c->frame.res_map[RT_RES_TEMPORAL]], d, g1_ok);
             }
             RT_HIP(c, hipGetLastError());
             unsigned long long h[3] = {0, 0, 0};
@@ -3462,7 +3439,7 @@ int rt_walk_stats_enable(rt_ctx* c, int on)
     }
     c->walk_on = on != 0;
     /* a pipelined stage 0 enqueued before the switch carries the other setting: the next frame runs its own */
-    c->spec_valid = false; c->spec_gen_valid = false;
+    drop_look_ahead(c);
     return RT_OK;
 }
 #ifdef RT_EXPERIMENTS
@@ -3491,7 +3468,7 @@ int rt_exp_wave_clock(rt_ctx* c, int kernel, int pass, uint64_t* out, size_t n_w
     }
     if (c->d_wave_clock) RT_HIP(c, hipMemset(c->d_wave_clock, 0, c->wave_clock_words * 8));
     c->wave_clock_kernel = kernel; c->wave_clock_pass = pass;
-    c->spec_valid = false; c->spec_gen_valid = false;
+    drop_look_ahead(c);
     return RT_OK;
 }
 #endif
@@ -3506,7 +3483,7 @@ int rt_exp_tile_perm(rt_ctx* c, int kernel, const uint32_t* perm, size_t n)
     int rc = rt_sync(c);
     if (rc != RT_OK) return rc;
     if (c->d_tile_perm[kernel]) { hipFree(c->d_tile_perm[kernel]); c->d_tile_perm[kernel] = nullptr; c->tile_perm_n[kernel] = 0; }
-    c->spec_valid = false; c->spec_gen_valid = false;
+    drop_look_ahead(c);
     if (n == 0) return RT_OK;
     if (!perm || n != (size_t)trace_grid(c, whole_launch(c))) RT_FAIL(c, RT_ERR_ARG, "the permutation must cover the kernel's %d workgroups", trace_grid(c, whole_launch(c)));
     std::vector<uint8_t> seen(n, 0);
@@ -3536,12 +3513,12 @@ int rt_row_shaded(rt_ctx* c, uint32_t* counts)
 {
     RT_CHECK_CTX(c);
     if (!counts) return RT_ERR_ARG;
-    if (!c->has_gbuffer) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
+    if (!c->gbuf.valid) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
     const int rows = c->row_end - c->row_begin;
     uint32_t* d = nullptr;
     RT_HIP(c, hipMalloc(&d, (size_t)rows * 4));
     RT_HIP(c, hipMemsetAsync(d, 0, (size_t)rows * 4, c->stream));
-    k_row_shaded<<<rows, BLOCK, 0, c->stream>>>(c->W, c->row_begin - c->lrow0, c->d_g1, d);
+    k_row_shaded<<<rows, BLOCK, 0, c->stream>>>(c->W, c->row_begin - c->lrow0, c->gbuf.g1, d);
     RT_HIP(c, hipGetLastError());
     RT_HIP(c, hipMemcpyAsync(counts, d, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
@@ -3568,11 +3545,11 @@ int rt_spatial_bytes(rt_ctx* c, int frame, int pass, int in, uint64_t* bytes, ui
 {
     RT_CHECK_CTX(c);
     NEED_RES(c, in);
-    if (!c->has_gbuffer) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
+    if (!c->gbuf.valid) RT_FAIL(c, RT_ERR_STATE, "no G-buffer yet");
     unsigned long long* d = nullptr;
     RT_HIP(c, hipMalloc(&d, 24));
     RT_HIP(c, hipMemsetAsync(d, 0, 24, c->stream));
-    k_spatial_bytes<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), frame, pass), c->d_g1, c->d_rec[c->res_map[in]], d);
+    k_spatial_bytes<<<launch_grid(c, whole_launch(c)), BLOCK, 0, c->stream>>>(make_params(c, whole_launch(c), frame, pass), c->gbuf.g1, c->d_rec[c->frame.res_map[in]], d);
     RT_HIP(c, hipGetLastError());
     unsigned long long h[2] = {0, 0};
     RT_HIP(c, hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, c->stream));
@@ -3725,7 +3702,7 @@ static constexpr TuneRow TUNING[] = {
     TUNE_ROW(BVH_BUILDER, bvh_builder, within<0, 3>, within<3, 3>, nullptr), /* before rt_scene_set; [exp] 0 LBVH, 1 host SAH, 2 PLOC + host top */
     TUNE_ROW(PT_WAVEFRONT, pt_wavefront, within<0, 2>, any_value, nullptr),
     TUNE_ROW(BVH_BFS_RECORDS, bvh_bfs_records, within<0, INT_MAX>, any_value, nullptr), /* before rt_scene_set */
-    TUNE_ROW(SPATIAL_VARIANT, tune_spatial_variant, within<0, 4>, within<2, 2>, [](rt_ctx* c) { c->shaded_bits_stale = true; }), /* [exp] gather, LDS-staged bits, software-pipelined, one-wavefront workgroups */
+    TUNE_ROW(SPATIAL_VARIANT, tune_spatial_variant, within<0, 4>, within<2, 2>, [](rt_ctx* c) { c->gbuf.shaded_bits_stale = true; }), /* [exp] gather, LDS-staged bits, software-pipelined, one-wavefront workgroups */
     TUNE_ROW(SPATIAL_WAVES, tune_spatial_waves, [](int v) { return v == 0 || v == -1 || (v >= 4 && v <= 6); },
              [](int v) { return v == -1 || v == RT_SPATIAL_GATHER_AUTO_WAVES; }, nullptr), /* [exp] the other register budgets of the pass */
     TUNE_ROW(PLOC_RADIUS, ploc_radius, within<1, 256>, no_value, nullptr), /* before rt_scene_set; [exp] builder 2 */
@@ -3733,7 +3710,7 @@ static constexpr TuneRow TUNING[] = {
     TUNE_ROW(RIS_PIPE, tune_ris_pipe, within<0, 1>, within<0, 0>, nullptr),   /* [exp] pipelined RIS loop form */
     TUNE_ROW(WS, tune_ws, within<-1, 1>, any_value, nullptr),
     TUNE_ROW(SPEC, tune_spec, within<-1, 2>, any_value,
-             [](rt_ctx* c) { if (!use_next_raycast(c, c->timing)) c->spec_valid = false; if (!use_next_generate(c, c->timing)) c->spec_gen_valid = false; }),
+             [](rt_ctx* c) { if (!use_next_raycast(c, c->timing)) c->ahead.valid = false; if (!use_next_generate(c, c->timing)) c->ahead.gen_valid = false; }),
     TUNE_ROW(STREAM, tune_stream, within<0, 1>, within<0, 0>, nullptr), /* [exp] resolve as a stream */
     TUNE_ROW(WS_PRIMARY, tune_ws_primary, within<-1, 2>, [](int v) { return v != 2; }, nullptr), /* [exp] 2 = four lanes per primary ray */
     TUNE_ROW(TAIL, tune_tail, within<-1, 1>, any_value, nullptr),
@@ -3741,7 +3718,7 @@ static constexpr TuneRow TUNING[] = {
     TUNE_ROW(MARK_WINDOW, tune_mark_window, within<0, 1>, any_value, nullptr),
     TUNE_ROW(FUSE_TONEMAP, tune_fuse_tonemap, within<0, 1>, any_value, nullptr),
     TUNE_ROW(MARK_CACHE, tune_mark_cache, within<0, 1>, any_value, [](rt_ctx* c) { c->mark_bits_epoch = 0; }),
-    TUNE_ROW(SPEC_FREE, tune_spec_free, within<-1, 1>, any_value, [](rt_ctx* c) { c->spec_valid = false; c->spec_gen_valid = false; }),
+    TUNE_ROW(SPEC_FREE, tune_spec_free, within<-1, 1>, any_value, drop_look_ahead),
     TUNE_ROW(FUSE_FINAL, tune_fuse_final, within<-1, 2>, within<INT_MIN, 0>, nullptr), /* [exp] last pass + resolve in one kernel */
     TUNE_ROW(HALF_RAYCAST, tune_half_raycast, within<0, 1>, within<0, 0>, nullptr), /* [exp] half-density raycast with helper lanes */
     TUNE_ROW(FUSE_RAYCAST, tune_fuse_raycast, within<-1, 1>, any_value, nullptr),
