@@ -11,7 +11,8 @@
  *   closest_ws          the same for closest hits (primary rays of strips)
  *   closest_quad (r06)  [experiments library] four lanes per ray, one child box each: measured slower (profiles/r06_quad_walk_ab.txt)
  * All of them run the reference's exact intersect_ray_triangle (common/core.hpp:91-136) at the leaves; boxes are rounded
- * outward and the slab tests carry a margin, so the tree only prunes.
+ * outward, leaf boxes are padded for the intersector's own rounding and the slab test carries a margin (bvh_cull.h has the
+ * argument), so the tree only prunes.
  *
  * Result contract (the pinned definition of raytrace()): the hit is the one a brute-force loop over ALL
  * triangles reports: smallest t in [tmin,tmax], ties -> highest triangle index (examples/04_ao/04_ao.cu:8-29).
@@ -24,6 +25,7 @@
  */
 #pragma once
 #include "rt_device.h"
+#include "bvh_cull.h"
 
 namespace rt
 {
@@ -212,9 +214,7 @@ constexpr int WIDE_LDS_STACK = RT_WIDE_LDS_STACK;
 #endif
 constexpr int WIDE_OVF_STACK = RT_WIDE_TOTAL_STACK - RT_WIDE_LDS_STACK; /* total 64 >= 3 * wide height + 1 (checked at build) */
 constexpr uint32_t WIDE_LEAF_BIT = 0x80000000u;
-/* slab test margin: [tn, tf] is accepted iff max(tn, tmin) <= min(tf, best) * PAD. PAD >= (1 + 4e-7) / (1 - 4e-7), the margins
- * r01-r03 put on both ends (tn * (1 - 4e-7) <= tf * (1 + 4e-7)): whatever that test kept this one keeps (tmin, best >= 0) */
-constexpr float WIDE_SLAB_PAD = 1.0f + 0x1p-20f;
+/* slab test: bvh_cull.h::wide_accept, the one copy every walk below calls; its header holds the error argument */
 #ifndef RT_WIDE_STRIDE
 #define RT_WIDE_STRIDE 3 /* float4 per wide record in HBM: 3 = packed 48 B, 4 = 64-B slots (a record never straddles a line) */
 #endif
@@ -228,44 +228,6 @@ static_assert(WIDE_STRIDE == 3 || WIDE_STRIDE == 4, "wide record stride");
  * work-sharing shadow-ray walk (occluded_ws: hit flags, thief/victim matching) */
 constexpr int WIDE_LDS_ROWS = WIDE_LDS_STACK + 2;
 #define WIDE_LDS_WORDS (WIDE_LDS_ROWS * BLOCK_THREADS)
-
-RT_DEV float wide_byte(uint32_t w, int k) { return (float)((w >> (8 * k)) & 0xffu); }
-
-/* Quantisation of one inner record, shared by every writer of the records (bvh_build_host.h::collapse_wide,
- * bvh_build_device.h::k_collapse_level, bvh_refit.h::k_refit_level). wide_quant_scale: per axis the power-of-two step
- * whose 255 steps cover the node box [lo, hi], exponent clamped to the normal range; returns ex | ey << 8 | ez << 16.
- * wide_quant_child: child k's byte bounds in q (q[a] = lo bytes, q[3 + a] = hi bytes), rounded outward so that the
- * box the traversal decodes in binary32, lo + q * scale, contains the child box. */
-RT_HD uint32_t wide_quant_scale(const float lo[3], const float hi[3], float scale[3])
-{
-    uint32_t ebits = 0;
-    for (int a = 0; a < 3; ++a)
-    {
-        const float ext = fmaxf(hi[a] - lo[a], 1e-30f);
-        int e;
-        frexpf(ext / 255.0f, &e); /* ext/255 = m * 2^e, m in [0.5,1) => 2^e >= ext/255 */
-        int biased = e + 127;
-        if (biased < 1) biased = 1;
-        if (biased > 254) biased = 254;
-        ebits |= (uint32_t)biased << (8 * a);
-        scale[a] = ldexpf(1.0f, biased - 127);
-    }
-    return ebits;
-}
-RT_HD void wide_quant_child(const float lo[3], const float scale[3], const float clo[3], const float chi[3], int k, uint32_t q[6])
-{
-    for (int a = 0; a < 3; ++a)
-    {
-        int ql = (int)floorf((clo[a] - lo[a]) / scale[a]);
-        int qh = (int)ceilf((chi[a] - lo[a]) / scale[a]);
-        while (ql > 0 && lo[a] + (float)ql * scale[a] > clo[a]) --ql;
-        while (qh < 255 && lo[a] + (float)qh * scale[a] < chi[a]) ++qh;
-        ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
-        qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
-        q[a] |= (uint32_t)ql << (8 * k);
-        q[3 + a] |= (uint32_t)qh << (8 * k);
-    }
-}
 
 /* Leaf tests are DEFERRED: a lane that reaches a leaf parks it (two slots) and keeps walking inner
  * records; the wave runs the triangle test only when the parked leaves number at least
@@ -380,11 +342,10 @@ RT_DEV bool trace_wide(const WideView& bvh, uint32_t* __restrict__ lds_stack, f3
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
             const uint32_t nx = px ? lx : hx, ny = py ? ly : hy, nz = pz ? lz : hz;
             const uint32_t fx = px ? hx : lx, fy = py ? hy : ly, fz = pz ? hz : lz;
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
-                        sz = as_float(((e >> 16) & 0xffu) << 23);
             /* t(q) = (origin + q*scale - ro) * inv = A + q*B : one FMA per plane */
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            float tnk[4];
+            bool hk[4];
+            wide_accept<4>(q0.x, q0.y, q0.z, e, nx, ny, nz, fx, fy, fz, ro, inv, tmin, best, tnk, hk);
             float td[4];
             uint32_t ce[4];
             int nhit = 0;
@@ -392,14 +353,8 @@ RT_DEV bool trace_wide(const WideView& bvh, uint32_t* __restrict__ lds_stack, f3
             for (int k = 0; k < 4; ++k)
             {
                 const uint32_t m = (meta >> (8 * k)) & 0xffu;
-                float tn = fmaxf(fmaxf(__builtin_fmaf(wide_byte(nx, k), Bx, Ax), __builtin_fmaf(wide_byte(ny, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(nz, k), Bz, Az));
-                float tf = fminf(fminf(__builtin_fmaf(wide_byte(fx, k), Bx, Ax), __builtin_fmaf(wide_byte(fy, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(fz, k), Bz, Az));
-                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
-                tn = fmaxf(tn, tmin);
-                tf = fminf(tf, best) * WIDE_SLAB_PAD;
-                const bool h = (m != 0u) && (tn <= tf);
+                const float tn = tnk[k];
+                const bool h = hk[k] && m != 0u;
                 td[k] = h ? tn : 3.0e38f;
                 ce[k] = (base + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
                 nhit += h ? 1 : 0;
@@ -674,24 +629,16 @@ RT_DEV bool occluded_ws(const WideView& bvh, uint32_t* __restrict__ lds_generic,
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
             const uint32_t nx = px ? lx : hx, ny = py ? ly : hy, nz = pz ? lz : hz;
             const uint32_t fx = px ? hx : lx, fy = py ? hy : ly, fz = pz ? hz : lz;
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
-                        sz = as_float(((e >> 16) & 0xffu) << 23);
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            float tnk[4];
+            bool hk[4];
+            wide_accept<4>(q0.x, q0.y, q0.z, e, nx, ny, nz, fx, fy, fz, ro, inv, tmin, tmax, tnk, hk);
             bool h[4];
             uint32_t ce[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
             {
                 const uint32_t m = (meta >> (8 * k)) & 0xffu;
-                float tn = fmaxf(fmaxf(__builtin_fmaf(wide_byte(nx, k), Bx, Ax), __builtin_fmaf(wide_byte(ny, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(nz, k), Bz, Az));
-                float tf = fminf(fminf(__builtin_fmaf(wide_byte(fx, k), Bx, Ax), __builtin_fmaf(wide_byte(fy, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(fz, k), Bz, Az));
-                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
-                tn = fmaxf(tn, tmin);
-                tf = fminf(tf, tmax) * WIDE_SLAB_PAD;
-                h[k] = (m != 0u) && (tn <= tf);
+                h[k] = hk[k] && m != 0u;
                 ce[k] = (cbase + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
             }
             if (h[0] || h[1] || h[2] || h[3])
@@ -854,10 +801,9 @@ RT_DEV bool closest_ws(const WideView& bvh, const float4* __restrict__ tv, uint3
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
             const uint32_t nx = px ? lx : hx, ny = py ? ly : hy, nz = pz ? lz : hz;
             const uint32_t fx = px ? hx : lx, fy = py ? hy : ly, fz = pz ? hz : lz;
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
-                        sz = as_float(((e >> 16) & 0xffu) << 23);
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            float tnk[4];
+            bool hk[4];
+            wide_accept<4>(q0.x, q0.y, q0.z, e, nx, ny, nz, fx, fy, fz, ro, inv, tmin, best, tnk, hk);
             float td[4];
             uint32_t ce[4];
             int nhit = 0;
@@ -865,14 +811,8 @@ RT_DEV bool closest_ws(const WideView& bvh, const float4* __restrict__ tv, uint3
             for (int k = 0; k < 4; ++k)
             {
                 const uint32_t m = (meta >> (8 * k)) & 0xffu;
-                float tn = fmaxf(fmaxf(__builtin_fmaf(wide_byte(nx, k), Bx, Ax), __builtin_fmaf(wide_byte(ny, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(nz, k), Bz, Az));
-                float tf = fminf(fminf(__builtin_fmaf(wide_byte(fx, k), Bx, Ax), __builtin_fmaf(wide_byte(fy, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(fz, k), Bz, Az));
-                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
-                tn = fmaxf(tn, tmin);
-                tf = fminf(tf, best) * WIDE_SLAB_PAD;
-                const bool h = (m != 0u) && (tn <= tf);
+                const float tn = tnk[k];
+                const bool h = hk[k] && m != 0u;
                 td[k] = h ? tn : 3.0e38f;
                 ce[k] = (cbase + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
                 nhit += h ? 1 : 0;
@@ -1013,17 +953,12 @@ RT_DEV bool closest_quad(const WideView& bvh, const float4* __restrict__ tv, uin
             const uint32_t cbase = as_uint(q1f.x), meta = as_uint(q1f.y);
             const uint32_t lx = as_uint(q1f.z), ly = as_uint(q1f.w), lz = as_uint(q2f.x);
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
-            const float nxq = (float)(((px ? lx : hx) >> sh) & 0xffu), nyq = (float)(((py ? ly : hy) >> sh) & 0xffu), nzq = (float)(((pz ? lz : hz) >> sh) & 0xffu);
-            const float fxq = (float)(((px ? hx : lx) >> sh) & 0xffu), fyq = (float)(((py ? hy : ly) >> sh) & 0xffu), fzq = (float)(((pz ? hz : lz) >> sh) & 0xffu);
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23), sz = as_float(((e >> 16) & 0xffu) << 23);
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
             const uint32_t m = (meta >> sh) & 0xffu;
-            float tn = fmaxf(fmaxf(__builtin_fmaf(nxq, Bx, Ax), __builtin_fmaf(nyq, By, Ay)), __builtin_fmaf(nzq, Bz, Az));
-            float tf = fminf(fminf(__builtin_fmaf(fxq, Bx, Ax), __builtin_fmaf(fyq, By, Ay)), __builtin_fmaf(fzq, Bz, Az));
-            tn = fmaxf(tn, tmin);
-            tf = fminf(tf, best) * WIDE_SLAB_PAD; /* the same conservative test as trace_wide */
-            const bool h = (m != 0u) && (tn <= tf);
+            float tn;
+            bool h; /* this lane's child: the same conservative test as trace_wide */
+            wide_accept<1>(q0.x, q0.y, q0.z, e, (px ? lx : hx) >> sh, (py ? ly : hy) >> sh, (pz ? lz : hz) >> sh, (px ? hx : lx) >> sh, (py ? hy : ly) >> sh,
+                           (pz ? hz : lz) >> sh, ro, inv, tmin, best, &tn, &h);
+            h = h && m != 0u;
             child = cbase + (uint32_t)k;
             park = h && m == 2u;
             if (h && m != 2u) tnv = tn;
@@ -1254,24 +1189,16 @@ RT_DEV void occluded_stream(const WideView& bvh, uint32_t* __restrict__ lds_gene
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
             const uint32_t nx = px ? lx : hx, ny = py ? ly : hy, nz = pz ? lz : hz;
             const uint32_t fx = px ? hx : lx, fy = py ? hy : ly, fz = pz ? hz : lz;
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
-                        sz = as_float(((e >> 16) & 0xffu) << 23);
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            float tnk[4];
+            bool hk[4];
+            wide_accept<4>(q0.x, q0.y, q0.z, e, nx, ny, nz, fx, fy, fz, ro, inv, tmin, tmax, tnk, hk);
             bool h[4];
             uint32_t ce[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
             {
                 const uint32_t m = (meta >> (8 * k)) & 0xffu;
-                float tn = fmaxf(fmaxf(__builtin_fmaf(wide_byte(nx, k), Bx, Ax), __builtin_fmaf(wide_byte(ny, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(nz, k), Bz, Az));
-                float tf = fminf(fminf(__builtin_fmaf(wide_byte(fx, k), Bx, Ax), __builtin_fmaf(wide_byte(fy, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(fz, k), Bz, Az));
-                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
-                tn = fmaxf(tn, tmin);
-                tf = fminf(tf, tmax) * WIDE_SLAB_PAD;
-                h[k] = (m != 0u) && (tn <= tf);
+                h[k] = hk[k] && m != 0u;
                 ce[k] = (cbase + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
             }
             if (h[0] || h[1] || h[2] || h[3])
@@ -1477,24 +1404,16 @@ RT_DEV uint32_t occluded_walk_plain(const WideView& bvh, uint32_t* __restrict__ 
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
             const uint32_t nx = px ? lx : hx, ny = py ? ly : hy, nz = pz ? lz : hz;
             const uint32_t fx = px ? hx : lx, fy = py ? hy : ly, fz = pz ? hz : lz;
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
-                        sz = as_float(((e >> 16) & 0xffu) << 23);
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            float tnk[4];
+            bool hk[4];
+            wide_accept<4>(q0.x, q0.y, q0.z, e, nx, ny, nz, fx, fy, fz, ro, inv, tmin, tmax, tnk, hk);
             bool h[4];
             uint32_t ce[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
             {
                 const uint32_t m = (meta >> (8 * k)) & 0xffu;
-                float tn = fmaxf(fmaxf(__builtin_fmaf(wide_byte(nx, k), Bx, Ax), __builtin_fmaf(wide_byte(ny, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(nz, k), Bz, Az));
-                float tf = fminf(fminf(__builtin_fmaf(wide_byte(fx, k), Bx, Ax), __builtin_fmaf(wide_byte(fy, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(fz, k), Bz, Az));
-                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
-                tn = fmaxf(tn, tmin);
-                tf = fminf(tf, tmax) * WIDE_SLAB_PAD;
-                h[k] = (m != 0u) && (tn <= tf);
+                h[k] = hk[k] && m != 0u;
                 ce[k] = (base + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
             }
             if (h[0] || h[1] || h[2] || h[3])
@@ -1607,24 +1526,16 @@ RT_DEV int occluded_count_refill(const WideView& bvh, uint32_t* __restrict__ lds
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
             const uint32_t nx = px ? lx : hx, ny = py ? ly : hy, nz = pz ? lz : hz;
             const uint32_t fx = px ? hx : lx, fy = py ? hy : ly, fz = pz ? hz : lz;
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
-                        sz = as_float(((e >> 16) & 0xffu) << 23);
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            float tnk[4];
+            bool hk[4];
+            wide_accept<4>(q0.x, q0.y, q0.z, e, nx, ny, nz, fx, fy, fz, ro, inv, tmin, tmax, tnk, hk);
             bool h[4];
             uint32_t ce[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
             {
                 const uint32_t m = (meta >> (8 * k)) & 0xffu;
-                float tn = fmaxf(fmaxf(__builtin_fmaf(wide_byte(nx, k), Bx, Ax), __builtin_fmaf(wide_byte(ny, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(nz, k), Bz, Az));
-                float tf = fminf(fminf(__builtin_fmaf(wide_byte(fx, k), Bx, Ax), __builtin_fmaf(wide_byte(fy, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(fz, k), Bz, Az));
-                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
-                tn = fmaxf(tn, tmin);
-                tf = fminf(tf, tmax) * WIDE_SLAB_PAD;
-                h[k] = (m != 0u) && (tn <= tf);
+                h[k] = hk[k] && m != 0u;
                 ce[k] = (base + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
             }
             if (h[0] || h[1] || h[2] || h[3])
@@ -1796,24 +1707,16 @@ RT_DEV uint32_t occluded_walk_ws(const WideView& bvh, uint32_t* __restrict__ lds
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
             const uint32_t nx = px ? lx : hx, ny = py ? ly : hy, nz = pz ? lz : hz;
             const uint32_t fx = px ? hx : lx, fy = py ? hy : ly, fz = pz ? hz : lz;
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
-                        sz = as_float(((e >> 16) & 0xffu) << 23);
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            float tnk[4];
+            bool hk[4];
+            wide_accept<4>(q0.x, q0.y, q0.z, e, nx, ny, nz, fx, fy, fz, ro, inv, tmin, tmax, tnk, hk);
             bool h[4];
             uint32_t ce[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
             {
                 const uint32_t m = (meta >> (8 * k)) & 0xffu;
-                float tn = fmaxf(fmaxf(__builtin_fmaf(wide_byte(nx, k), Bx, Ax), __builtin_fmaf(wide_byte(ny, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(nz, k), Bz, Az));
-                float tf = fminf(fminf(__builtin_fmaf(wide_byte(fx, k), Bx, Ax), __builtin_fmaf(wide_byte(fy, k), By, Ay)),
-                                 __builtin_fmaf(wide_byte(fz, k), Bz, Az));
-                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
-                tn = fmaxf(tn, tmin);
-                tf = fminf(tf, tmax) * WIDE_SLAB_PAD;
-                h[k] = (m != 0u) && (tn <= tf);
+                h[k] = hk[k] && m != 0u;
                 ce[k] = (cbase + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
             }
             if (h[0] || h[1] || h[2] || h[3])

@@ -3323,26 +3323,18 @@ __global__ __launch_bounds__(BLOCK) void k_trace_queue(WideView wide, const floa
             const uint32_t base = as_uint(q1f.x), meta = as_uint(q1f.y);
             const uint32_t lx = as_uint(q1f.z), ly = as_uint(q1f.w), lz = as_uint(q2f.x);
             const uint32_t hx = as_uint(q2f.y), hy = as_uint(q2f.z), hz = as_uint(q2f.w);
-            const float sx = as_float((e & 0xffu) << 23), sy = as_float(((e >> 8) & 0xffu) << 23),
-                        sz = as_float(((e >> 16) & 0xffu) << 23);
-            const float Ax = (q0.x - ro.x) * inv.x, Ay = (q0.y - ro.y) * inv.y, Az = (q0.z - ro.z) * inv.z;
-            const float Bx = sx * inv.x, By = sy * inv.y, Bz = sz * inv.z;
+            const bool px = inv.x >= 0.0f, py = inv.y >= 0.0f, pz = inv.z >= 0.0f; /* entry plane: the low one for inv >= 0 */
             float td[4];
+            bool hk[4];
+            wide_accept<4>(q0.x, q0.y, q0.z, e, px ? lx : hx, py ? ly : hy, pz ? lz : hz, px ? hx : lx, py ? hy : ly, pz ? hz : lz, ro, inv, tmin, best, td, hk);
             uint32_t ce[4];
             int nhit = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k)
             {
                 const uint32_t m = (meta >> (8 * k)) & 0xffu;
-                const float x0 = __builtin_fmaf(wide_byte(lx, k), Bx, Ax), x1 = __builtin_fmaf(wide_byte(hx, k), Bx, Ax);
-                const float y0 = __builtin_fmaf(wide_byte(ly, k), By, Ay), y1 = __builtin_fmaf(wide_byte(hy, k), By, Ay);
-                const float z0 = __builtin_fmaf(wide_byte(lz, k), Bz, Az), z1 = __builtin_fmaf(wide_byte(hz, k), Bz, Az);
-                float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
-                float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
-                /* conservative: rounding may leave tn a few 1e-7 too large and tf too small; one factor on the far side covers both */
-                tn = fmaxf(tn, tmin);
-                tf = fminf(tf, best) * WIDE_SLAB_PAD;
-                const bool h = (m != 0u) && (tn <= tf);
+                const bool h = hk[k] && m != 0u;
+                const float tn = td[k];
                 td[k] = h ? tn : 3.0e38f;
                 ce[k] = (base + (uint32_t)k) | (m == 2u ? WIDE_LEAF_BIT : 0u);
                 nhit += h ? 1 : 0;

@@ -271,7 +271,10 @@ int rt_row_shaded(rt_ctx* ctx, uint32_t* counts);
  * on-screen / not-self tests. Replays the RNG; independent of reservoir contents. */
 int rt_spatial_bytes(rt_ctx* ctx, int frame, int pass, int in, uint64_t* bytes, uint64_t* accepted);
 /* ---- BVH utilities (parity tests: BVH traversal == brute force) ----
- * rays: n x {ox,oy,oz, dx,dy,dz, tmin,tmax}; hits: n x {t,u,v, bits(index)}; host pointers. */
+ * rays: n x {ox,oy,oz, dx,dy,dz, tmin,tmax}; hits: n x {t,u,v, bits(index)}; host pointers.
+ * Equal to brute force because the leaf boxes' pad, the quantiser's outward rounding and the margin of the accept predicate
+ * together keep every box that holds a hit the intersector accepts (csrc/bvh_cull.h has the argument); held to it on random rays
+ * (tests/test_gpu_parity.py) and on rays aimed at vertices, edges, box faces and duplicated triangles (tests/test_gpu_targeted_rays.py). */
 int rt_trace_closest(rt_ctx* ctx, const float* rays, uint32_t n, float* hits);
 /* per ray {nodes visited, triangle tests} of the same traversal (BVH quality diagnostics); for the
  * wide traversal the upper 16 bits of each word count the inner / leaf passes the ray's wavefront

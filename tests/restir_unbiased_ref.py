@@ -4,7 +4,8 @@ for tests/test_restir_unbiased_cpu.py and tests/test_gpu_restir_unbiased.py.
 One pass over the whole image in plain C++ on the reference's 76-byte Reservoir records (buffer index = row * W + x). Every formula
 comes from csrc/rt_device.h and csrc/portable_math.h, the headers the kernel is compiled from; built with `g++ -ffp-contract=off`,
 so the result equals the GPU's bit for bit (rows run on OpenMP threads: a pixel is computed by one thread). Visibility is brute-force
-any-hit over all triangles with intersect_ray_triangle: the BVH walk equals brute force by construction.
+any-hit over all triangles with intersect_ray_triangle: the BVH walk equals brute force (csrc/bvh_cull.h has the argument,
+tests/test_gpu_targeted_rays.py the rays that would show otherwise).
 mode = REFERENCE makes it the reference's pass (10_restir_di.cu:256-388, unshadowed target function), which anchors the restatement
 to oracle.Scene.spatial_resampling. diag holds per pixel {Z, M_sum, mask of neighbours k with Mk > 0 that geometry alone kept out
 of Z, mask of those the shadow ray alone kept out}; in reference mode Z = M_sum and the masks are 0."""
