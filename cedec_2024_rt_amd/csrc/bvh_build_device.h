@@ -6,11 +6,28 @@
  *       pass (the recursion of bvh_build_host.h::split_refs with a per-thread stack);
  *   3b. top-down binned SAH over the references: nodes of more than SAH_MEDIUM references are binned by many
  *       workgroups and split by one wavefront each, medium nodes are binned and split by one workgroup, small ones by one
- *       wavefront down to the leaves — the tree the host builder (bvh_build_host.h, builder 1) makes, reproduced on the device;
+ *       wavefront down to the leaves — the tree the host builder (bvh_build_host.h, builder 1) makes, reproduced on the device
+ *       wherever a plane separates the centroids of every node above SAH_SMALL references (see TESTED below);
  *   4.  collapse into the 4-wide quantised 48-B records the kernels walk (bvh.h), level by level on the device.
  * No host round trip carries tree data; the host reads back a handful of counters (reference count, record count,
  * heights). Wall time of rt_scene_set for the 212 k-triangle bench scene: rt_build_ms / `build_ms` of the bench line
  * (upload + light tables + this build, synchronised).
+ *
+ * TESTED (tests/test_gpu_bvh_build.py, scenes of tests/bvh_build_scenes.py), beyond "the walks equal brute force":
+ *   - builder 3 == builder 1 in reference count, wide record count, both heights, SAH cost (rt_bvh_cost) and the per-ray node and
+ *     triangle counts of the closest-hit walk, on soups in generic position of 2..5, 63..66 and 4095..4098 references (the
+ *     borders of the three regimes), on two-cluster scenes whose first split lands the children on 64 | 65, 1 | 65, 4096 | 4097
+ *     and 64 | 4097, on the same soups with pre-split fragments, on the pre-split budget scene, and on centroids on a line, in a
+ *     plane, in two clusters 1e6 apart and under one enclosing triangle; n copies of one triangle: all but the per-ray counts
+ *     (every area ties, and the collapse's order among equal areas is the host sort's);
+ *   - NOT equal, and asserted only as "device cost >= host cost": a node of MORE than SAH_SMALL references whose centroids all
+ *     coincide (concentric references). It is halved by position and both halves inherit the node's box, where the host gives
+ *     each half its own union; k_sah_small's wave reductions are exact again below 65. Measured on references concentric over
+ *     three decades of extent: cost x 1.0018 at 1000, x 1.0107 at 6000 (docs/MEASUREMENT_LOG_r18.md). Results are unaffected;
+ *   - the reference count stays within 4 * triangles + 1024 (bvh_fragment.h::frag_fit_length).
+ *   Not tested: equality with builder 1 where centroids tie AFTER a plane split (the host's partition is not stable, the
+ *   device's is, so a later positional halving may take other references; the two-cluster scene at 1e6 has such ties and came
+ *   out equal, which is a measurement, not an argument), the 212 k and 1.1 M scenes against builder 1, NaN or infinite vertices.
  *
  * A/B only (-DRT_EXPERIMENTS): section 3, PLOC — parallel locally-ordered clustering (Meister & Bittner 2018) over Morton-sorted
  * references (builder 2, round 2) — and, through bvh.h's kernels, the Karras hierarchy + refit of round 1 (builder 0).
@@ -472,7 +489,8 @@ RT_DEV void sah_split_wave(int level, int s, const SahNode& nd, const unsigned i
     else
     {
         /* every centroid of the node is the same point: halves by position; their boxes are not known separately, the
-         * node's box bounds both (only duplicates and concentric references come here) */
+         * node's box bounds both (only duplicates and concentric references come here). The host builder gives each half
+         * its own union: for concentric references of different sizes this tree is the looser one (header, TESTED) */
         for (int sd = 0; sd < 2; ++sd)
             for (int k = 0; k < 6; ++k) { cb[sd][k] = nd.box[k]; cc[sd][k] = nd.cent[k]; }
     }

@@ -172,6 +172,36 @@ RT_HD unsigned int frag_split(const float* t /* 9 floats */, float L, Sink&& sin
     return emitted;
 }
 
+/* The fragment length both builders use (host code; the ONE owner of the search). budget = 4 * triangles + 1024 references.
+ * count(L) returns the scene's total number of fragments at length L as uint64_t — a triangle gives up to FRAG_MAX_PER_TRI, so
+ * above 2^20 triangles a 32-bit total can wrap and pass the test below: the callers sum in 64 bits (the device build by a
+ * 64-bit reduction over the per-triangle counts, the host path by the size of its vector).
+ *   - L0 is returned unchanged when it fits (or is <= 0: no splitting, one reference per triangle).
+ *   - Up to FRAG_FIT_ROUNDS steps of 1.5 x, as the build has always relaxed L: a scene that fitted within them keeps its L bit
+ *     for bit.
+ *   - After that L doubles until the count fits. It ends: frag_split cuts a polygon only while its extent exceeds L, so from
+ *     L >= the largest triangle extent (at the latest L = +inf, which binary32 doubling reaches in under 280 steps from any
+ *     L > 0) every triangle is one fragment, and triangles <= budget.
+ * The LAST call of count is at the returned L, so what count left behind (per-triangle counts, the fragments themselves)
+ * belongs to it; *total, if given, receives that count. tests/test_bvh_presplit_budget_cpu.py runs it, beside the loop it
+ * replaced, on scenes that loop left far over the budget. */
+constexpr int FRAG_FIT_ROUNDS = 16;
+template <class Count>
+inline float frag_fit_length(float L0, uint64_t budget, Count&& count, uint64_t* total = nullptr)
+{
+    float L = L0;
+    for (int it = 0;; ++it)
+    {
+        const uint64_t n = count(L);
+        if (n <= budget || !(L > 0.0f))
+        {
+            if (total) *total = n;
+            return L;
+        }
+        L *= it < FRAG_FIT_ROUNDS - 1 ? 1.5f : 2.0f;
+    }
+}
+
 /* (1 - u - v) A + u B + v C: a corner's (u, v) gives its vertex back exactly */
 RT_HD void frag_point(const float* A, const float* B, const float* C, float u, float v, float* p)
 {

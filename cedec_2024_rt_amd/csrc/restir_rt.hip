@@ -588,6 +588,7 @@ static int build_wide(rt_ctx* c, const rt_triangle* tris, int n_refs)
 #ifndef RT_PLOC_TOP
 #define RT_PLOC_TOP 8192 /* clusters left when the host builds the top of the tree (builder 2): 2048 / 8192 / 32768 -> build 10.4 / 13.3 / 25.3 ms, frame +3.5 / +1.5 / +0.5 % against the host SAH tree */
 #endif
+struct FragCount64 { __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; } };
 static int build_bvh_device(rt_ctx* c, int n_tris)
 {
     hipStream_t st = c->stream;
@@ -631,21 +632,31 @@ static int build_bvh_device(rt_ctx* c, int n_tris)
     BD_HIP(rocprim::exclusive_scan(nullptr, sb, d_cnt, d_off, 0u, (size_t)n_tris, rocprim::plus<uint32_t>(), st));
     void* d_t1 = dalloc(sb); BD_PTR(d_t1);
     float L = c->bvh_split_factor > 0.0f ? c->bvh_split_factor * median : 0.0f;
-    const size_t budget = (size_t)n_tris * 4 + 1024;
-    int n = 0;
-    for (int it = 0; it < 16; ++it)
-    {
-        k_split_refs<false><<<gt, 256, 0, st>>>(c->d_tris, n_tris, L, pad, nullptr, d_cnt, nullptr, nullptr);
-        BD_HIP(hipGetLastError());
-        BD_HIP(rocprim::exclusive_scan(d_t1, sb, d_cnt, d_off, 0u, (size_t)n_tris, rocprim::plus<uint32_t>(), st));
-        uint32_t last[2];
-        BD_HIP(hipMemcpyAsync(&last[0], d_off + n_tris - 1, 4, hipMemcpyDeviceToHost, st));
-        BD_HIP(hipMemcpyAsync(&last[1], d_cnt + n_tris - 1, 4, hipMemcpyDeviceToHost, st));
-        BD_HIP(hipStreamSynchronize(st));
-        n = (int)(last[0] + last[1]);
-        if ((size_t)n <= budget || L <= 0.0f) break;
-        L *= 1.5f;
-    }
+    const uint64_t budget = (uint64_t)n_tris * 4 + 1024;
+    /* the total in 64 bits (FragCount64): up to FRAG_MAX_PER_TRI fragments of each of more than 2^20 triangles wrap 32 */
+    uint64_t* d_total = (uint64_t*)dalloc(8); BD_PTR(d_total);
+    auto cnt64 = rocprim::make_transform_iterator(d_cnt, FragCount64());
+    size_t rdb = 0;
+    BD_HIP(rocprim::reduce(nullptr, rdb, cnt64, d_total, (uint64_t)0, (size_t)n_tris, rocprim::plus<uint64_t>(), st));
+    void* d_t1b = dalloc(rdb); BD_PTR(d_t1b);
+    hipError_t count_err = hipSuccess;
+    uint64_t total = 0;
+    L = frag_fit_length(L, budget, [&](float len) -> uint64_t {
+        /* per-triangle counts at `len` and their 64-bit sum; an error ends the search (0 fits) and is reported below */
+        uint64_t sum = 0;
+        k_split_refs<false><<<gt, 256, 0, st>>>(c->d_tris, n_tris, len, pad, nullptr, d_cnt, nullptr, nullptr);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = rocprim::reduce(d_t1b, rdb, cnt64, d_total, (uint64_t)0, (size_t)n_tris, rocprim::plus<uint64_t>(), st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_total, 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { count_err = e; return 0; }
+        return sum;
+    }, &total);
+    if (count_err != hipSuccess) BD_FAIL(RT_ERR_HIP, "counting the pre-split fragments failed: %s", hipGetErrorString(count_err));
+    if (total > budget || total > (uint64_t)INT32_MAX) BD_FAIL(RT_ERR_STATE, "internal: %llu pre-split references for %d triangles", (unsigned long long)total, n_tris);
+    /* offsets of the accepted counts: total <= budget < 2^32, so this 32-bit scan cannot wrap */
+    BD_HIP(rocprim::exclusive_scan(d_t1, sb, d_cnt, d_off, 0u, (size_t)n_tris, rocprim::plus<uint32_t>(), st));
+    const int n = (int)total;
     c->n_refs = n;
     float* d_boxes = (float*)dalloc((size_t)n * 24); BD_PTR(d_boxes);
     int* d_ref_tri = (int*)dalloc((size_t)n * 4); BD_PTR(d_ref_tri);
@@ -975,13 +986,10 @@ static int build_bvh(rt_ctx* c, const rt_triangle* tris, int n_tris)
         std::vector<float> e2(extents);
         std::nth_element(e2.begin(), e2.begin() + e2.size() / 2, e2.end());
         float L = c->bvh_split_factor > 0.0f ? c->bvh_split_factor * e2[e2.size() / 2] : 0.0f;
-        const size_t budget = (size_t)n_tris * 4 + 1024;
-        for (int it = 0; it < 16; ++it)
-        {
-            split_refs(tris, n_tris, L, pad, refs);
-            if (refs.size() <= budget || L <= 0.0f) break;
-            L *= 1.5f;
-        }
+        frag_fit_length(L, (uint64_t)n_tris * 4 + 1024, [&](float len) -> uint64_t {
+            split_refs(tris, n_tris, len, pad, refs);
+            return (uint64_t)refs.size();
+        });
     }
     const int n = (int)refs.size();
     c->n_refs = n;

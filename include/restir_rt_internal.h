@@ -353,7 +353,7 @@ enum rt_tuning_key
     /* ---- Scene (before rt_scene_set) ---- */
     /* BVH builder: 3 = on the device: pre-split, top-down binned SAH, 4-wide collapse; the host reads counters (default;
      * 11 ms for 212 k triangles). [exp] 0 = device LBVH + host collapse (r01), 1 = host binned SAH (the tree builder 3
-     * reproduces; 230 ms), 2 = device PLOC + host SAH over the top 8 192 clusters. All feed the same walk. */
+     * reproduces, except below a node of more than 64 references with one common centroid: csrc/bvh_build_device.h; 230 ms), 2 = device PLOC + host SAH over the top 8 192 clusters. All feed the same walk. */
     RT_TUNE_BVH_BUILDER = 5,
     /* wide-BVH records emitted breadth-first before the collapse goes depth-first (default 2048; no measurable effect). */
     RT_TUNE_BVH_BFS_RECORDS = 7,
