@@ -44,7 +44,7 @@ INTERNAL_EXPORTS = [
     "rt_mg_selftest_rccl", "rt_visibility_rays_walked", "rt_walk_stats_enable", "rt_walk_stats", "rt_stage0_one_launch",
     "rt_row_shaded", "rt_spatial_bytes", "rt_trace_closest", "rt_trace_stats", "rt_bvh_config", "rt_bvh_info", "rt_bvh_cost", "rt_build_ms",
     "rt_trace_mode", "rt_trace_time", "rt_tuning", "rt_tuning_get", "rt_math_eval", "rt_gbuffer_reuse", "rt_primary_launches",
-    "rt_spatial_unbiased", "rt_spatial_unbiased_get",
+    "rt_spatial_unbiased", "rt_spatial_unbiased_get", "rt_occluder_hints", "rt_occluder_hint_stats", "rt_trace_occluders",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -185,6 +185,10 @@ def load_library(exp=False, path=None):
     if hasattr(L, "rt_spatial_unbiased"):  # r15; likewise (Renderer.spatial_unbiased raises on such a build)
         L.rt_spatial_unbiased.argtypes = [vp, ci]
         L.rt_spatial_unbiased_get.argtypes = [vp, vp]
+    if hasattr(L, "rt_occluder_hints"):  # r19; likewise
+        L.rt_occluder_hints.argtypes = [vp, ci]
+        L.rt_occluder_hint_stats.argtypes = [vp, vp]
+        L.rt_trace_occluders.argtypes = [vp, vp, C.c_uint32, vp]
     L.rt_visibility_rays_walked.argtypes = [vp, vp]
     L.rt_state_epoch.argtypes = [vp, vp]
     L.rt_get_stream.argtypes = [vp, vp]
@@ -394,6 +398,10 @@ class Renderer:
         # without the call does that anyway)
         if os.environ.get("RT_GBUFFER_REUSE", "") == "0" and hasattr(self.L, "rt_gbuffer_reuse"):
             self._ck(self.L.rt_gbuffer_reuse(self.h, 0))
+        # A/B runs: RT_OCCLUDER_HINTS=0 makes the candidates of every context walk without their pixels' remembered occluders
+        # (rt_occluder_hints; a library without the call has none anyway)
+        if os.environ.get("RT_OCCLUDER_HINTS", "") == "0" and hasattr(self.L, "rt_occluder_hints"):
+            self._ck(self.L.rt_occluder_hints(self.h, 0))
         a, b = C.c_int(), C.c_int()
         self._ck(self.L.rt_local_rows(self.h, C.byref(a), C.byref(b)))
         self.local_row0, self.local_rows = a.value, b.value
@@ -699,7 +707,8 @@ class Renderer:
 
     def walk_stats(self):
         """per kernel: reference rays / walked through the BVH / settled by the self-occlusion test / not evaluated; the last three
-        sum to the first. While spatial_unbiased is on, the spatial slot counts the pass's own rays instead: 0 reference rays (the
+        sum to the first. generate_candidate's self_test includes the rays a remembered occluder settled (occluder_hint_stats). While
+        spatial_unbiased is on, the spatial slot counts the pass's own rays instead: 0 reference rays (the
         reference's unshadowed pass has none), the neighbours' and own rays walked, those the origin's triangle settled, and as
         not_evaluated the own rays an earlier kernel of the frame had answered."""
         a = np.zeros(16, dtype=np.uint64)
@@ -739,6 +748,30 @@ class Renderer:
                 raise RtError("this build of librestir_rt has no rt_gbuffer_reuse: every frame traces its primary rays")
             return
         self._ck(self.L.rt_gbuffer_reuse(self.h, int(bool(on))))
+
+    def occluder_hints(self, on=True):
+        """the candidates of a staged frame test the triangles that occluded their pixel's earlier shadow rays before they walk the
+        BVH (default on; results never depend on it). A library without the call has no hints: on=False is then a no-op and on=True
+        an error."""
+        if not hasattr(self.L, "rt_occluder_hints"):
+            if on:
+                raise RtError("this build of librestir_rt has no rt_occluder_hints")
+            return
+        self._ck(self.L.rt_occluder_hints(self.h, int(bool(on))))
+
+    def occluder_hint_stats(self):
+        """while walk_stats_enable is on: candidate rays that had a remembered triangle to test, rays one of them settled (part of
+        walk_stats()['generate_candidate']['self_test']), triangle tests made"""
+        a = np.zeros(3, dtype=np.uint64)
+        self._ck(self.L.rt_occluder_hint_stats(self.h, _p(a)))
+        return dict(rays_with_hint=int(a[0]), settled=int(a[1]), tests=int(a[2]))
+
+    def trace_occluders(self, rays):
+        """the work-sharing any-hit walk asked for its occluder: per ray the index of a triangle that occludes it, -1 = none"""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        tri = np.full(len(r), -1, dtype=np.int32)
+        self._ck(self.L.rt_trace_occluders(self.h, _p(r), len(r), _p(tri)))
+        return tri
 
     def spatial_unbiased(self, on=None):
         """rt_spatial_unbiased: the spatial passes normalise by 1/Z (only the contributors that could have produced the selected

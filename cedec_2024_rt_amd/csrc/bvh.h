@@ -452,8 +452,10 @@ RT_DEV bool trace_wide(const WideView& bvh, uint32_t* __restrict__ lds_stack, f3
 template <int STRIDE = BLOCK_THREADS>
 RT_DEV bool occluded_ws(const WideView& bvh, uint32_t* __restrict__ lds_generic, f3 ro, f3 rd, float tmin, float tmax,
                         uint32_t* stats = nullptr /* [0] passes of the wavefront, [1] steals by this lane | own steps << 16, [2] leaf passes, [3] own triangle tests */,
-                        const bool live = true /* false: this lane has no ray of its own and only helps (returns false) */)
+                        const bool live = true /* false: this lane has no ray of its own and only helps (returns false) */,
+                        int* occluder = nullptr /* out: index of a triangle that occludes this lane's ray (whichever lane reported last), -1 if none */)
 {
+    if (occluder) *occluder = -1;
     if (bvh.n_tris <= 0) return false;
     /* an LDS-typed pointer: generic-pointer accesses in this loop (entries of another lane's slots) make the gfx950
      * backend emit an aperture test it then rejects ("V_CMP_NE_U32 0, $src_shared_base: incorrect register class") */
@@ -612,7 +614,9 @@ RT_DEV bool occluded_ws(const WideView& bvh, uint32_t* __restrict__ lds_generic,
                 float t, u, v;
                 if (intersect_ray_triangle(t, u, v, ro, rd, tmin, tmax, v0, v1, v2))
                 {
-                    s_hit[owner] = 1u; /* any hit settles a shadow ray */
+                    /* any hit settles a shadow ray; with `occluder` the flag names the triangle (1 + index): concurrent
+                     * writers are helpers of the same ray, and each of them names a true occluder */
+                    s_hit[owner] = occluder ? 1u + as_uint(t2.y) : 1u;
                     cur = NONE; pend = NONE; pend2 = NONE; sp = 0; base = 0;
                 }
             }
@@ -663,7 +667,9 @@ RT_DEV bool occluded_ws(const WideView& bvh, uint32_t* __restrict__ lds_generic,
     }
     (void)ba;
     if (stats) stats[0] = pass;
-    return s_hit[slot] != 0u;
+    const uint32_t flag = s_hit[slot];
+    if (occluder) *occluder = (int)flag - 1;
+    return flag != 0u;
 }
 
 /* ---- Work-sharing CLOSEST-hit walk (r02). Same sharing rules as occluded_ws; the answer of a ray is the minimum over
@@ -1292,12 +1298,15 @@ RT_DEV uint32_t self_occluded_mask(const float4* __restrict__ tv, int own_tri, f
  * wavefront's walk as a helper. tv / own_tri: the triangle the ray starts from, for the self-occlusion pre-test. */
 template <int STRIDE = BLOCK_THREADS, bool WS = false>
 RT_DEV bool check_visibility_wide(const WideView& bvh, uint32_t* __restrict__ lds_stack, f3 p0, f3 n0, f3 p1, const bool live = true,
-                                  const float4* __restrict__ tv = nullptr, const int own_tri = -1)
+                                  const float4* __restrict__ tv = nullptr, const int own_tri = -1,
+                                  int* occluder = nullptr /* work-sharing walk only: the triangle the WALK found (occluded_ws), -1 if the
+                                                             ray is visible or its own triangle settled it */)
 {
     const f3 org = p0 + 0.001f * n0;
     const f3 dir = p1 - p0;
     const bool self = self_occluded(tv, own_tri, org, dir, n0, live);
-    if (WS) return !occluded_ws<STRIDE>(bvh, lds_stack, org, dir, 0.0f, 0.99f, nullptr, live && !self) && !self;
+    if (WS) return !occluded_ws<STRIDE>(bvh, lds_stack, org, dir, 0.0f, 0.99f, nullptr, live && !self, occluder) && !self;
+    if (occluder) *occluder = -1;
     if (!live) return true;
     if (self) return false;
     Hit h;

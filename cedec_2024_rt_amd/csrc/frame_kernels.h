@@ -8,6 +8,7 @@
  */
 #pragma once
 #include "bvh.h"
+#include "occluder_hint.h"
 #include "rt_device.h"
 
 using namespace rt;
@@ -71,7 +72,7 @@ struct WaveClock
 #else
 #define RT_WAVE_CLOCK(P)
 #endif
-enum { WALK_RAYCAST = 0, WALK_GENERATE = 1, WALK_SPATIAL = 2, WALK_RESOLVE = 3 };
+enum { WALK_RAYCAST = 0, WALK_GENERATE = 1, WALK_SPATIAL = 2, WALK_RESOLVE = 3, WALK_HINTS = 4 /* rt_occluder_hint_stats: {rays with a hint to test, settled by one, triangle tests, -} */, WALK_SLOTS = 5 };
 /* one ray per lane at most; works under any exec mask (ballots count the active lanes) */
 RT_DEV void count_walk_flags(unsigned long long* __restrict__ st, bool ref, bool walked, bool self, bool skipped)
 {
@@ -521,6 +522,26 @@ RT_DEV bool temporal_merge(const FrameParams& P, int x, int yi, f3 sp, f3 sn, Re
     return took_prev;
 }
 
+/* a pixel's record of remembered occluders (occluder_hint.h) as one aligned word of the hint buffer. The second form reads
+ * the record anew after the walk: a plain load of the same address could be kept in registers across it. */
+typedef int hint_word __attribute__((ext_vector_type(OCCLUDER_HINTS)));
+RT_DEV OccluderHints<OCCLUDER_HINTS> hint_unpack(const hint_word w)
+{
+    OccluderHints<OCCLUDER_HINTS> h;
+#pragma unroll
+    for (int k = 0; k < OCCLUDER_HINTS; ++k) h.tri[k] = w[k];
+    return h;
+}
+RT_DEV OccluderHints<OCCLUDER_HINTS> hint_load(const int* hints, size_t li) { return hint_unpack(reinterpret_cast<const hint_word*>(hints)[li]); }
+RT_DEV OccluderHints<OCCLUDER_HINTS> hint_reload(const int* hints, size_t li) { return hint_unpack(reinterpret_cast<const volatile hint_word*>(hints)[li]); }
+RT_DEV void hint_store(int* hints, size_t li, const OccluderHints<OCCLUDER_HINTS>& h)
+{
+    hint_word w;
+#pragma unroll
+    for (int k = 0; k < OCCLUDER_HINTS; ++k) w[k] = h.tri[k];
+    reinterpret_cast<hint_word*>(hints)[li] = w;
+}
+
 #ifndef RT_RESOLVE_WAVES_FWD
 #define RT_RESOLVE_WAVES_FWD 6 /* k_candidate_visibility: the register budget of k_resolve (one shadow ray per lane) */
 #endif
@@ -535,8 +556,10 @@ RT_DEV bool temporal_merge(const FrameParams& P, int x, int yi, f3 sp, f3 sn, Re
  * kernel gets the same saving without a queue (LATE below). */
 /* the work-sharing variant allocates 102 VGPRs unconstrained (4 wavefronts per SIMD); held to the 96 of the plain
  * kernel (5 per SIMD) it is 3 % faster (A/B on the GPU, profiles/r02_ws_register_budgets.txt) */
+/* r19: 6. The kernel had come down to 80 VGPRs by itself (log r17 section 3); with the occluder-hint test in front of the walk it
+ * allocates 82 under a budget of 5 and 79 under this one, without spills (docs/MEASUREMENT_LOG_r19.md) */
 #ifndef RT_GENERATE_WS_WAVES
-#define RT_GENERATE_WS_WAVES 5
+#define RT_GENERATE_WS_WAVES 6
 #endif
 #ifndef RT_GENERATE_SH_WAVES
 #define RT_GENERATE_SH_WAVES RT_TRACE_WAVES /* the shadowed-target kernel (110 VGPRs) */
@@ -566,7 +589,8 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     SceneView S, FrameParams P, const float4* __restrict__ g0, const float4* __restrict__ g1,
     const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad, float4* __restrict__ out_rec,
     float4* __restrict__ out_rad, uint32_t* __restrict__ vis_queue = nullptr, unsigned int* __restrict__ vis_count = nullptr,
-    float4* __restrict__ vis_w = nullptr, float4* __restrict__ g0_w = nullptr, float4* __restrict__ g1_w = nullptr)
+    float4* __restrict__ vis_w = nullptr, float4* __restrict__ g0_w = nullptr, float4* __restrict__ g1_w = nullptr,
+    int* hints = nullptr /* LATE: OCCLUDER_HINTS remembered occluders per local pixel (occluder_hint.h), nullptr = none */)
 {
     static_assert(!DEFER || (FUSE_TEMPORAL && !SHADOWED), "deferred visibility: fused unshadowed kernel only");
     static_assert(!RAYCAST || (WS && FUSE_TEMPORAL && !SHADOWED && !DEFER && !PIPE), "primary rays in the product's fused kernel only");
@@ -839,15 +863,58 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
          * whole wavefront. The ray's answer is observable only if the candidate survived (otherwise the stored bit is
          * the previous sample's, reservoir.hpp:36); lanes whose candidate did not survive, sky / emissive pixels and
          * lanes outside the image walk no ray of their own and take over parts of the others' walks instead. */
+        /* Occluder hints: 87 % of the candidates are occluded, and a pixel's shadow rays keep ending on the same few triangles.
+         * Between the own triangle's test and the walk, a lane with a live ray tests the triangles its record remembers
+         * (occluder_hint.h: any index below the triangle count is a valid hint, a hit is a hit of brute force); one pass per
+         * position, only while some lane of the wavefront has an entry there. A settled lane joins the walk as a helper. */
+        const f3 late_org = late_sp + 0.001f * late_sn, late_dir = r.hit_p - late_sp;
+        const bool self = self_occluded(S.bvh.tv, as_int(G0.w), late_org, late_dir, late_sn, late_live);
+        const bool own_ray = late_live && !self; /* not settled by the triangle the ray starts from */
+        /* >= 0: a one-triangle test settled the ray: the remembered triangle at that position, or the own triangle (0: like a hit
+         * of the first remembered triangle, it leaves the record as it is) */
+        int hint_at = self ? 0 : -1;
+        if (hints)
+        {
+            OccluderHints<OCCLUDER_HINTS> h = hint_empty<OCCLUDER_HINTS>();
+            if (own_ray) h = hint_load(hints, li);
+            uint32_t n_tests = 0u;
+            bool had = false;
+#pragma unroll
+            for (int k = 0; k < OCCLUDER_HINTS; ++k)
+            {
+                const bool pending = own_ray && hint_at < 0 && hint_pending(h, k, S.bvh.n_tris);
+                had = had || pending;
+                if (__ballot(pending) == 0ull) continue;
+                if (pending)
+                {
+                    f3 v0, v1, v2;
+                    load_tri(S.bvh.tv, h.tri[k], v0, v1, v2);
+                    float t, u, v;
+                    if (intersect_ray_triangle(t, u, v, late_org, late_dir, 0.0f, 0.99f, v0, v1, v2)) hint_at = k;
+                    ++n_tests;
+                }
+            }
+            if (P.stats) count_walk_counts(P.stats + 4 * WALK_HINTS, had ? 1u : 0u, own_ray && hint_at >= 0 ? 1u : 0u, n_tests, 0u);
+        }
+        const bool walk = late_live && hint_at < 0;
         if (P.stats)
         {
             /* the reference walks the visibility-reuse ray of every shaded pixel (:127-131); here: only where the answer is
-             * observable (the candidate survived the merge), less what the own triangle settles */
+             * observable (the candidate survived the merge), less what the own triangle or a remembered one settles: both are
+             * one-triangle tests and count as self_test */
             const bool ref_ray = act && P.vis_reuse;
-            const bool self = self_occluded(S.bvh.tv, as_int(G0.w), late_sp + 0.001f * late_sn, r.hit_p - late_sp, late_sn, late_live);
-            count_walk_flags(P.stats + 4 * WALK_GENERATE, ref_ray, late_live && !self, late_live && self, ref_ray && !late_live);
+            count_walk_flags(P.stats + 4 * WALK_GENERATE, ref_ray, walk, late_live && !walk, ref_ray && !late_live);
         }
-        const bool visible = check_visibility_wide<TRACE_BLOCK, true>(S.wide, s_stack, late_sp, late_sn, r.hit_p, late_live, S.bvh.tv, as_int(G0.w));
+        int occluder = -1;
+        const bool walked_hit = occluded_ws<TRACE_BLOCK>(S.wide, s_stack, late_org, late_dir, 0.0f, 0.99f, nullptr, walk, &occluder);
+        const bool visible = !(walked_hit || hint_at >= 0);
+        if (hints && (occluder >= 0 || hint_at > 0))
+        {
+            /* reloaded, not held across the walk (registers); whatever another launch wrote meanwhile is a valid record too */
+            OccluderHints<OCCLUDER_HINTS> h = hint_reload(hints, li);
+            const bool changed = occluder >= 0 ? hint_insert(h, occluder) : hint_hit(h, hint_at);
+            if (changed) hint_store(hints, li, h);
+        }
         if (late_live) { r.vis = visible; r.ownv = ownv_of(P.ownv_tag, visible); }
         /* the wavefront's 64 records leave together, a quad per record (wave_scatter_records below; the walk's LDS is idle now) */
         const bool shaded = in_image && (flags & GB_SHADED);
@@ -3217,6 +3284,17 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_anyhit(SceneView S, const
     }
     float4* out = (float4*)hits;
     out[i] = make_float4(0.0f, 0.0f, 0.0f, as_float(occ ? 0 : -1));
+}
+/* the work-sharing walk of k_trace_anyhit<true>, asked for its occluder (occluded_ws): tri[i] = a triangle that occludes ray i, -1 = none */
+__global__ __launch_bounds__(TRACE_BLOCK) void k_trace_occluders(SceneView S, const float* __restrict__ rays, int n, int* __restrict__ tri)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_stack[WIDE_LDS_ROWS * TRACE_BLOCK];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* r = rays + 8 * (size_t)i;
+    int occluder = -1;
+    if (r[7] >= 0.0f) occluded_ws<TRACE_BLOCK>(S.wide, s_stack, F3(r[0], r[1], r[2]), F3(r[3], r[4], r[5]), r[6], r[7], nullptr, true, &occluder);
+    tri[i] = occluder;
 }
 template <int MODE, bool ANY = false>
 __global__ __launch_bounds__(BLOCK) void k_trace_stats(SceneView S, const float* __restrict__ rays, int n, uint32_t* __restrict__ stats)

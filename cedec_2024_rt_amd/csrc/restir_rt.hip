@@ -101,8 +101,14 @@ struct rt_ctx
      * a staged frame carry frame.tag (Launch::tag), the per-kernel entry points carry 0 */
     uint32_t ownv_serial = 0;
     uint64_t rec_gserial[5] = {0, 0, 0, 0, 0}; /* gbuf.serial of the G-buffer each reservoir buffer's shaded bits belong to */
-    unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters */
+    unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters, then the slot of rt_occluder_hint_stats (WALK_SLOTS) */
     bool walk_on = false;
+    /* r19, rt_occluder_hints: OCCLUDER_HINTS triangle indices per pixel of the local rows (occluder_hint.h), the triangles that occluded
+     * the pixel's earlier candidate rays. Made at the first staged frame, all -1 then and after every rt_scene_set (the triangle count
+     * can shrink); rt_scene_update leaves it (an index stays an index of the scene). Read and written by the staged frame's candidates
+     * only: the per-kernel entry point passes none. */
+    int* d_hints = nullptr;
+    bool hints_on = true;
     int tune_ws_primary = -1; /* rt_tuning key 16: primary rays with the work-sharing closest-hit walk: -1 auto (r04) = launches of at
                                  most about one generation of wavefronts (a 135-row strip: -1.5 % of its frame; whole frames +2 %), 0 never, 1 always */
     int tune_stream = 0; /* rt_tuning key 15: resolve as a stream of pixels through persistent wavefronts (A/B: slower) */
@@ -516,6 +522,7 @@ int rt_destroy(rt_ctx* c)
     hipFree(c->d_shaded_bits); hipFree(c->d_mark_bits);
     hipFree(c->d_visq[0]); hipFree(c->d_visq[1]); hipFree(c->d_visq_count);
     if (c->h_visq_count) hipHostFree(c->h_visq_count);
+    hipFree(c->d_hints);
     hipFree(c->d_walk); hipFree(c->d_wire); hipFree(c->d_wave_clock);
     for (auto& p : c->d_tile_perm) hipFree(p);
     hipFree(c->d_dn_vis); hipFree(c->d_dn_gx); hipFree(c->d_dn_gn); hipFree(c->d_dn_col[0]); hipFree(c->d_dn_col[1]); hipFree(c->d_dn_hdr);
@@ -1127,6 +1134,8 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
     drop_look_ahead(c);
     c->dt_valid = false; /* rt_denoise_temporal's history belongs to the old scene */
+    /* the remembered occluders are indices of the old scene, which may have had more triangles (every stream is idle here) */
+    if (c->d_hints) RT_HIP(c, hipMemset(c->d_hints, 0xff, local_pixels(c) * sizeof(int) * OCCLUDER_HINTS));
     const auto t_build0 = std::chrono::steady_clock::now();
     free_scene(c);
     ++c->epoch;
@@ -1729,7 +1738,7 @@ static bool use_next_generate(const rt_ctx* c, bool timed)
  * is running several of them side by side (rank 4 of 8: 1080p 0.306 -> 0.287 ms, 4K 0.889 -> 0.870, profiles/r05_spec_free_ab.txt);
  * a whole frame's kernels fill the GPU alone and only take slots from each other (pipelined 1080p frame 1.277 -> 1.296 ms) */
 static bool spec_free(const rt_ctx* c) { return c->tune_spec_free < 0 ? !whole_frame(c) : c->tune_spec_free != 0; }
-static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis = nullptr);
+static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis = nullptr, bool staged = false);
 /* r05, rt_tuning key 25: raycast + generate_candidate (+ temporal merge) of a frame in ONE launch — the candidates need the primary ray
  * of their own pixel only, and two launches on a stream cost the first one's ramp-down (its last wavefront starts at 216 of 257 us).
  * The product's fused candidate kernel only (temporal merge on, unshadowed, work-sharing shadow walk), whole owned rows.
@@ -1818,7 +1827,7 @@ static int launch_next_raycast(rt_ctx* c, int frame)
         }
         c->ahead.gen_tag = next_ownv_tag(c); /* the frame that takes these candidates continues under their tag */
         spec.tag = c->ahead.gen_tag;
-        const int rc = launch_generate(c, spec, frame + 1, c->frame.spare, c->frame.Y, c->opt.use_temporal_resampling != 0, one_launch ? spec.vis : nullptr);
+        const int rc = launch_generate(c, spec, frame + 1, c->frame.spare, c->frame.Y, c->opt.use_temporal_resampling != 0, one_launch ? spec.vis : nullptr, true);
         if (rc != RT_OK) return rc;
         c->ahead.gen_valid = true;
         c->ahead.gen_frame = frame + 1;
@@ -1894,10 +1903,28 @@ static int raycast_or_take(rt_ctx* c, Launch& L, int frame, bool may_defer, Stag
     return raycast_rows(c, L);
 }
 
-static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis)
+/* the hint buffer of the staged frame's candidates (rt_occluder_hints), made on first use; nullptr = switched off */
+static int staged_hints(rt_ctx* c, int** hints)
+{
+    *hints = nullptr;
+    if (!c->hints_on || !c->d_tv) return RT_OK;
+    if (!c->d_hints)
+    {
+        const size_t bytes = local_pixels(c) * sizeof(int) * OCCLUDER_HINTS;
+        RT_HIP(c, hipMalloc(&c->d_hints, bytes));
+        RT_HIP(c, hipMemset(c->d_hints, 0xff, bytes)); /* complete before any stream's launch below: once per context */
+    }
+    *hints = c->d_hints;
+    return RT_OK;
+}
+
+/* staged: a launch of the staged frame (its stage 0 or the look-ahead's): the product's kernel then gets the context's occluder hints */
+static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis, bool staged)
 {
     if (c->n_lights == 0 && c->opt.ris_sample_count > 0)
         RT_FAIL(c, RT_ERR_STATE, "scene has no emissive triangle (the reference divides by zero here)");
+    int* hints = nullptr;
+    if (staged) { const int rc = staged_hints(c, &hints); if (rc != RT_OK) return rc; }
     const SceneView S = make_scene(c);
     const FrameParams P = make_params(c, L, frame, 0, K_GENERATE);
     const bool sh = c->opt.use_shadowed_target_function;
@@ -1946,9 +1973,9 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
     else if (fuse && c->tune_ris_pipe) k_generate_candidate<true, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
 #endif
     else if (fuse && use_ws(c, g) && raycast_vis)
-        k_generate_candidate<true, false, false, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, L.g0, L.g1);
+        k_generate_candidate<true, false, false, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, L.g0, L.g1, hints);
     else if (raycast_vis) RT_FAIL(c, RT_ERR_STATE, "the one-launch stage 0 needs the product's fused candidate kernel");
-    else if (fuse && use_ws(c, g)) k_generate_candidate<true, false, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else if (fuse && use_ws(c, g)) k_generate_candidate<true, false, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad, nullptr, nullptr, nullptr, nullptr, nullptr, hints);
     else if (fuse) k_generate_candidate<true, false><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
     else if (sh) k_generate_candidate<false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
     else k_generate_candidate<false, false><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
@@ -2640,7 +2667,7 @@ static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part,
         if (part != 1 && rc == RT_OK && !c->frame.gen_taken)
         {
             rc = join_tail_for(c, L, c->frame.Y); /* this frame's candidates may go where the previous frame's resolve still reads */
-            if (rc == RT_OK) rc = launch_generate(c, L, frame, c->frame.Y, c->frame.X, c->opt.use_temporal_resampling != 0, got.deferred ? L.vis : nullptr);
+            if (rc == RT_OK) rc = launch_generate(c, L, frame, c->frame.Y, c->frame.X, c->opt.use_temporal_resampling != 0, got.deferred ? L.vis : nullptr, true);
         }
         if (got.deferred && rc == RT_OK) rc = refresh_shaded_bits(c, L);
         mark(3);
@@ -3442,8 +3469,8 @@ int rt_walk_stats_enable(rt_ctx* c, int on)
     if (rc != RT_OK) return rc;
     if (on)
     {
-        if (!c->d_walk) RT_HIP(c, hipMalloc(&c->d_walk, 16 * 8));
-        RT_HIP(c, hipMemset(c->d_walk, 0, 16 * 8));
+        if (!c->d_walk) RT_HIP(c, hipMalloc(&c->d_walk, 4 * WALK_SLOTS * 8));
+        RT_HIP(c, hipMemset(c->d_walk, 0, 4 * WALK_SLOTS * 8));
     }
     c->walk_on = on != 0;
     /* a pipelined stage 0 enqueued before the switch carries the other setting: the next frame runs its own */
@@ -3514,6 +3541,26 @@ int rt_walk_stats(rt_ctx* c, uint64_t out[16])
     int rc = rt_sync(c);
     if (rc != RT_OK) return rc;
     RT_HIP(c, hipMemcpy(out, c->d_walk, 16 * 8, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+/* r19. A switch of its own for the reason rt_gbuffer_reuse is one. Results never depend on it (occluder_hint.h). */
+int rt_occluder_hints(rt_ctx* c, int on)
+{
+    RT_CHECK_CTX(c);
+    c->hints_on = on != 0;
+    /* a look-ahead enqueued under the other setting is not taken: the counters of rt_occluder_hint_stats follow the switch at once */
+    drop_look_ahead(c);
+    return RT_OK;
+}
+int rt_occluder_hint_stats(rt_ctx* c, uint64_t out[3])
+{
+    RT_CHECK_CTX(c);
+    if (!out) return RT_ERR_ARG;
+    if (!c->d_walk) RT_FAIL(c, RT_ERR_STATE, "rt_walk_stats_enable first");
+    int rc = rt_sync(c);
+    if (rc != RT_OK) return rc;
+    RT_HIP(c, hipMemcpy(out, c->d_walk + 4 * WALK_HINTS, 3 * 8, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -3646,6 +3693,25 @@ int rt_trace_closest(rt_ctx* c, const float* rays, uint32_t n, float* hits)
     hipEventElapsedTime(&c->last_trace_ms, e0, e1);
     hipEventDestroy(e0); hipEventDestroy(e1);
     hipFree(d_r); hipFree(d_h);
+    return RT_OK;
+}
+/* the work-sharing any-hit walk of mode RT_TRACE_OCCLUDED_WS, asked for the triangle it found: tri[i] = its index, -1 = not occluded */
+int rt_trace_occluders(rt_ctx* c, const float* rays, uint32_t n, int32_t* tri)
+{
+    RT_CHECK_CTX(c);
+    if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "no scene");
+    if (n == 0) return RT_OK;
+    if (!rays || !tri) return RT_ERR_ARG;
+    float* d_r = nullptr;
+    int* d_t = nullptr;
+    RT_HIP(c, hipMalloc(&d_r, (size_t)n * 32));
+    RT_HIP(c, hipMalloc(&d_t, (size_t)n * 4));
+    RT_HIP(c, hipMemcpyAsync(d_r, rays, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    k_trace_occluders<<<(n + TRACE_BLOCK - 1) / TRACE_BLOCK, TRACE_BLOCK, 0, c->stream>>>(make_scene(c), d_r, (int)n, d_t);
+    RT_HIP(c, hipGetLastError());
+    RT_HIP(c, hipMemcpyAsync(tri, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    hipFree(d_r); hipFree(d_t);
     return RT_OK;
 }
 /* device time of the traversal kernel of the last rt_trace_closest call */

@@ -245,6 +245,17 @@ int rt_stage0_one_launch(rt_ctx* ctx, int* one_launch);
  * RT_ERR_UNSUPPORTED. Not an rt_tuning key: tests/golden/tuning_matrix.json pins keys 29 and 30 as unknown and the table has one row
  * per key. */
 int rt_gbuffer_reuse(rt_ctx* ctx, int on);
+/* (r19) Occluder hints, default on: every pixel remembers the triangles that occluded its earlier candidate shadow rays, and the
+ * candidates of a staged frame (rt_frame, rt_frame_stage*; whole-frame and strip contexts alike) test them, most recently used first,
+ * before they walk the BVH. A remembered triangle is tested exactly, on its current vertices, with the ray's own origin, direction
+ * and range: a hit is a hit of the walk, a miss leaves the walk to run, so results never depend on the switch nor on what the buffer
+ * holds (csrc/occluder_hint.h). The buffer is made at the first staged frame, emptied by rt_scene_set, kept by rt_scene_update.
+ * The per-kernel entry point rt_generate_candidate uses none. on = 0: A/B runs. Not an rt_tuning key, as rt_gbuffer_reuse. */
+int rt_occluder_hints(rt_ctx* ctx, int on);
+/* counted while rt_walk_stats_enable is on, zeroed by it: out[0] = candidate rays that had a remembered triangle to test, out[1] = rays
+ * one of them settled (these count in rt_walk_stats' self_test of the generate_candidate slot: a one-triangle test, no walk),
+ * out[2] = triangle tests made. Synchronises. */
+int rt_occluder_hint_stats(rt_ctx* ctx, uint64_t out[3]);
 /* Unbiased spatial reuse, default off: every byte is then what it was without the call. While on,
  * rt_spatial_resampling, rt_frame and rt_frame_stage* run the spatial pass with the 1/Z normalisation of Bitterli et al. 2020 (Alg. 6)
  * whenever use_spatial_resampling = 1: Z counts only the contributors (the pixel and the merged neighbours) whose own target function
@@ -280,6 +291,9 @@ int rt_trace_closest(rt_ctx* ctx, const float* rays, uint32_t n, float* hits);
  * wide traversal the upper 16 bits of each word count the inner / leaf passes the ray's wavefront
  * executed while the ray was live (SIMT efficiency diagnostics) */
 int rt_trace_stats(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t* stats);
+/* the work-sharing any-hit walk (mode RT_TRACE_OCCLUDED_WS, whatever rt_trace_mode says) asked for the triangle it found:
+ * tri[i] = index of a triangle that occludes ray i - any of them, the walk's helpers race to report - or -1 if there is none */
+int rt_trace_occluders(rt_ctx* ctx, const float* rays, uint32_t n, int32_t* tri);
 /* BVH build knob, call before rt_scene_set: large triangles are pre-split into fragments no
  * longer than split_factor x (median triangle extent); 0 = no pre-split. Default 10. */
 int rt_bvh_config(rt_ctx* ctx, float split_factor);
