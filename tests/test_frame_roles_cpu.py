@@ -3,7 +3,8 @@
 The header is plain C++17 with no HIP include, so g++ compiles what hipcc compiles. The program below holds, beside the walk, a
 VERBATIM restatement of the integer statements rt_frame_stage_begin, raycast_or_take, rt_frame_stage_end and launch_next_raycast
 had before the header existed (the fields of rt_ctx they touched, under their old names). The walk visits EVERY state reachable
-from the start state under every per-frame choice (spatial passes 0..3, look-ahead free of the main stream or not, candidates taken
+from the start state under every per-frame choice (spatial passes 0..8: the ping-pong of pass indices 3..7 is what a frame with more
+passes than the reference's default runs, look-ahead free of the main stream or not, candidates taken
 from the look-ahead or not) and compares the two after every begin, take, pass and end.
 """
 import ctypes as C
@@ -109,7 +110,7 @@ extern "C" void walk(int* out)
     {
         const rt::FrameRoles from = todo.back();
         todo.pop_back();
-        for (int passes = 0; passes <= 3; ++passes)
+        for (int passes = 0; passes <= 8; ++passes)
             for (int free_ = 0; free_ <= 1; ++free_)
                 for (int taken = 0; taken <= 1; ++taken)
                 {
@@ -186,9 +187,9 @@ def test_roles_are_five_different_buffers_after_every_take():
 
 
 def test_the_walk_closed_over_every_reachable_state():
-    """5! orders of the buffers x 2 values of final_res = 240 states, 4 x 2 x 2 choices per state = 3 840 transitions: a walk that
+    """5! orders of the buffers x 2 values of final_res = 240 states, 9 x 2 x 2 choices per state = 8 640 transitions: a walk that
     silently visits less does not pass"""
     w = walk()
     assert (w["orders"], w["finals"]) == (120, 2)
     assert w["states"] == 240
-    assert w["transitions"] == 3840
+    assert w["transitions"] == 8640

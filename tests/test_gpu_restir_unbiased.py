@@ -143,6 +143,9 @@ CASES = [
     # a lamp in the floor's plane: the geometry term alone keeps floor neighbours out of a ramp pixel's Z, in either setting
     ("ledge", 64, 48, 1, 5, 30.0, 3, 0),
     ("ledge", 37, 29, 0, 5, 30.0, 2, 1),
+    # past the reference's defaults (tests/test_gpu_option_space.py): pass indices 3 and 4, a reach of 130 px
+    ("room", 64, 48, 1, 5, 45.0, 5, 1),
+    ("soup", 37, 29, 0, 3, 45.0, 4, 0),
 ]
 
 

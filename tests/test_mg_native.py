@@ -87,7 +87,7 @@ def _eq_bits(a, b):
 class _Rig:
     """A single full-frame context and N strip contexts + native drivers over the LOCAL transport."""
 
-    def __init__(self, api, tris, W, H, n, eye, at, optkw, flags=0, bounds=None):
+    def __init__(self, api, tris, W, H, n, eye, at, optkw, flags=0, bounds=None, halo=87):
         from cedec_2024_rt_amd.types import bench_options
 
         self.api, self.W, self.H = api, W, H
@@ -102,7 +102,7 @@ class _Rig:
             return r
 
         self.full = make()
-        self.ctxs = [make(rows=b, halo=87) for b in self.bounds]
+        self.ctxs = [make(rows=b, halo=halo) for b in self.bounds]
         self.hub = api.MgHub(len(self.bounds), renderer=self.ctxs[0])
         self.mgs = [api.MultiGpu(c, k, self.bounds, transport=api.RT_MG_TRANSPORT_LOCAL, hub=self.hub, flags=flags)
                     for k, c in enumerate(self.ctxs)]
