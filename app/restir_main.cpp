@@ -11,6 +11,7 @@
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
  *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased]
+ *              [--light-sampling uniform|power]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
  * image rows (cedec_2024_rt_amd/csrc/host_path.h: brute-force closest hit, 64 ambient-occlusion rays per pixel,
@@ -22,6 +23,8 @@
  * --denoise-temporal (with --denoise N): rt_denoise_temporal (default alphas) in place of rt_denoise, one call per frame.
  * --unbiased (--example 10, one GPU): rt_spatial_unbiased, the spatial passes normalise by 1/Z; not with
  * --shadowed 1.
+ * --light-sampling power (--example 10, also with --ranks): rt_light_sampling, the candidates pick their emissive triangle with a
+ * probability proportional to area x luminance from an alias table; uniform: the reference's, default.
  * --orbit dx dy (one GPU): before every frame from the second on, rt_camera_orbit(dx, dy) (a left-button drag); with
  * --accumulate 1 that frame starts a new accumulation, as the example clears on a camera update.
  * --move-lights dx dy dz (--example 10, also with --ranks): before every frame from the second on, the emissive triangles move
@@ -309,7 +312,7 @@ static void shared_barrier(Shared* sh, int which, int ranks)
     }
 }
 static int rank_main(int rank, int ranks, bool mirror, bool shm, bool equal_strips, const std::vector<int>& given_bounds, Shared* sh,
-                     const std::vector<rt_triangle>& triangles, int W, int H, int frames, const float* eye, const float* lookat, const rt_options& opt,
+                     const std::vector<rt_triangle>& triangles, int W, int H, int frames, const float* eye, const float* lookat, const rt_options& opt, int light_mode,
                      const std::string& pfm, const LightMove& mv)
 {
     std::vector<rt_triangle> moving = mv.on ? triangles : std::vector<rt_triangle>();
@@ -339,6 +342,7 @@ static int rank_main(int rank, int ranks, bool mirror, bool shm, bool equal_stri
         rc = rt_scene_set(ctx, triangles.data(), (uint32_t)triangles.size());
         if (rc == RT_OK) rc = rt_camera_lookat(ctx, eye, lookat, up, 3.14159265358979323846f / 4.0f);
         if (rc == RT_OK) rc = rt_options_set(ctx, &opt);
+        if (rc == RT_OK) rc = rt_light_sampling(ctx, light_mode);
         return rc;
     };
     int rc = make_ctx();
@@ -437,6 +441,7 @@ int main(int argc, char** argv)
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
     bool denoise_temporal = false, orbit = false, unbiased = false;
+    int light_mode = RT_LIGHTS_UNIFORM;
     float orbit_d[2] = {0.0f, 0.0f};
     LightMove mv;
     rt_options opt;
@@ -482,6 +487,13 @@ int main(int argc, char** argv)
         else if (a == "--denoise") denoise = atoi(argv[++i]);
         else if (a == "--denoise-temporal") denoise_temporal = true;
         else if (a == "--unbiased") unbiased = true;
+        else if (a == "--light-sampling")
+        {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m == "uniform") light_mode = RT_LIGHTS_UNIFORM;
+            else if (m == "power") light_mode = RT_LIGHTS_POWER;
+            else { fprintf(stderr, "--light-sampling uniform|power\n"); return 2; }
+        }
         else if (a == "--orbit") { orbit_d[0] = f(1); orbit_d[1] = f(2); i += 2; orbit = true; }
         else if (a == "--move-lights") { mv.d[0] = f(1); mv.d[1] = f(2); mv.d[2] = f(3); i += 3; mv.on = true; }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -491,6 +503,7 @@ int main(int argc, char** argv)
     if (denoise > 8) { fprintf(stderr, "--denoise: 0..8 iterations\n"); return 2; }
     if (denoise_temporal && denoise < 0) { fprintf(stderr, "--denoise-temporal needs --denoise N\n"); return 2; }
     if (unbiased && (ranks > 1 || example != 10)) { fprintf(stderr, "--unbiased applies to one GPU and --example 10\n"); return 2; }
+    if (light_mode != RT_LIGHTS_UNIFORM && example != 10) { fprintf(stderr, "--light-sampling applies to --example 10\n"); return 2; }
     if (orbit && (ranks > 1 || example == 4 || example == 6)) { fprintf(stderr, "--orbit applies to one GPU and --example 10, 7, 8 and 9\n"); return 2; }
     std::vector<rt_triangle> triangles = !obj.empty() ? load_obj(obj) : load_tris(tris_path);
     if (triangles.empty()) { fprintf(stderr, "no triangles (use --obj or --tris)\n"); return 2; }
@@ -574,7 +587,7 @@ int main(int argc, char** argv)
             const pid_t pid = fork();
             if (pid == 0)
             {
-                const int code = rank_main(r, ranks, mirror, shm, equal_strips, given_bounds, sh, triangles, W, H, frames, eye, lookat, opt, pfm, mv);
+                const int code = rank_main(r, ranks, mirror, shm, equal_strips, given_bounds, sh, triangles, W, H, frames, eye, lookat, opt, light_mode, pfm, mv);
                 fflush(stdout);
                 fflush(stderr);
                 _exit(code); /* no atexit handlers of the parent's image in a forked child */
@@ -602,6 +615,7 @@ int main(int argc, char** argv)
     CK(rt_camera_lookat(ctx, eye, lookat, up, 3.14159265358979323846f / 4.0f)); /* :242-251 */
     CK(rt_options_set(ctx, &opt));
     if (unbiased) CK(rt_spatial_unbiased(ctx, 1));
+    CK(rt_light_sampling(ctx, light_mode));
     CK(rt_timing_enable(ctx, 1));
     CK(rt_clear(ctx)); /* :222-226 */
 

@@ -45,11 +45,14 @@ INTERNAL_EXPORTS = [
     "rt_row_shaded", "rt_spatial_bytes", "rt_trace_closest", "rt_trace_stats", "rt_bvh_config", "rt_bvh_info", "rt_bvh_cost", "rt_build_ms",
     "rt_trace_mode", "rt_trace_time", "rt_tuning", "rt_tuning_get", "rt_math_eval", "rt_gbuffer_reuse", "rt_primary_launches",
     "rt_spatial_unbiased", "rt_spatial_unbiased_get", "rt_occluder_hints", "rt_occluder_hint_stats", "rt_trace_occluders",
+    "rt_light_sampling", "rt_light_sampling_get", "rt_light_table",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
 RT_MG_TRANSPORT_RCCL, RT_MG_TRANSPORT_LOCAL, RT_MG_TRANSPORT_MIRROR, RT_MG_TRANSPORT_SHM, RT_MG_TRANSPORT_RCCL_SELF, RT_MG_TRANSPORT_WIRE_MODEL = 0, 1, 2, 3, 4, 5
 RT_MG_TRANSPORT_MIRROR_WIRE = 6
+RT_LIGHTS_UNIFORM, RT_LIGHTS_POWER = 0, 1  # rt_light_sampling
+LIGHT_SAMPLING = {"uniform": RT_LIGHTS_UNIFORM, "power": RT_LIGHTS_POWER}
 RT_MG_DENSE, RT_MG_ONE_LANE, RT_MG_SEPARATE_PACK = 1, 2, 4
 
 
@@ -189,6 +192,10 @@ def load_library(exp=False, path=None):
         L.rt_occluder_hints.argtypes = [vp, ci]
         L.rt_occluder_hint_stats.argtypes = [vp, vp]
         L.rt_trace_occluders.argtypes = [vp, vp, C.c_uint32, vp]
+    if hasattr(L, "rt_light_sampling"):  # r21; likewise
+        L.rt_light_sampling.argtypes = [vp, ci]
+        L.rt_light_sampling_get.argtypes = [vp, vp]
+        L.rt_light_table.argtypes = [vp, vp, vp, vp, C.c_uint32]
     L.rt_visibility_rays_walked.argtypes = [vp, vp]
     L.rt_state_epoch.argtypes = [vp, vp]
     L.rt_get_stream.argtypes = [vp, vp]
@@ -784,6 +791,29 @@ class Renderer:
         v = C.c_int()
         self._ck(self.L.rt_spatial_unbiased_get(self.h, C.byref(v)))
         return bool(v.value)
+
+    def light_sampling(self, mode=None):
+        """rt_light_sampling: how the candidates pick their emissive triangle. RT_LIGHTS_UNIFORM / "uniform" (the reference's, default) or
+        RT_LIGHTS_POWER / "power" (proportional to area x luminance, from an alias table; DESIGN.md section 12). mode=None queries;
+        returns the mode as its number."""
+        if not hasattr(self.L, "rt_light_sampling"):  # an older build through RT_LIB_PATH: the mode is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_light_sampling")
+        if mode is not None:
+            if isinstance(mode, str):
+                if mode not in LIGHT_SAMPLING:
+                    raise RtError(f"light_sampling: unknown mode {mode!r}, known: {sorted(LIGHT_SAMPLING)}")
+                mode = LIGHT_SAMPLING[mode]
+            self._ck(self.L.rt_light_sampling(self.h, int(mode)))
+        v = C.c_int()
+        self._ck(self.L.rt_light_sampling_get(self.h, C.byref(v)))
+        return v.value
+
+    def light_table(self):
+        """rt_light_table: (thr, alias, K) per light of the scene, as the host built them"""
+        n = self.scene_info()["lights"]
+        thr, alias, K = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        self._ck(self.L.rt_light_table(self.h, _p(thr), _p(alias), _p(K), n))
+        return thr, alias, K
 
     def primary_launches(self):
         """launches so far that traced primary rays over the context's rows (rt_raycast, stage-0 raycasts, the one-launch stage 0,

@@ -10,6 +10,7 @@
 #include "bvh.h"
 #include "occluder_hint.h"
 #include "rt_device.h"
+#include "light_alias.h"
 
 using namespace rt;
 
@@ -119,6 +120,9 @@ struct SceneView
     const float4* __restrict__ trimat; /* 2 per triangle: {Kd.xyz, bits(emissive?)}, {Ke.xyz, 0} */
     const float4* __restrict__ lights;   /* 3 per light, see k_light_table */
     const float4* __restrict__ light_ke; /* 1 per light: {Ke.xyz, 0} */
+    /* rt_light_sampling = RT_LIGHTS_POWER, the candidates' launches only (light_alias.h): one slot per light, and `lights` is then the
+     * table whose pdf is the realised one; nullptr otherwise */
+    const AliasSlot* __restrict__ light_alias;
 };
 
 #ifndef RT_TILE_W
@@ -584,7 +588,10 @@ RT_DEV void wave_gather_records(const float4* q, float4* s_wave, const int lane,
 /* RAYCAST (r05, rt_tuning key 25): the kernel traces the pixel's primary ray first (raycast, 10_restir_di.cu:9-34) and writes the
  * Visibility record and the G-buffer (`vis_w`, `g0_w`, `g1_w`; `g0` / `g1` are not read) — generate_candidate needs the raycast of its
  * OWN pixel only, and as two launches the second waits until the first has drained (its last wavefront starts at 216 of 257 us). */
-template <bool FUSE_TEMPORAL, bool SHADOWED, bool DEFER = false, bool PIPE = false, bool WS = false, bool RAYCAST = false>
+/* POWER (r21, rt_light_sampling): the light of a candidate comes from the alias table (light_alias.h) instead of
+ * the uniform index: a fifth draw `ra` directly after rv0, one 8-byte slot gathered per lane, and S.lights holds the realised pdf. A
+ * template parameter: the kernels of the uniform mode are compiled from the text they had. */
+template <bool FUSE_TEMPORAL, bool SHADOWED, bool DEFER = false, bool PIPE = false, bool WS = false, bool RAYCAST = false, bool POWER = false>
 __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED ? RT_GENERATE_SH_WAVES : RT_TRACE_WAVES)) void k_generate_candidate(
     SceneView S, FrameParams P, const float4* __restrict__ g0, const float4* __restrict__ g1,
     const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad, float4* __restrict__ out_rec,
@@ -659,11 +666,14 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
             if (act)
             {
                 const float rv0 = rng.uniformf_chained();
+                float ra = 0.0f;
+                if constexpr (POWER) ra = rng.uniformf_chained();
                 bx_n = rng.uniformf_chained();
                 by_n = rng.uniformf_chained();
                 u_n = rng.uniformf_chained();
                 nth_n = (uint32_t)(rv0 * fL);
                 if (nth_n == (uint32_t)P.n_lights) nth_n = (uint32_t)P.n_lights - 1u;
+                if constexpr (POWER) nth_n = light_select_slot(S.light_alias[nth_n], nth_n, ra);
             }
             wave_gather_request_at(S.lights, nth_n, s_img, lane);
         };
@@ -699,10 +709,13 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
             if (act)
             {
                 const float rv0 = rng.uniformf();
+                float ra = 0.0f;
+                if constexpr (POWER) ra = rng.uniformf();
                 bx = rng.uniformf();
                 by = rng.uniformf();
                 nth = (uint32_t)(rv0 * fL);
                 if (nth == (uint32_t)P.n_lights) nth = (uint32_t)P.n_lights - 1u;
+                if constexpr (POWER) nth = light_select_slot(S.light_alias[nth], nth, ra);
             }
             float4 L0, L1, L2, L3n;
             wave_gather_records_at(S.lights, nth, s_img, lane, L0, L1, L2, L3n);
@@ -743,6 +756,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
             const float rv0 = rng.uniformf();
             nth = (uint32_t)(rv0 * fL);
             if (nth == (uint32_t)P.n_lights) nth = (uint32_t)P.n_lights - 1u;
+            if constexpr (POWER) nth = light_select_slot(S.light_alias[nth], nth, rng.uniformf());
             const float4* L = S.lights + RT_LIGHT_STRIDE * (size_t)nth;
             C0 = L[0]; C1 = L[1]; C2 = L[2]; C3 = L[3];
         }
@@ -758,6 +772,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
                 const float rv0n = rng.uniformf();
                 nth_n = (uint32_t)(rv0n * fL);
                 if (nth_n == (uint32_t)P.n_lights) nth_n = (uint32_t)P.n_lights - 1u;
+                if constexpr (POWER) nth_n = light_select_slot(S.light_alias[nth_n], nth_n, rng.uniformf());
                 const float4* Ln = S.lights + RT_LIGHT_STRIDE * (size_t)nth_n;
                 N0 = Ln[0]; N1 = Ln[1]; N2 = Ln[2]; N3 = Ln[3];
             }
@@ -779,13 +794,16 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     else
     for (int i = 0; i < P.ris_sample_count; ++i)
     {
-        /* draw order rv0, rv1, rv2, u: left-to-right argument evaluation (hipcc) */
+        /* draw order rv0, rv1, rv2, u: left-to-right argument evaluation (hipcc); POWER: rv0, ra, rv1, rv2, u */
         const float rv0 = rng.uniformf();
+        float ra = 0.0f;
+        if constexpr (POWER) ra = rng.uniformf();
         float bx = rng.uniformf();
         float by = rng.uniformf();
         /* common/core.hpp:261-285 */
         uint32_t nth = (uint32_t)(rv0 * fL);
         if (nth == (uint32_t)P.n_lights) nth = (uint32_t)P.n_lights - 1u;
+        if constexpr (POWER) nth = light_select_slot(S.light_alias[nth], nth, ra);
         /* 64-B light record: vertices + luminance(Ke) + pdf + the geometric normal (the reference's
          * exact expression, common/core.hpp:50-55, evaluated once at scene set: the loop is bound by
          * vector-ALU issue and a normalize costs 3 IEEE divisions + a square root); Ke is fetched
@@ -3186,8 +3204,10 @@ __global__ void k_refresh_shaded(int n, const float4* __restrict__ g1, float4* _
  *   {v0.xyz, v1.x} {v1.yz, v2.xy} {v2.z, luminance(Ke), pdf, bits(tri)}   + a side table {Ke.xyz, 0}
  * pdf = 1/L * 1/area_of — the exact expression of common/core.hpp:57-62 and
  * 10_restir_di.cu:98-99, evaluated once instead of once per candidate. */
+/* sel_prob (rt_light_sampling's second table, light_alias.h): the probability the alias table selects light i with, in place of 1/L;
+ * a light it never selects (0) gets a pdf of 0 that nothing reads. nullptr = the reference's table. */
 __global__ void k_light_table(int n_lights, const uint32_t* __restrict__ light_ids, const float* __restrict__ tris,
-                              float4* __restrict__ lights, float4* __restrict__ light_ke)
+                              float4* __restrict__ lights, float4* __restrict__ light_ke, const float* __restrict__ sel_prob = nullptr)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_lights) return;
@@ -3195,7 +3215,7 @@ __global__ void k_light_table(int n_lights, const uint32_t* __restrict__ light_i
     const float* t = tris + 15 * (size_t)ti;
     const f3 v0 = F3(t[0], t[1], t[2]), v1 = F3(t[3], t[4], t[5]), v2 = F3(t[6], t[7], t[8]);
     const f3 ke = F3(t[12], t[13], t[14]);
-    const float pdf = 1.0f / (float)(size_t)n_lights * 1.0f / tri_area(v0, v1, v2);
+    const float pdf = (sel_prob ? sel_prob[i] : 1.0f / (float)(size_t)n_lights) * 1.0f / tri_area(v0, v1, v2);
     float4* L = lights + RT_LIGHT_STRIDE * (size_t)i;
     L[0] = make_float4(v0.x, v0.y, v0.z, v1.x);
     L[1] = make_float4(v1.y, v1.z, v2.x, v2.y);

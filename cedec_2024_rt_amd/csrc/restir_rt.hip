@@ -166,6 +166,15 @@ struct rt_ctx
     /* rt_scene_update: the light list in index order (host), its device copy, the refit's level lists (built at the first
      * update of a scene: refit_off[l] .. refit_off[l + 1] = inner records of level l), its box scratch and the scene bounds */
     std::vector<uint32_t> h_lights;
+    /* rt_light_sampling (light_alias.h): the mode, per-light host weights (so that rt_scene_update needs only its
+     * span), the alias table with its realised counts, and on the device the table and a second light table whose pdf is the realised one */
+    int light_mode = RT_LIGHTS_UNIFORM;
+    std::vector<float> h_light_w;
+    std::vector<AliasSlot> h_alias;
+    std::vector<uint64_t> h_alias_K;
+    bool alias_ok = false; /* some light has q > 0 */
+    float4* d_lights_power = nullptr;
+    AliasSlot* d_alias = nullptr;
     uint32_t* d_light_ids = nullptr;
     uint32_t* d_refit_list = nullptr;
     float* d_refit_box = nullptr;
@@ -393,6 +402,7 @@ static SceneView make_scene(const rt_ctx* c)
     S.bvh.nodes = c->d_nodes; S.bvh.tv = c->d_tv; S.bvh.n_tris = c->n_tris;
     S.wide.rec = c->d_wide; S.wide.n_tris = c->n_tris; S.wide.n_rec = c->n_wide;
     S.trimat = c->d_trimat; S.lights = c->d_lights; S.light_ke = c->d_light_ke;
+    S.light_alias = nullptr;
     return S;
 }
 static size_t local_pixels(const rt_ctx* c) { return (size_t)c->W * (size_t)c->lrows; }
@@ -482,6 +492,9 @@ int rt_create(int device, int width, int height, int row_begin, int row_end, int
 static void free_scene(rt_ctx* c)
 {
     hipFree(c->d_tris); hipFree(c->d_tv); hipFree(c->d_nodes); hipFree(c->d_trimat); hipFree(c->d_lights); hipFree(c->d_light_ke); hipFree(c->d_wide);
+    hipFree(c->d_lights_power); hipFree(c->d_alias);
+    c->d_lights_power = nullptr; c->d_alias = nullptr;
+    c->h_light_w.clear(); c->h_alias.clear(); c->h_alias_K.clear(); c->alias_ok = false;
     hipFree(c->d_light_ids); hipFree(c->d_refit_list); hipFree(c->d_refit_box); hipFree(c->d_refit_bounds);
     c->d_light_ids = nullptr; c->d_refit_list = nullptr; c->d_refit_box = nullptr; c->d_refit_bounds = nullptr;
     if (c->d_frag_uv) hipFree(c->d_frag_uv); /* only a scene that was updated has them: a static scene's rt_scene_set makes no call for them */
@@ -1122,6 +1135,47 @@ static int build_bvh(rt_ctx* c, const rt_triangle* tris, int n_tris)
     return build_wide(c, tris, n);
 }
 
+static float light_weight_of(const rt_triangle& t)
+{
+    return light_weight(F3(t.v[0][0], t.v[0][1], t.v[0][2]), F3(t.v[1][0], t.v[1][1], t.v[1][2]), F3(t.v[2][0], t.v[2][1], t.v[2][2]),
+                        F3(t.emissive[0], t.emissive[1], t.emissive[2]));
+}
+/* The alias table of rt_light_sampling from the per-light weights `w` (host, light_alias.h), uploaded next to d_lights with the light
+ * table of the realised pdf. d_ids: the light list on the device; resize: the number of lights changed. Enqueues on `st`; the host
+ * arrays it copies from stay until the caller's synchronisation (they are members). */
+static int build_light_alias(rt_ctx* c, std::vector<float>& w, const uint32_t* d_ids, bool resize, hipStream_t st)
+{
+    const uint32_t L = (uint32_t)w.size();
+    if (resize || !c->d_alias)
+    {
+        hipFree(c->d_lights_power); hipFree(c->d_alias);
+        c->d_lights_power = nullptr; c->d_alias = nullptr;
+    }
+    c->h_light_w.swap(w);
+    c->alias_ok = alias_build(c->h_light_w.data(), L, c->h_alias, c->h_alias_K);
+    if (L == 0) return RT_OK;
+    if (!c->d_alias)
+    {
+        RT_HIP(c, hipMalloc(&c->d_alias, (size_t)L * sizeof(AliasSlot)));
+        RT_HIP(c, hipMalloc(&c->d_lights_power, (size_t)L * 16 * RT_LIGHT_STRIDE));
+    }
+    std::vector<float> prob(L);
+    for (uint32_t i = 0; i < L; ++i) prob[i] = light_select_prob(c->h_alias_K[i], L);
+    float* d_prob = nullptr;
+    RT_HIP(c, hipMalloc(&d_prob, (size_t)L * 4));
+    hipError_t e = hipMemcpyAsync(d_prob, prob.data(), (size_t)L * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_alias, c->h_alias.data(), (size_t)L * sizeof(AliasSlot), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+    {
+        k_light_table<<<((int)L + 255) / 256, 256, 0, st>>>((int)L, d_ids, c->d_tris, c->d_lights_power, c->d_light_ke, d_prob);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st); /* `prob` is host memory */
+    hipFree(d_prob);
+    if (e != hipSuccess) RT_FAIL(c, RT_ERR_HIP, "light alias table: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
 int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
 {
     RT_CHECK_CTX(c);
@@ -1164,8 +1218,12 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
         RT_HIP(c, hipMalloc(&c->d_light_ke, lights.size() * 16));
         k_light_table<<<(c->n_lights + 255) / 256, 256, 0, c->stream>>>(c->n_lights, d_ids, c->d_tris, c->d_lights, c->d_light_ke);
         RT_HIP(c, hipGetLastError());
+        std::vector<float> w(lights.size());
+        for (size_t i = 0; i < lights.size(); ++i) w[i] = light_weight_of(triangles[lights[i]]);
+        const int ra = build_light_alias(c, w, d_ids, true, c->stream);
         RT_HIP(c, hipStreamSynchronize(c->stream));
         hipFree(d_ids);
+        if (ra != RT_OK) return ra;
     }
     const int rc = build_bvh(c, triangles, n);
     if (rc != RT_OK) return rc;
@@ -1361,15 +1419,24 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     hipStream_t st = c->stream;
     /* light list: the ids below and above the span stay, the span's are taken from the new triangles (index order) */
     std::vector<uint32_t> lights;
+    std::vector<float> light_w; /* the weights likewise: those of the span from the new triangles (rt_light_sampling) */
+    bool span_has_light = false;
     {
         const auto lo = std::lower_bound(c->h_lights.begin(), c->h_lights.end(), first);
         const auto hi = std::lower_bound(lo, c->h_lights.end(), first + count); /* <= n_tris: no wrap */
         lights.reserve(c->h_lights.size());
         lights.insert(lights.end(), c->h_lights.begin(), lo);
+        light_w.reserve(c->h_lights.size());
+        light_w.insert(light_w.end(), c->h_light_w.begin(), c->h_light_w.begin() + (lo - c->h_lights.begin()));
         for (uint32_t i = 0; i < count; ++i)
             if (triangles[i].emissive[0] > 0.0f || triangles[i].emissive[1] > 0.0f || triangles[i].emissive[2] > 0.0f)
+            {
                 lights.push_back(first + i);
+                light_w.push_back(light_weight_of(triangles[i]));
+                span_has_light = true;
+            }
         lights.insert(lights.end(), hi, c->h_lights.end());
+        light_w.insert(light_w.end(), c->h_light_w.begin() + (hi - c->h_lights.begin()), c->h_light_w.end());
     }
     if (lights.size() > ((size_t)1 << 26)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "more than 2^26 emissive triangles (the light table is addressed by 32-bit byte offsets)");
     if (c->refit_off.empty()) { const int rc = refit_topology(c); if (rc != RT_OK) return rc; }
@@ -1398,6 +1465,12 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
         if (upload) RT_HIP(c, hipMemcpyAsync(c->d_light_ids, lights.data(), lights.size() * 4, hipMemcpyHostToDevice, st));
         k_light_table<<<((int)lights.size() + 255) / 256, 256, 0, st>>>((int)lights.size(), c->d_light_ids, c->d_tris, c->d_lights, c->d_light_ke);
         RT_HIP(c, hipGetLastError());
+    }
+    /* the alias table: only if a weight or the list can have changed (the span holds a light now, or held one) */
+    if (span_has_light || lights != c->h_lights)
+    {
+        const int ra = build_light_alias(c, light_w, c->d_light_ids, lights.size() != c->h_lights.size(), st);
+        if (ra != RT_OK) return ra;
     }
     c->n_lights = (int)lights.size();
     /* refit: the pad's bounds grown by the span, then the inner records level by level, deepest first */
@@ -1925,13 +1998,26 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
         RT_FAIL(c, RT_ERR_STATE, "scene has no emissive triangle (the reference divides by zero here)");
     int* hints = nullptr;
     if (staged) { const int rc = staged_hints(c, &hints); if (rc != RT_OK) return rc; }
-    const SceneView S = make_scene(c);
+    SceneView S = make_scene(c);
+    const bool power = c->light_mode == RT_LIGHTS_POWER && c->opt.ris_sample_count > 0;
+    if (power)
+    {
+        if (!c->alias_ok) RT_FAIL(c, RT_ERR_STATE, "rt_light_sampling: no light of the scene has a positive finite area x luminance");
+        S.lights = c->d_lights_power;
+        S.light_alias = c->d_alias;
+    }
     const FrameParams P = make_params(c, L, frame, 0, K_GENERATE);
     const bool sh = c->opt.use_shadowed_target_function;
     float4 *orec = c->d_rec[dst_phys], *orad = c->d_rad[dst_phys];
     c->rec_gserial[dst_phys] = c->gbuf.serial;
     const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
     const int g = trace_grid(c, L);
+    /* every form of the kernel in both light samplings: <fused, shadowed, deferred, pipelined, work-sharing, with primary rays> */
+#define GEN_LAUNCH(FT, SH, DF, PP, WS_, RC, ...)                                                                                  \
+    do {                                                                                                                          \
+        if (power) k_generate_candidate<FT, SH, DF, PP, WS_, RC, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);              \
+        else k_generate_candidate<FT, SH, DF, PP, WS_, RC><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);                          \
+    } while (0)
 #ifdef RT_EXPERIMENTS
     if (fuse && !sh && c->tune_defer_vis)
     {
@@ -1949,8 +2035,8 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
         }
         if (c->visq_epoch != c->epoch) { c->h_visq_count[0] = c->h_visq_count[1] = 0xffffffffu; c->visq_epoch = c->epoch; }
         RT_HIP(c, hipMemsetAsync(c->d_visq_count + lane, 0, 4, L.stream));
-        if (c->tune_ris_pipe) k_generate_candidate<true, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
-        else k_generate_candidate<true, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
+        if (c->tune_ris_pipe) GEN_LAUNCH(true, false, true, true, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
+        else GEN_LAUNCH(true, false, true, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
         RT_HIP(c, hipGetLastError());
         /* grid of the walk: one queue entry per lane if the count is like the last one that reached the host (+50 %),
          * every pixel of the launch if that is unknown (first frame, camera / option change); the kernel's stride loop
@@ -1968,17 +2054,18 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
         return RT_OK;
     }
 #endif
-    if (fuse && sh) k_generate_candidate<true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
+    if (fuse && sh) GEN_LAUNCH(true, true, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
 #ifdef RT_EXPERIMENTS
-    else if (fuse && c->tune_ris_pipe) k_generate_candidate<true, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else if (fuse && c->tune_ris_pipe) GEN_LAUNCH(true, false, false, true, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
 #endif
     else if (fuse && use_ws(c, g) && raycast_vis)
-        k_generate_candidate<true, false, false, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, L.g0, L.g1, hints);
+        GEN_LAUNCH(true, false, false, false, true, true, S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, L.g0, L.g1, hints);
     else if (raycast_vis) RT_FAIL(c, RT_ERR_STATE, "the one-launch stage 0 needs the product's fused candidate kernel");
-    else if (fuse && use_ws(c, g)) k_generate_candidate<true, false, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad, nullptr, nullptr, nullptr, nullptr, nullptr, hints);
-    else if (fuse) k_generate_candidate<true, false><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
-    else if (sh) k_generate_candidate<false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
-    else k_generate_candidate<false, false><<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else if (fuse && use_ws(c, g)) GEN_LAUNCH(true, false, false, false, true, false, S, P, L.g0, L.g1, prec, prad, orec, orad, nullptr, nullptr, nullptr, nullptr, nullptr, hints);
+    else if (fuse) GEN_LAUNCH(true, false, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else if (sh) GEN_LAUNCH(false, true, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else GEN_LAUNCH(false, false, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
+#undef GEN_LAUNCH
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }
@@ -2896,6 +2983,38 @@ int rt_spatial_unbiased_get(rt_ctx* c, int* on)
     RT_CHECK_CTX(c);
     if (!on) return RT_ERR_ARG;
     *on = c->spatial_unbiased ? 1 : 0;
+    return RT_OK;
+}
+/* How the candidates pick their light (light_alias.h). Changes results, so not an rt_tuning key; counts as an
+ * option change (rt_state_epoch) and drops the look-ahead, whose stage 0 drew its candidates under the other setting. Touches no
+ * buffer: a stored record carries a contribution weight, valid under either sampling. */
+int rt_light_sampling(rt_ctx* c, int mode)
+{
+    RT_CHECK_CTX(c);
+    if (mode != RT_LIGHTS_UNIFORM && mode != RT_LIGHTS_POWER) RT_FAIL(c, RT_ERR_ARG, "rt_light_sampling: unknown mode %d", mode);
+    c->light_mode = mode;
+    drop_look_ahead(c);
+    ++c->epoch;
+    return RT_OK;
+}
+int rt_light_sampling_get(rt_ctx* c, int* mode)
+{
+    RT_CHECK_CTX(c);
+    if (!mode) return RT_ERR_ARG;
+    *mode = c->light_mode;
+    return RT_OK;
+}
+int rt_light_table(rt_ctx* c, uint32_t* thr, uint32_t* alias, uint64_t* K, uint32_t n)
+{
+    RT_CHECK_CTX(c);
+    if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "rt_light_table before rt_scene_set");
+    if (n != (uint32_t)c->n_lights) RT_FAIL(c, RT_ERR_ARG, "rt_light_table: %u entries asked for, the scene has %d lights", n, c->n_lights);
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        if (thr) thr[i] = c->h_alias[i].thr;
+        if (alias) alias[i] = c->h_alias[i].alias;
+        if (K) K[i] = c->h_alias_K[i];
+    }
     return RT_OK;
 }
 int rt_primary_launches(rt_ctx* c, uint64_t* n)

@@ -272,6 +272,21 @@ int rt_occluder_hint_stats(rt_ctx* ctx, uint64_t out[3]);
  * answered: the slot's sum is the pass's own rays, not the reference's. Not an rt_tuning key: tuning keys never change results. */
 int rt_spatial_unbiased(rt_ctx* ctx, int on);
 int rt_spatial_unbiased_get(rt_ctx* ctx, int* on);
+/* Light selection of the ReSTIR candidates, default RT_LIGHTS_UNIFORM: every byte is then what it was without
+ * the call. RT_LIGHTS_POWER: a candidate's emissive triangle is drawn with a probability proportional to area x luminance(Ke) from an
+ * alias table built on the host at rt_scene_set / rt_scene_update (csrc/light_alias.h), with one more random number per candidate
+ * (rv0, ra, bx, by, u); the pdf divided by is the one the table realises, so the estimate keeps its expectation. A property of the
+ * context, set before or after the scene, on whole-frame and strip contexts alike (every strip of an rt_mg_frame must be given the
+ * same mode); applies to rt_generate_candidate, rt_frame, rt_frame_stage* and rt_mg_frame, not to rt_path_trace. The call changes
+ * rt_state_epoch and drops look-ahead work, touches no buffer and needs no new temporal history. Unknown mode: RT_ERR_ARG. A scene
+ * in which no light has a positive finite area x luminance: RT_ERR_STATE from the launching call while the mode is RT_LIGHTS_POWER
+ * and ris_sample_count > 0. Not an rt_tuning key: tuning keys never change results. */
+enum { RT_LIGHTS_UNIFORM = 0 /* the reference's, default */, RT_LIGHTS_POWER = 1 };
+int rt_light_sampling(rt_ctx* ctx, int mode);
+int rt_light_sampling_get(rt_ctx* ctx, int* mode);
+/* the alias table and the realised counts (thr / alias / K per light, light list order; any pointer may be null), for tests; n = the
+ * scene's light count (RT_ERR_ARG otherwise); RT_ERR_STATE without a scene */
+int rt_light_table(rt_ctx* ctx, uint32_t* thr, uint32_t* alias, uint64_t* K, uint32_t n);
 /* launches so far that traced primary rays over the context's rows: rt_raycast, stage-0 raycasts, the one-launch stage 0 and
  * look-ahead raycasts (counted when launched, taken or not). How the tests see reuse without timing anything. */
 int rt_primary_launches(rt_ctx* ctx, uint64_t* n);
