@@ -44,7 +44,7 @@ INTERNAL_EXPORTS = [
     "rt_mg_selftest_rccl", "rt_visibility_rays_walked", "rt_walk_stats_enable", "rt_walk_stats", "rt_stage0_one_launch",
     "rt_row_shaded", "rt_spatial_bytes", "rt_trace_closest", "rt_trace_stats", "rt_bvh_config", "rt_bvh_info", "rt_bvh_cost", "rt_build_ms",
     "rt_trace_mode", "rt_trace_time", "rt_tuning", "rt_tuning_get", "rt_math_eval", "rt_gbuffer_reuse", "rt_primary_launches",
-    "rt_spatial_unbiased", "rt_spatial_unbiased_get", "rt_occluder_hints", "rt_occluder_hint_stats", "rt_trace_occluders",
+    "rt_spatial_unbiased", "rt_spatial_unbiased_get", "rt_occluder_hints", "rt_occluder_hint_stats", "rt_neighbour_pick", "rt_neighbour_pick_stats", "rt_trace_occluders",
     "rt_light_sampling", "rt_light_sampling_get", "rt_light_table",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
@@ -192,6 +192,9 @@ def load_library(exp=False, path=None):
         L.rt_occluder_hints.argtypes = [vp, ci]
         L.rt_occluder_hint_stats.argtypes = [vp, vp]
         L.rt_trace_occluders.argtypes = [vp, vp, C.c_uint32, vp]
+    if hasattr(L, "rt_neighbour_pick"):  # r22; likewise
+        L.rt_neighbour_pick.argtypes = [vp, ci]
+        L.rt_neighbour_pick_stats.argtypes = [vp, vp]
     if hasattr(L, "rt_light_sampling"):  # r21; likewise
         L.rt_light_sampling.argtypes = [vp, ci]
         L.rt_light_sampling_get.argtypes = [vp, vp]
@@ -773,6 +776,23 @@ class Renderer:
         self._ck(self.L.rt_occluder_hint_stats(self.h, _p(a)))
         return dict(rays_with_hint=int(a[0]), settled=int(a[1]), tests=int(a[2]))
 
+    def neighbour_pick(self, mode):
+        """how the unshadowed spatial pass picks its neighbours (rt_neighbour_pick): 1 hardware transcendentals behind an interval
+        guard (default), 0 the portable functions only, 2 the guard forced to fail. The same bytes in every mode. A library without
+        the call computes the portable functions: mode 0 is then a no-op and anything else an error."""
+        if not hasattr(self.L, "rt_neighbour_pick"):
+            if mode != 0:
+                raise RtError("this build of librestir_rt has no rt_neighbour_pick")
+            return
+        self._ck(self.L.rt_neighbour_pick(self.h, int(mode)))
+
+    def neighbour_pick_stats(self):
+        """while walk_stats_enable is on: neighbour picks the unshadowed spatial pass made, and the near ties among them (lanes the
+        guard sent to the portable functions)"""
+        a = np.zeros(2, dtype=np.uint64)
+        self._ck(self.L.rt_neighbour_pick_stats(self.h, _p(a)))
+        return dict(picks=int(a[0]), near_ties=int(a[1]))
+
     def trace_occluders(self, rays):
         """the work-sharing any-hit walk asked for its occluder: per ray the index of a triangle that occludes it, -1 = none"""
         r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
@@ -903,7 +923,7 @@ class Renderer:
 
     def math_eval(self, fn, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
-        n = x.size // {26: 2, 33: 2, 35: 2, 31: 12, 32: 12, 36: 3, 37: 3, 38: 14}.get(fn, 1)
+        n = x.size // {26: 2, 33: 2, 35: 2, 31: 12, 32: 12, 36: 3, 37: 3, 38: 14, 45: 5}.get(fn, 1)
         out = np.zeros(n, dtype=np.float32)
         self._ck(self.L.rt_math_eval(self.h, int(fn), _p(x), n, _p(out)))
         return out

@@ -33,6 +33,7 @@ struct FrameParams
     float spatial_radius;
     int tile_mode; /* workgroup -> tile order inside an XCD's band: 0 row-major, 1 column-major; 2 / 3: tile rows interleaved over the XCDs, row- / column-major */
     uint32_t ownv_tag; /* own-visibility flags are written / trusted under this tag only (rt_device.h); 0 = never */
+    int pick_mode; /* RT_TUNE_SPATIAL_PICK (neighbour_pick.h): how k_spatial_coop picks its neighbours; the same integers in every mode */
     /* rt_walk_stats (measurement, off = nullptr: one wave-uniform test per kernel): 4 counters per kernel slot
      * {rays the reference traces here, walked through the BVH, settled by the one-triangle self-occlusion test, not evaluated
      * (answer known from the own-visibility flags, or unobservable)}; slots WALK_RAYCAST .. WALK_RESOLVE */
@@ -73,7 +74,8 @@ struct WaveClock
 #else
 #define RT_WAVE_CLOCK(P)
 #endif
-enum { WALK_RAYCAST = 0, WALK_GENERATE = 1, WALK_SPATIAL = 2, WALK_RESOLVE = 3, WALK_HINTS = 4 /* rt_occluder_hint_stats: {rays with a hint to test, settled by one, triangle tests, -} */, WALK_SLOTS = 5 };
+enum { WALK_RAYCAST = 0, WALK_GENERATE = 1, WALK_SPATIAL = 2, WALK_RESOLVE = 3, WALK_HINTS = 4 /* rt_occluder_hint_stats: {rays with a hint to test, settled by one, triangle tests, -} */,
+       WALK_PICKS = 5 /* rt_neighbour_pick_stats: {neighbour picks of k_spatial_coop, near ties (lanes on the exact path), -, -} */, WALK_SLOTS = 6 };
 /* one ray per lane at most; works under any exec mask (ballots count the active lanes) */
 RT_DEV void count_walk_flags(unsigned long long* __restrict__ st, bool ref, bool walked, bool self, bool skipped)
 {
@@ -1796,6 +1798,7 @@ RT_DEV void spatial_coop_wave(const FrameParams& P, const HaloFuse& F, const flo
     if (P.use_spatial)
     {
         const float scale = P.spatial_radius / 1.96f;
+        const float pick_E = neighbour_pick_bound(scale);
         /* rejection_heuristics' first distance is that of r's origin: the own one until a neighbour's sample is taken, that
          * neighbour's from then on (res_take_sample copies the origin) - the same expression on the same operands */
         float d0 = length(r.org_p - P.eye);
@@ -1809,14 +1812,11 @@ RT_DEV void spatial_coop_wave(const FrameParams& P, const HaloFuse& F, const flo
             {
                 const float rv0 = rng.uniformf();
                 const float rv1 = rng.uniformf();
-                /* common/reservoir.hpp:89-95 with portable log/cos/sin */
-                const float radius = sqrt_guarded(fmax_dev(-2.0f * pm_logf(rv0), 0.0f));
-                const float phi = 2.0f * kPI * rv1;
-                float sn_phi, cs_phi;
-                pm_sincosf(phi, &sn_phi, &cs_phi);
-                const float gx = radius * cs_phi, gy = radius * sn_phi;
-                const int nx = f2i_sat((float)x + scale * gx);
-                const int ny = f2i_sat((float)yi + scale * gy);
+                /* common/reservoir.hpp:89-95: the hardware's log2 / sqrt / sin / cos where the interval guard proves the two integers
+                 * are the portable functions' ones, those functions themselves on the other lanes (neighbour_pick.h) */
+                int nx, ny;
+                const bool near_tie = neighbour_pick(P.pick_mode, rv0, rv1, x, yi, scale, pick_E, &nx, &ny);
+                if (P.stats) count_walk_flags(P.stats + 4 * WALK_PICKS, true, near_tie && P.pick_mode != PICK_EXACT, false, false);
                 const int nrow = P.H - 1 - ny;
                 const int lr = nrow - P.lrow0;
                 have = !(nx < 0 || nx >= P.W || ny < 0 || ny >= P.H) && !(nx == x && ny == yi) && !(lr < 0 || lr >= P.lrows);
@@ -3533,6 +3533,29 @@ __global__ void k_math_eval(int fn, const float* __restrict__ in, int n, float* 
             const float lum = q[12], pdf = q[13];
             const float r1 = div_den_ok(pdf) ? rcp_refined(pdf) : as_float(0x7fc00000u); /* as k_light_table stores it */
             r = as_float(as_uint(ris_weight(sp, sn, lp, ln, lum, pdf, r1)) ^ as_uint(target_unshadowed(sp, sn, lp, ln, lum) / pdf));
+            break;
+        }
+        /* r22 neighbour_pick.h. 39 / 40: the fast and the exact radius of the draw rv0; 41 / 42: the hardware's sin / cos of the draw
+         * rv1 (revolutions); 43 / 44: the portable sin / cos of the angle the exact pick forms from rv1 (tools/pick_error_sweep.py) */
+        case 39: r = neighbour_pick_fast_radius(in[i]); break;
+        case 40: r = sqrt_guarded(fmax_dev(-2.0f * pm_logf(in[i]), 0.0f)); break;
+        case 41: r = hw_sin_rev(in[i]); break;
+        case 42: r = hw_cos_rev(in[i]); break;
+        case 43: { float sn, cs; pm_sincosf(2.0f * kPI * in[i], &sn, &cs); r = sn; break; }
+        case 44: { float sn, cs; pm_sincosf(2.0f * kPI * in[i], &sn, &cs); r = cs; break; }
+        /* 45: the pick three ways; in: rv0 rv1 x yi scale (5, x and yi as floats). Bit 0: the guard passed; bit 1: it passed and its
+         * integers are not the exact ones; bit 2 / 3: neighbour_pick in mode PICK_FAST / PICK_FORCE_SLOW differs from the exact pick */
+        case 45:
+        {
+            const float* q = in + 5 * (size_t)i;
+            const int x = (int)q[2], yi = (int)q[3];
+            const float scale = q[4], E = neighbour_pick_bound(scale);
+            int ex, ey, fx, fy, ax, ay, bx, by;
+            neighbour_pick_exact(q[0], q[1], x, yi, scale, &ex, &ey);
+            const bool ok = neighbour_pick_fast(q[0], q[1], x, yi, scale, E, &fx, &fy);
+            neighbour_pick(PICK_FAST, q[0], q[1], x, yi, scale, E, &ax, &ay);
+            neighbour_pick(PICK_FORCE_SLOW, q[0], q[1], x, yi, scale, E, &bx, &by);
+            r = as_float((ok ? 1u : 0u) | ((ok && (fx != ex || fy != ey)) ? 2u : 0u) | ((ax != ex || ay != ey) ? 4u : 0u) | ((bx != ex || by != ey) ? 8u : 0u));
             break;
         }
         default: break;

@@ -38,6 +38,7 @@ static_assert(sizeof(rt_raygen) == 36, "RayGenerator layout (common/camera.hpp:5
 static_assert(sizeof(BvhNode) == 64, "BVH node");
 static_assert(ROLE_RES_0 == RT_RES_0 && ROLE_RES_1 == RT_RES_1 && ROLE_RES_TEMPORAL == RT_RES_TEMPORAL, "frame_roles.h names the reservoir buffers as restir_rt.h does");
 
+#include "neighbour_pick.h"
 #include "frame_kernels.h"
 #include "host_path.h"
 #include "bvh_build_host.h"
@@ -127,6 +128,7 @@ struct rt_ctx
                                                     spatial pass keeps an XCD's band of tile rows, column by column (its +-87-px
                                                     neighbour window must stay in that XCD's L2); profiles/r05_tile_interleave_ab.txt */
     int tune_spatial_lds = 0;     /* rt_tuning key 4: extra dynamic LDS per unshadowed spatial workgroup (A/B of the old throttle) */
+    int pick_mode = PICK_FAST; /* rt_neighbour_pick (r22): k_spatial_coop's neighbour pick, neighbour_pick.h; the same integers in every mode */
     int tune_spatial_variant = 2; /* rt_tuning key 8: 2 = k_spatial_coop (default: four lanes per record, LDS-DMA gathers, transposed
                                      stores), 0 = k_spatial_gather (one per-lane gather per neighbour), 1 = k_spatial_lds (staged
                                      shaded-bit window; falls back to 0 where it does not apply) */
@@ -382,6 +384,7 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
         P.tile_mode = c->tune_tile_mode[kernel] >= 0 ? c->tune_tile_mode[kernel] : autom;
     }
     P.ownv_tag = L.tag;
+    P.pick_mode = c->pick_mode;
     P.stats = c->walk_on ? c->d_walk : nullptr;
 #ifdef RT_EXPERIMENTS
     P.wave_clock = c->d_wave_clock && kernel == c->wave_clock_kernel && (kernel != K_SPATIAL || pass == c->wave_clock_pass) ? c->d_wave_clock : nullptr;
@@ -3683,6 +3686,25 @@ int rt_occluder_hint_stats(rt_ctx* c, uint64_t out[3])
     return RT_OK;
 }
 
+/* r22. A switch of its own for the reason rt_gbuffer_reuse is one. Results never depend on it (neighbour_pick.h). */
+int rt_neighbour_pick(rt_ctx* c, int mode)
+{
+    RT_CHECK_CTX(c);
+    if (mode != PICK_EXACT && mode != PICK_FAST && mode != PICK_FORCE_SLOW) RT_FAIL(c, RT_ERR_ARG, "rt_neighbour_pick: mode must be 0, 1 or 2");
+    c->pick_mode = mode;
+    return RT_OK;
+}
+int rt_neighbour_pick_stats(rt_ctx* c, uint64_t out[2])
+{
+    RT_CHECK_CTX(c);
+    if (!out) return RT_ERR_ARG;
+    if (!c->d_walk) RT_FAIL(c, RT_ERR_STATE, "rt_walk_stats_enable first");
+    int rc = rt_sync(c);
+    if (rc != RT_OK) return rc;
+    RT_HIP(c, hipMemcpy(out, c->d_walk + 4 * WALK_PICKS, 2 * 8, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 int rt_row_shaded(rt_ctx* c, uint32_t* counts)
 {
     RT_CHECK_CTX(c);
@@ -3961,7 +3983,7 @@ int rt_math_eval(rt_ctx* c, int fn, const float* in, uint32_t n, float* out)
 {
     RT_CHECK_CTX(c);
     if (n == 0) return RT_OK;
-    const size_t nin = (fn == 26 || fn == 33 || fn == 35) ? 2 : ((fn == 31 || fn == 32) ? 12 : ((fn == 36 || fn == 37) ? 3 : (fn == 38 ? 14 : 1))); /* floats per item */
+    const size_t nin = (fn == 26 || fn == 33 || fn == 35) ? 2 : ((fn == 31 || fn == 32) ? 12 : ((fn == 36 || fn == 37) ? 3 : (fn == 38 ? 14 : (fn == 45 ? 5 : 1)))); /* floats per item */
     float *d_i = nullptr, *d_o = nullptr;
     RT_HIP(c, hipMalloc(&d_i, (size_t)n * 4 * nin));
     RT_HIP(c, hipMalloc(&d_o, (size_t)n * 4));

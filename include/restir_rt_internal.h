@@ -256,6 +256,16 @@ int rt_occluder_hints(rt_ctx* ctx, int on);
  * one of them settled (these count in rt_walk_stats' self_test of the generate_candidate slot: a one-triangle test, no walk),
  * out[2] = triangle tests made. Synchronises. */
 int rt_occluder_hint_stats(rt_ctx* ctx, uint64_t out[3]);
+/* (r22) The neighbour pick of the unshadowed spatial pass (k_spatial_coop; csrc/neighbour_pick.h). mode 1 (default): the two draws go
+ * through the hardware's log2 / sqrt / sin / cos, and an interval guard proves per lane that the neighbour's integer pixel is the one
+ * the portable functions give; the lanes it cannot clear ("near ties", about 0.1 %) run those functions. mode 0: the portable
+ * functions on every lane (r01-r21). mode 2: the guard fails on every lane (the slow path through the fast form's control flow:
+ * tests). The same bytes in every mode. Every other kernel that replays the pick (shadowed and unbiased passes, rt_halo_mark,
+ * rt_spatial_bytes) computes the portable functions. Not an rt_tuning key, as rt_gbuffer_reuse. */
+int rt_neighbour_pick(rt_ctx* ctx, int mode);
+/* counted while rt_walk_stats_enable is on, zeroed by it: out[0] = neighbour picks k_spatial_coop made, out[1] = near ties among them
+ * (mode 0 counts none, mode 2 all). Synchronises. */
+int rt_neighbour_pick_stats(rt_ctx* ctx, uint64_t out[2]);
 /* Unbiased spatial reuse, default off: every byte is then what it was without the call. While on,
  * rt_spatial_resampling, rt_frame and rt_frame_stage* run the spatial pass with the 1/Z normalisation of Bitterli et al. 2020 (Alg. 6)
  * whenever use_spatial_resampling = 1: Z counts only the contributors (the pixel and the merged neighbours) whose own target function
