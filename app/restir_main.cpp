@@ -10,7 +10,7 @@
  *              [--shadowed 0|1] [--visreuse 0|1] [--accumulate 0|1] [--by-kernel]
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
- *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased]
+ *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased] [--reproject]
  *              [--light-sampling uniform|power]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
@@ -25,6 +25,9 @@
  * --shadowed 1.
  * --light-sampling power (--example 10, also with --ranks): rt_light_sampling, the candidates pick their emissive triangle with a
  * probability proportional to area x luminance from an alias table; uniform: the reference's, default.
+ * --reproject (--example 10, one GPU): rt_temporal_reprojection, after a camera move the temporal merge takes a pixel's history from the
+ *     previous frame's pixel that saw the same surface point; meant for --orbit, a camera that stands still
+ *     renders what it renders without the flag.
  * --orbit dx dy (one GPU): before every frame from the second on, rt_camera_orbit(dx, dy) (a left-button drag); with
  * --accumulate 1 that frame starts a new accumulation, as the example clears on a camera update.
  * --move-lights dx dy dz (--example 10, also with --ranks): before every frame from the second on, the emissive triangles move
@@ -440,7 +443,7 @@ int main(int argc, char** argv)
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
-    bool denoise_temporal = false, orbit = false, unbiased = false;
+    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false;
     int light_mode = RT_LIGHTS_UNIFORM;
     float orbit_d[2] = {0.0f, 0.0f};
     LightMove mv;
@@ -487,6 +490,7 @@ int main(int argc, char** argv)
         else if (a == "--denoise") denoise = atoi(argv[++i]);
         else if (a == "--denoise-temporal") denoise_temporal = true;
         else if (a == "--unbiased") unbiased = true;
+        else if (a == "--reproject") reproject = true;
         else if (a == "--light-sampling")
         {
             const std::string m = i + 1 < argc ? argv[++i] : "";
@@ -503,6 +507,7 @@ int main(int argc, char** argv)
     if (denoise > 8) { fprintf(stderr, "--denoise: 0..8 iterations\n"); return 2; }
     if (denoise_temporal && denoise < 0) { fprintf(stderr, "--denoise-temporal needs --denoise N\n"); return 2; }
     if (unbiased && (ranks > 1 || example != 10)) { fprintf(stderr, "--unbiased applies to one GPU and --example 10\n"); return 2; }
+    if (reproject && (ranks > 1 || example != 10)) { fprintf(stderr, "--reproject applies to one GPU and --example 10\n"); return 2; }
     if (light_mode != RT_LIGHTS_UNIFORM && example != 10) { fprintf(stderr, "--light-sampling applies to --example 10\n"); return 2; }
     if (orbit && (ranks > 1 || example == 4 || example == 6)) { fprintf(stderr, "--orbit applies to one GPU and --example 10, 7, 8 and 9\n"); return 2; }
     std::vector<rt_triangle> triangles = !obj.empty() ? load_obj(obj) : load_tris(tris_path);
@@ -615,6 +620,7 @@ int main(int argc, char** argv)
     CK(rt_camera_lookat(ctx, eye, lookat, up, 3.14159265358979323846f / 4.0f)); /* :242-251 */
     CK(rt_options_set(ctx, &opt));
     if (unbiased) CK(rt_spatial_unbiased(ctx, 1));
+    if (reproject) CK(rt_temporal_reprojection(ctx, 1));
     CK(rt_light_sampling(ctx, light_mode));
     CK(rt_timing_enable(ctx, 1));
     CK(rt_clear(ctx)); /* :222-226 */

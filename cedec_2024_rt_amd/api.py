@@ -46,6 +46,7 @@ INTERNAL_EXPORTS = [
     "rt_trace_mode", "rt_trace_time", "rt_tuning", "rt_tuning_get", "rt_math_eval", "rt_gbuffer_reuse", "rt_primary_launches",
     "rt_spatial_unbiased", "rt_spatial_unbiased_get", "rt_occluder_hints", "rt_occluder_hint_stats", "rt_neighbour_pick", "rt_neighbour_pick_stats", "rt_trace_occluders",
     "rt_light_sampling", "rt_light_sampling_get", "rt_light_table",
+    "rt_temporal_reprojection", "rt_temporal_reprojection_get", "rt_reservoir_camera", "rt_temporal_reprojection_stats",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -199,6 +200,11 @@ def load_library(exp=False, path=None):
         L.rt_light_sampling.argtypes = [vp, ci]
         L.rt_light_sampling_get.argtypes = [vp, vp]
         L.rt_light_table.argtypes = [vp, vp, vp, vp, C.c_uint32]
+    if hasattr(L, "rt_temporal_reprojection"):  # r23; likewise
+        L.rt_temporal_reprojection.argtypes = [vp, ci]
+        L.rt_temporal_reprojection_get.argtypes = [vp, vp]
+        L.rt_reservoir_camera.argtypes = [vp, ci, vp, vp]
+        L.rt_temporal_reprojection_stats.argtypes = [vp, vp]
     L.rt_visibility_rays_walked.argtypes = [vp, vp]
     L.rt_state_epoch.argtypes = [vp, vp]
     L.rt_get_stream.argtypes = [vp, vp]
@@ -834,6 +840,33 @@ class Renderer:
         thr, alias, K = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
         self._ck(self.L.rt_light_table(self.h, _p(thr), _p(alias), _p(K), n))
         return thr, alias, K
+
+    def temporal_reprojection(self, on=None):
+        """rt_temporal_reprojection: after a camera move the temporal merge takes a pixel's history from the previous frame's pixel
+        that saw the same surface point (DESIGN.md section 13) instead of from the pixel itself. Default off. on=None queries;
+        returns the state. Whole-frame contexts."""
+        if not hasattr(self.L, "rt_temporal_reprojection"):  # an older build through RT_LIB_PATH: the mode is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_temporal_reprojection")
+        if on is not None:
+            self._ck(self.L.rt_temporal_reprojection(self.h, int(bool(on))))
+        v = C.c_int()
+        self._ck(self.L.rt_temporal_reprojection_get(self.h, C.byref(v)))
+        return bool(v.value)
+
+    def reservoir_camera(self, res):
+        """rt_reservoir_camera: the RayGenerator (oracle RAYGEN layout, 9 floats) reservoir buffer RT_RES_* was last written under, or
+        None while it carries none"""
+        rg = np.zeros(9, dtype=np.float32)
+        has = C.c_int()
+        self._ck(self.L.rt_reservoir_camera(self.h, int(res), _p(rg), C.byref(has)))
+        return rg if has.value else None
+
+    def temporal_reprojection_stats(self):
+        """while walk_stats_enable is on: shaded pixels merged by a reprojecting launch, those that found a valid history, and those
+        among them whose history came from another pixel"""
+        a = np.zeros(3, dtype=np.uint64)
+        self._ck(self.L.rt_temporal_reprojection_stats(self.h, _p(a)))
+        return dict(merged=int(a[0]), valid=int(a[1]), moved=int(a[2]))
 
     def primary_launches(self):
         """launches so far that traced primary rays over the context's rows (rt_raycast, stage-0 raycasts, the one-launch stage 0,

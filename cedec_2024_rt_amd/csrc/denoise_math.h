@@ -22,6 +22,7 @@
  */
 #pragma once
 #include "rt_device.h"
+#include "temporal_reproject.h"
 
 namespace rt
 {
@@ -157,20 +158,7 @@ constexpr float DN_TEMPORAL_WEIGHT_MIN = 0.01f; /* history exists if the valid t
 constexpr float DN_HISTORY_MAX = 32.0f;         /* cap of the history length h */
 constexpr float DN_HISTORY_VARIANCE_MIN = 4.0f; /* h >= this: the temporal variance; below: the spatial window (k_denoise_var's) */
 
-/* inverse of primary_direction (frame_kernels.h: pixel x has u = x / W, storage row = H - 1 - yi with v = yi / H) for the
- * RayGenerator {o, R, U} (R, U and forward = normalize(U x R) orthogonal, as raygen_lookat makes them): continuous storage
- * coordinates of x. false behind the camera, or where no bilinear tap can be inside the image (NaN included) */
-RT_HD bool dn_reproject(f3 x, f3 o, f3 R, f3 U, int W, int H, float& px, float& pr)
-{
-    const f3 fwd = normalize(cross(U, R));
-    const f3 d = x - o;
-    const float t = dot(d, fwd);
-    if (!(t > 0.0f)) return false;
-    const float a = dot(d, R) / (t * dot(R, R)), b = dot(d, U) / (t * dot(U, U));
-    px = ((a + 1.0f) * 0.5f) * (float)W;
-    pr = (float)(H - 1) - ((1.0f - b) * 0.5f) * (float)H;
-    return px >= -1.0f && px < (float)W && pr >= -1.0f && pr < (float)H;
-}
+/* dn_reproject, the inverse of primary_direction: temporal_reproject.h (shared with the ReSTIR history's gather) */
 /* the 2 x 2 taps from (x0, r0), weights in tap order r0x0, r0x1, r1x0, r1x1 */
 RT_HD void dn_bilinear(float px, float pr, int& x0, int& r0, float w[4])
 {

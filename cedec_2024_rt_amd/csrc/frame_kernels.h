@@ -11,6 +11,7 @@
 #include "occluder_hint.h"
 #include "rt_device.h"
 #include "light_alias.h"
+#include "temporal_reproject.h"
 
 using namespace rt;
 
@@ -38,6 +39,9 @@ struct FrameParams
      * {rays the reference traces here, walked through the BVH, settled by the one-triangle self-occlusion test, not evaluated
      * (answer known from the own-visibility flags, or unobservable)}; slots WALK_RAYCAST .. WALK_RESOLVE */
     unsigned long long* stats;
+    /* rt_temporal_reprojection (temporal_reproject.h): the RayGenerator the history buffer of this launch was written under; read by
+     * the REPROJECT instantiations only, which the host launches only where it differs from rg_* */
+    f3 prev_origin, prev_right, prev_up;
 #ifdef RT_EXPERIMENTS
     /* rt_exp_wave_clock (measurement, experiments library only): two words per wavefront of the chosen kernel — the constant
      * 100-MHz clock when it started, and when its last lane left | hardware id << 40 (XCD, SE, CU, SIMD) */
@@ -75,7 +79,9 @@ struct WaveClock
 #define RT_WAVE_CLOCK(P)
 #endif
 enum { WALK_RAYCAST = 0, WALK_GENERATE = 1, WALK_SPATIAL = 2, WALK_RESOLVE = 3, WALK_HINTS = 4 /* rt_occluder_hint_stats: {rays with a hint to test, settled by one, triangle tests, -} */,
-       WALK_PICKS = 5 /* rt_neighbour_pick_stats: {neighbour picks of k_spatial_coop, near ties (lanes on the exact path), -, -} */, WALK_SLOTS = 6 };
+       WALK_PICKS = 5 /* rt_neighbour_pick_stats: {neighbour picks of k_spatial_coop, near ties (lanes on the exact path), -, -} */,
+       WALK_REPROJECT = 6 /* rt_temporal_reprojection_stats: {shaded pixels merged by a reprojecting launch, valid histories, gathered from another pixel, -} */,
+       WALK_SLOTS = 7 };
 /* one ray per lane at most; works under any exec mask (ballots count the active lanes) */
 RT_DEV void count_walk_flags(unsigned long long* __restrict__ st, bool ref, bool walked, bool self, bool skipped)
 {
@@ -500,6 +506,32 @@ RT_DEV void temporal_rays(const SceneView& S, uint32_t* s_stack, const FramePara
     V_prev = (occl & 2u) ? 0.0f : 1.0f;
 }
 
+/* rt_temporal_reprojection, history written under another camera (temporal_reproject.h): the record of the previous frame's pixel
+ * that saw sp, or Reservoir{} where there is none. One per-lane gather of a 64-B aligned record + its side record, the access shape
+ * of the spatial pass's neighbour read. The pixel index is formed only from coordinates tr_previous_pixel has range-checked in
+ * float, and once more against the rows the buffer holds. */
+RT_DEV Res load_prev_reprojected(const FrameParams& P, f3 sp, int x, int row, const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad)
+{
+    Res pr = res_zero();
+    const TrPixel q = tr_previous_pixel(sp, P.prev_origin, P.prev_right, P.prev_up, P.W, P.H);
+    bool have = false;
+    if (q.valid && (unsigned)q.xq < (unsigned)P.W && (unsigned)(q.rq - P.lrow0) < (unsigned)P.lrows)
+    {
+        const size_t qi = (size_t)q.xq + (size_t)(q.rq - P.lrow0) * P.W;
+        bool shaded;
+        const Res g = res_load(prev_rec, qi, shaded);
+        if (shaded) /* a sky or emissive pixel of the previous frame holds no history */
+        {
+            pr = g;
+            const float4 pq = prev_rad[qi];
+            pr.rad = F3(pq.x, pq.y, pq.z);
+            have = true;
+        }
+    }
+    if (P.stats) count_walk_flags(P.stats + 4 * WALK_REPROJECT, true, have, have && (q.xq != x || q.rq != row), false);
+    return pr;
+}
+
 template <bool SHADOWED>
 RT_DEV bool temporal_merge(const FrameParams& P, int x, int yi, f3 sp, f3 sn, Res& r, Res pr, float V_cur, float V_prev)
 {
@@ -593,7 +625,9 @@ RT_DEV void wave_gather_records(const float4* q, float4* s_wave, const int lane,
 /* POWER (r21, rt_light_sampling): the light of a candidate comes from the alias table (light_alias.h) instead of
  * the uniform index: a fifth draw `ra` directly after rv0, one 8-byte slot gathered per lane, and S.lights holds the realised pdf. A
  * template parameter: the kernels of the uniform mode are compiled from the text they had. */
-template <bool FUSE_TEMPORAL, bool SHADOWED, bool DEFER = false, bool PIPE = false, bool WS = false, bool RAYCAST = false, bool POWER = false>
+/* REPROJECT (r23, rt_temporal_reprojection): the history record comes from load_prev_reprojected instead of the own pixel. A template
+ * parameter for the reason POWER is one; launched only where the history buffer was written under another camera. */
+template <bool FUSE_TEMPORAL, bool SHADOWED, bool DEFER = false, bool PIPE = false, bool WS = false, bool RAYCAST = false, bool POWER = false, bool REPROJECT = false>
 __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED ? RT_GENERATE_SH_WAVES : RT_TRACE_WAVES)) void k_generate_candidate(
     SceneView S, FrameParams P, const float4* __restrict__ g0, const float4* __restrict__ g1,
     const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad, float4* __restrict__ out_rec,
@@ -603,6 +637,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
 {
     static_assert(!DEFER || (FUSE_TEMPORAL && !SHADOWED), "deferred visibility: fused unshadowed kernel only");
     static_assert(!RAYCAST || (WS && FUSE_TEMPORAL && !SHADOWED && !DEFER && !PIPE), "primary rays in the product's fused kernel only");
+    static_assert(!REPROJECT || (FUSE_TEMPORAL && !DEFER && !PIPE), "reprojected history: the product's fused kernels only");
     RT_WAVE_CLOCK(P);
     constexpr bool LATE = WS && FUSE_TEMPORAL && !SHADOWED && !DEFER; /* the visibility-reuse ray after the temporal merge */
     /* shadowed target: every lane stays through the RIS loop, so that the wavefront can fetch its light records together */
@@ -846,10 +881,14 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     }
     Res pr = res_zero();
     auto load_prev = [&]() {
+        if constexpr (REPROJECT) pr = load_prev_reprojected(P, sp, x, row, prev_rec, prev_rad);
+        else
+        {
         bool dummy;
         pr = res_load(prev_rec, li, dummy);
         const float4 pq = prev_rad[li];
         pr.rad = F3(pq.x, pq.y, pq.z);
+        }
     };
     if (FUSE_TEMPORAL && SHADOWED) load_prev(); /* its sample is a ray target */
     float V_cur = 1.0f, V_prev = 1.0f;
@@ -992,7 +1031,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, RT_RESOLVE_WAVES_FWD) void k_candidate
 #endif /* RT_EXPERIMENTS */
 /* -------------------------------------------------------- temporal_resampling */
 /* examples/10_restir_di/10_restir_di.cu:137-237 (stand-alone entry point) */
-template <bool SHADOWED>
+template <bool SHADOWED, bool REPROJECT = false>
 __global__ __launch_bounds__(BLOCK) void k_temporal(SceneView S, FrameParams P, const float4* __restrict__ g0,
                                                      const float4* __restrict__ g1,
                                                      const float4* __restrict__ prev_rec,
@@ -1013,9 +1052,14 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(SceneView S, FrameParams P, 
     const float4 rq = radb[li];
     r.rad = F3(rq.x, rq.y, rq.z);
     r.ownv = as_uint(rq.w);
-    Res pr = res_load(prev_rec, li, dummy);
+    Res pr;
+    if constexpr (REPROJECT) pr = load_prev_reprojected(P, sp, x, row, prev_rec, prev_rad);
+    else
+    {
+    pr = res_load(prev_rec, li, dummy);
     const float4 pq = prev_rad[li];
     pr.rad = F3(pq.x, pq.y, pq.z);
+    }
     float V_cur = 1.0f, V_prev = 1.0f;
     if (SHADOWED) temporal_rays(S, s_stack, P, sp, sn, r, pr, true, V_cur, V_prev, as_int(G0.w));
     const bool took_prev = temporal_merge<SHADOWED>(P, x, yi, sp, sn, r, pr, V_cur, V_prev);

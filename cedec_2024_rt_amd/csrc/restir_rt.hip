@@ -102,6 +102,12 @@ struct rt_ctx
      * a staged frame carry frame.tag (Launch::tag), the per-kernel entry points carry 0 */
     uint32_t ownv_serial = 0;
     uint64_t rec_gserial[5] = {0, 0, 0, 0, 0}; /* gbuf.serial of the G-buffer each reservoir buffer's shaded bits belong to */
+    /* r23, rt_temporal_reprojection (temporal_reproject.h): the RayGenerator each physical reservoir buffer was
+     * last written under (rec_rg_has: it carries one), kept whether the mode is on or not. A temporal merge whose history buffer
+     * carries another camera than the current one launches the REPROJECT kernels while the mode is on (history_camera). */
+    rt_raygen rec_rg[5] = {};
+    bool rec_rg_has[5] = {false, false, false, false, false};
+    bool reproject = false;
     unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters, then the slot of rt_occluder_hint_stats (WALK_SLOTS) */
     bool walk_on = false;
     /* r19, rt_occluder_hints: OCCLUDER_HINTS triangle indices per pixel of the local rows (occluder_hint.h), the triangles that occluded
@@ -386,6 +392,7 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
     P.ownv_tag = L.tag;
     P.pick_mode = c->pick_mode;
     P.stats = c->walk_on ? c->d_walk : nullptr;
+    P.prev_origin = P.rg_origin; P.prev_right = P.rg_right; P.prev_up = P.rg_up; /* history_camera sets the history buffer's where it differs */
 #ifdef RT_EXPERIMENTS
     P.wave_clock = c->d_wave_clock && kernel == c->wave_clock_kernel && (kernel != K_SPATIAL || pass == c->wave_clock_pass) ? c->d_wave_clock : nullptr;
     /* whole launches over the context's own rows only (the grid the permutation was checked against) */
@@ -393,6 +400,23 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
 #endif
     return P;
 }
+/* the reservoir buffer `phys` is written under the current camera / holds a copy of buffer `src` */
+static void tag_camera(rt_ctx* c, int phys) { c->rec_rg[phys] = c->rg; c->rec_rg_has[phys] = true; }
+static void copy_camera(rt_ctx* c, int phys, int src) { c->rec_rg[phys] = c->rec_rg[src]; c->rec_rg_has[phys] = c->rec_rg_has[src]; }
+/* rt_temporal_reprojection: does a temporal merge that reads buffer `prev_phys` as its history gather by reprojection? Only with
+ * the mode on and a buffer whose 36 bytes of RayGenerator differ from the current ones (then P carries them); an untagged buffer
+ * and a camera that stands still launch what they launched before the mode existed. */
+static bool history_camera(const rt_ctx* c, int prev_phys, FrameParams& P)
+{
+    if (!c->reproject || !c->opt.use_temporal_resampling || !c->rec_rg_has[prev_phys]) return false;
+    const rt_raygen& q = c->rec_rg[prev_phys];
+    if (tr_same_camera(q.origin, c->rg.origin)) return false; /* origin, right, up: 9 contiguous floats */
+    P.prev_origin = F3(q.origin[0], q.origin[1], q.origin[2]);
+    P.prev_right = F3(q.right[0], q.right[1], q.right[2]);
+    P.prev_up = F3(q.up[0], q.up[1], q.up[2]);
+    return true;
+}
+static_assert(sizeof(rt_raygen) == 36 && offsetof(rt_raygen, right) == 12 && offsetof(rt_raygen, up) == 24, "tr_same_camera reads 9 contiguous floats");
 static uint32_t next_ownv_tag(rt_ctx* c)
 {
     c->ownv_serial = (c->ownv_serial + 1u) & 0x3fffffffu;
@@ -1191,6 +1215,7 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
     drop_look_ahead(c);
     c->dt_valid = false; /* rt_denoise_temporal's history belongs to the old scene */
+    for (int k = 0; k < 5; ++k) c->rec_rg_has[k] = false; /* ... and so do the reservoir buffers' camera tags: no reprojection into it */
     /* the remembered occluders are indices of the old scene, which may have had more triangles (every stream is idle here) */
     if (c->d_hints) RT_HIP(c, hipMemset(c->d_hints, 0xff, local_pixels(c) * sizeof(int) * OCCLUDER_HINTS));
     const auto t_build0 = std::chrono::steady_clock::now();
@@ -2009,10 +2034,12 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
         S.lights = c->d_lights_power;
         S.light_alias = c->d_alias;
     }
-    const FrameParams P = make_params(c, L, frame, 0, K_GENERATE);
+    FrameParams P = make_params(c, L, frame, 0, K_GENERATE);
     const bool sh = c->opt.use_shadowed_target_function;
     float4 *orec = c->d_rec[dst_phys], *orad = c->d_rad[dst_phys];
     c->rec_gserial[dst_phys] = c->gbuf.serial;
+    const bool rp = fuse && history_camera(c, prev_phys, P); /* before the tag below: dst may not be prev, but the order costs nothing */
+    tag_camera(c, dst_phys);
     const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
     const int g = trace_grid(c, L);
     /* every form of the kernel in both light samplings: <fused, shadowed, deferred, pipelined, work-sharing, with primary rays> */
@@ -2021,7 +2048,16 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
         if (power) k_generate_candidate<FT, SH, DF, PP, WS_, RC, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);              \
         else k_generate_candidate<FT, SH, DF, PP, WS_, RC><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);                          \
     } while (0)
+    /* the fused forms the product launches, with the history gathered by reprojection (rp) or from the own pixel */
+#define GEN_LAUNCH_RP(SH, WS_, RC, ...)                                                                                           \
+    do {                                                                                                                          \
+        if (!rp) GEN_LAUNCH(true, SH, false, false, WS_, RC, __VA_ARGS__);                                                         \
+        else if (power) k_generate_candidate<true, SH, false, false, WS_, RC, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
+        else k_generate_candidate<true, SH, false, false, WS_, RC, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);     \
+    } while (0)
 #ifdef RT_EXPERIMENTS
+    if (rp && fuse && ((!sh && c->tune_defer_vis) || (!sh && c->tune_ris_pipe)))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_reprojection: the [exp] stage-0 variants (rt_tuning keys 11 and 12) gather their history from the own pixel only");
     if (fuse && !sh && c->tune_defer_vis)
     {
         /* fused + unshadowed: the visibility-reuse rays that survive the temporal merge go through a queue */
@@ -2057,17 +2093,18 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
         return RT_OK;
     }
 #endif
-    if (fuse && sh) GEN_LAUNCH(true, true, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
+    if (fuse && sh) GEN_LAUNCH_RP(true, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
 #ifdef RT_EXPERIMENTS
     else if (fuse && c->tune_ris_pipe) GEN_LAUNCH(true, false, false, true, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
 #endif
     else if (fuse && use_ws(c, g) && raycast_vis)
-        GEN_LAUNCH(true, false, false, false, true, true, S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, L.g0, L.g1, hints);
+        GEN_LAUNCH_RP(false, true, true, S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, L.g0, L.g1, hints);
     else if (raycast_vis) RT_FAIL(c, RT_ERR_STATE, "the one-launch stage 0 needs the product's fused candidate kernel");
-    else if (fuse && use_ws(c, g)) GEN_LAUNCH(true, false, false, false, true, false, S, P, L.g0, L.g1, prec, prad, orec, orad, nullptr, nullptr, nullptr, nullptr, nullptr, hints);
-    else if (fuse) GEN_LAUNCH(true, false, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
+    else if (fuse && use_ws(c, g)) GEN_LAUNCH_RP(false, true, false, S, P, L.g0, L.g1, prec, prad, orec, orad, nullptr, nullptr, nullptr, nullptr, nullptr, hints);
+    else if (fuse) GEN_LAUNCH_RP(false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
     else if (sh) GEN_LAUNCH(false, true, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
     else GEN_LAUNCH(false, false, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
+#undef GEN_LAUNCH_RP
 #undef GEN_LAUNCH
     RT_HIP(c, hipGetLastError());
     return RT_OK;
@@ -2097,9 +2134,15 @@ int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
     if (prev == inout) RT_FAIL(c, RT_ERR_ARG, "prev and inout must differ");
     const SceneView S = make_scene(c);
     const Launch L = whole_launch(c);
-    const FrameParams P = make_params(c, L, frame, 0);
+    FrameParams P = make_params(c, L, frame, 0);
     const int pp = c->frame.res_map[prev], pi = c->frame.res_map[inout];
-    if (c->opt.use_shadowed_target_function)
+    const bool rp = history_camera(c, pp, P);
+    tag_camera(c, pi);
+    if (rp && c->opt.use_shadowed_target_function)
+        k_temporal<true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+    else if (rp)
+        k_temporal<false, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+    else if (c->opt.use_shadowed_target_function)
         k_temporal<true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
     else
         k_temporal<false><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
@@ -2121,6 +2164,7 @@ int rt_save_temporal_reservoir(rt_ctx* c, int src, int dst)
     const size_t n = (size_t)(c->row_end - c->row_begin) * c->W;
     const int ps = c->frame.res_map[src], pd = c->frame.res_map[dst];
     c->rec_gserial[pd] = c->rec_gserial[ps];
+    copy_camera(c, pd, ps);
     RT_HIP(c, hipMemcpyAsync(c->d_rec[pd] + 4 * off, c->d_rec[ps] + 4 * off, n * 64, hipMemcpyDeviceToDevice, c->stream));
     RT_HIP(c, hipMemcpyAsync(c->d_rad[pd] + off, c->d_rad[ps] + off, n * 16, hipMemcpyDeviceToDevice, c->stream));
     return RT_OK;
@@ -2207,6 +2251,7 @@ static int launch_spatial(rt_ctx* c, const Launch& L, int frame, int pass, int i
     const bool lds_variant = use_lds_spatial(c);
     (void)lds_variant; /* the product build has no LDS-staged form */
     c->rec_gserial[out_phys] = c->gbuf.serial;
+    tag_camera(c, out_phys); /* a pass's output lies on the current camera's pixels (the history is never a pass's output) */
     if (unbiased_applies(c))
         /* one kernel whatever keys 8 and 23 say: the A/B forms restate the reference's pass */
         k_spatial_unbiased<<<trace_grid(c, L), TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys]);
@@ -2878,6 +2923,7 @@ int rt_frame_stage_end(rt_ctx* c, int stage)
         const size_t n = local_pixels(c);
         { const int jr = join_tail_for(c, whole_launch(c), X); if (jr != RT_OK) return jr; }
         c->rec_gserial[X] = c->rec_gserial[Y];
+        copy_camera(c, X, Y);
         RT_HIP(c, hipMemcpyAsync(c->d_rec[X], c->d_rec[Y], n * 64, hipMemcpyDeviceToDevice, c->stream));
         RT_HIP(c, hipMemcpyAsync(c->d_rad[X], c->d_rad[Y], n * 16, hipMemcpyDeviceToDevice, c->stream));
     }
@@ -2986,6 +3032,46 @@ int rt_spatial_unbiased_get(rt_ctx* c, int* on)
     RT_CHECK_CTX(c);
     if (!on) return RT_ERR_ARG;
     *on = c->spatial_unbiased ? 1 : 0;
+    return RT_OK;
+}
+/* r23. Temporal history gathered by reprojection where its buffer was written under another camera (temporal_reproject.h, DESIGN.md
+ * section 13). Changes results after a camera move, so not an rt_tuning key; counts as an option change (rt_state_epoch) and drops the
+ * look-ahead. Touches no buffer. A previous pixel can lie in another strip: whole-frame contexts only. */
+int rt_temporal_reprojection(rt_ctx* c, int on)
+{
+    RT_CHECK_CTX(c);
+    if (!whole_frame(c))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_reprojection: a strip context holds only its own rows of the history");
+    c->reproject = on != 0;
+    drop_look_ahead(c);
+    ++c->epoch;
+    return RT_OK;
+}
+int rt_temporal_reprojection_get(rt_ctx* c, int* on)
+{
+    RT_CHECK_CTX(c);
+    if (!on) return RT_ERR_ARG;
+    *on = c->reproject ? 1 : 0;
+    return RT_OK;
+}
+int rt_reservoir_camera(rt_ctx* c, int res, rt_raygen* out, int* has)
+{
+    RT_CHECK_CTX(c);
+    NEED_RES(c, res);
+    if (!out && !has) return RT_ERR_ARG;
+    const int phys = c->frame.res_map[res];
+    if (has) *has = c->rec_rg_has[phys] ? 1 : 0;
+    if (out) { if (c->rec_rg_has[phys]) *out = c->rec_rg[phys]; else memset(out, 0, sizeof(*out)); }
+    return RT_OK;
+}
+int rt_temporal_reprojection_stats(rt_ctx* c, uint64_t out[3])
+{
+    RT_CHECK_CTX(c);
+    if (!out) return RT_ERR_ARG;
+    if (!c->d_walk) RT_FAIL(c, RT_ERR_STATE, "rt_walk_stats_enable first");
+    int rc = rt_sync(c);
+    if (rc != RT_OK) return rc;
+    RT_HIP(c, hipMemcpy(out, c->d_walk + 4 * WALK_REPROJECT, 3 * 8, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 /* How the candidates pick their light (light_alias.h). Changes results, so not an rt_tuning key; counts as an
@@ -3121,6 +3207,7 @@ int rt_upload(rt_ctx* c, int buf, const void* src, size_t bytes)
             ++c->res_epoch;
             const int phys = c->frame.res_map[buf - RT_BUF_RES_0];
             c->rec_gserial[phys] = c->gbuf.serial;
+            tag_camera(c, phys); /* its shaded bits come from the current G-buffer: the current camera's pixels */
             /* the record keeps M in 30 bits: refuse what it cannot hold rather than truncate */
             for (size_t i = 0; i < n; ++i)
             {

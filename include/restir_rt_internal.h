@@ -294,6 +294,28 @@ int rt_spatial_unbiased_get(rt_ctx* ctx, int* on);
 enum { RT_LIGHTS_UNIFORM = 0 /* the reference's, default */, RT_LIGHTS_POWER = 1 };
 int rt_light_sampling(rt_ctx* ctx, int mode);
 int rt_light_sampling_get(rt_ctx* ctx, int* mode);
+/* (r23) Temporal reuse that follows the camera (csrc/temporal_reproject.h), default off: every byte is then what
+ * it was without the call. Every physical reservoir buffer carries the rt_raygen it was last written under: set by
+ * rt_generate_candidate, rt_temporal_resampling, stage 0 and the spatial passes of a staged frame and rt_upload of a reservoir buffer
+ * (each taking the current camera), copied by rt_save_temporal_reservoir and with the buffers as rt_frame rotates them, cleared by
+ * rt_scene_set. While the mode is on, a temporal merge (rt_temporal_resampling, stage 0 of rt_frame / rt_frame_stage*) whose history
+ * buffer carries a camera whose 36 bytes differ from the current ones takes, for every shaded pixel, the history of the previous
+ * frame's pixel nearest to where the pixel's surface point projects in that camera, or Reservoir{} where there is none (behind the
+ * previous camera, outside its image, NaN, or a previous pixel that was sky or emissive); the merge itself, its random numbers and
+ * the rejection heuristics are the reference's. With equal bytes, or a buffer without a tag, the launches are the ones of the mode
+ * off: a camera that stands still costs and computes what it did. Geometry moved by rt_scene_update is not followed (cameras only).
+ * The call changes rt_state_epoch and drops look-ahead work, touches no buffer. Strip contexts (and so rt_mg_frame):
+ * RT_ERR_UNSUPPORTED from the toggle, a previous pixel can lie in another strip. use_temporal_resampling = 0 makes it moot.
+ * rt_temporal_resampling keeps refusing prev == inout (with a gather it would be a race). The [exp] stage-0 variants (rt_tuning keys
+ * 11 and 12): RT_ERR_UNSUPPORTED at the launching call while the mode is on and the cameras differ. rt_ray_count keeps counting the
+ * reference's rays. Not an rt_tuning key: tuning keys never change results. */
+int rt_temporal_reprojection(rt_ctx* ctx, int on);
+int rt_temporal_reprojection_get(rt_ctx* ctx, int* on);
+/* the camera tag of RT_RES_* (tests): *has = 1 and *out = the rt_raygen, or *has = 0 and *out zeroed; either pointer may be null */
+int rt_reservoir_camera(rt_ctx* ctx, int res, rt_raygen* out, int* has);
+/* counted while rt_walk_stats_enable is on, zeroed by it: out[0] = shaded pixels merged by a reprojecting launch, out[1] = those that
+ * found a valid history, out[2] = those among them whose history came from another pixel than their own. Synchronises. */
+int rt_temporal_reprojection_stats(rt_ctx* ctx, uint64_t out[3]);
 /* the alias table and the realised counts (thr / alias / K per light, light list order; any pointer may be null), for tests; n = the
  * scene's light count (RT_ERR_ARG otherwise); RT_ERR_STATE without a scene */
 int rt_light_table(rt_ctx* ctx, uint32_t* thr, uint32_t* alias, uint64_t* K, uint32_t n);
