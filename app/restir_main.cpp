@@ -11,6 +11,7 @@
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
  *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased] [--reproject]
+ *              [--move-tris first count dx dy dz] [--follow-motion]
  *              [--light-sampling uniform|power]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
@@ -33,6 +34,10 @@
  * --move-lights dx dy dz (--example 10, also with --ranks): before every frame from the second on, the emissive triangles move
  * by (dx, dy, dz) and rt_scene_update refits the scene (the span from the lowest to the highest emissive index); the call's wall
  * time is printed per frame, and with --accumulate 1 the frame starts a new accumulation.
+ * --move-tris first count dx dy dz (--example 10, also with --ranks): the general form of --move-lights, every triangle of
+ *     [first, first + count) moves by (dx, dy, dz) before every frame from the second on (the same float add); not with --move-lights.
+ * --follow-motion (with --reproject): rt_temporal_motion, the temporal merge of a pixel on a moved triangle takes the history of the
+ *     previous frame's pixel that saw the point it was at; meant for --move-tris on non-emissive triangles.
  * --example 6: the same ambient occlusion ON THE GPU through rt_path_trace (examples/06_ao_hiprt/06_ao_hiprt.cu:35-91, the
  * same image as 04_ao's kernel). Defaults follow 06_ao_hiprt.cpp:79-80: 1920x1080, camera (8,8,8) -> (0,0,0), fovy pi/4.
  * --frames K times K launches after one warm-up (host clock around rt_sync) and prints ms per launch and Mray/s in the
@@ -258,6 +263,7 @@ struct LightMove
     bool on = false;
     float d[3] = {0.0f, 0.0f, 0.0f};
     uint32_t first = 0, count = 0;
+    bool all = false; /* --move-tris: every triangle of the span, emissive or not */
 };
 static void light_span(const std::vector<rt_triangle>& tris, LightMove& mv)
 {
@@ -277,7 +283,7 @@ static double move_lights(rt_ctx* ctx, std::vector<rt_triangle>& tris, const Lig
     for (uint32_t i = mv.first; i < mv.first + mv.count; ++i)
     {
         rt_triangle& t = tris[i];
-        if (!(t.emissive[0] > 0.0f || t.emissive[1] > 0.0f || t.emissive[2] > 0.0f)) continue;
+        if (!mv.all && !(t.emissive[0] > 0.0f || t.emissive[1] > 0.0f || t.emissive[2] > 0.0f)) continue;
         for (int k = 0; k < 3; ++k)
             for (int a = 0; a < 3; ++a) t.v[k][a] = t.v[k][a] + mv.d[a];
     }
@@ -443,7 +449,7 @@ int main(int argc, char** argv)
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
-    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false;
+    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false, follow_motion = false, move_lights_given = false;
     int light_mode = RT_LIGHTS_UNIFORM;
     float orbit_d[2] = {0.0f, 0.0f};
     LightMove mv;
@@ -491,6 +497,7 @@ int main(int argc, char** argv)
         else if (a == "--denoise-temporal") denoise_temporal = true;
         else if (a == "--unbiased") unbiased = true;
         else if (a == "--reproject") reproject = true;
+        else if (a == "--follow-motion") follow_motion = true;
         else if (a == "--light-sampling")
         {
             const std::string m = i + 1 < argc ? argv[++i] : "";
@@ -499,7 +506,12 @@ int main(int argc, char** argv)
             else { fprintf(stderr, "--light-sampling uniform|power\n"); return 2; }
         }
         else if (a == "--orbit") { orbit_d[0] = f(1); orbit_d[1] = f(2); i += 2; orbit = true; }
-        else if (a == "--move-lights") { mv.d[0] = f(1); mv.d[1] = f(2); mv.d[2] = f(3); i += 3; mv.on = true; }
+        else if (a == "--move-lights") { mv.d[0] = f(1); mv.d[1] = f(2); mv.d[2] = f(3); i += 3; mv.on = true; move_lights_given = true; }
+        else if (a == "--move-tris" && i + 5 < argc)
+        {
+            mv.first = (uint32_t)strtoul(argv[i + 1], nullptr, 10); mv.count = (uint32_t)strtoul(argv[i + 2], nullptr, 10);
+            mv.d[0] = f(3); mv.d[1] = f(4); mv.d[2] = f(5); i += 5; mv.on = true; mv.all = true;
+        }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     if (denoise >= 0 && (example == 4 || example == 6)) { fprintf(stderr, "--denoise applies to --example 10, 7, 8 and 9\n"); return 2; }
@@ -508,6 +520,8 @@ int main(int argc, char** argv)
     if (denoise_temporal && denoise < 0) { fprintf(stderr, "--denoise-temporal needs --denoise N\n"); return 2; }
     if (unbiased && (ranks > 1 || example != 10)) { fprintf(stderr, "--unbiased applies to one GPU and --example 10\n"); return 2; }
     if (reproject && (ranks > 1 || example != 10)) { fprintf(stderr, "--reproject applies to one GPU and --example 10\n"); return 2; }
+    if (follow_motion && !reproject) { fprintf(stderr, "--follow-motion needs --reproject\n"); return 2; }
+    if (mv.all && move_lights_given) { fprintf(stderr, "--move-tris and --move-lights exclude each other\n"); return 2; }
     if (light_mode != RT_LIGHTS_UNIFORM && example != 10) { fprintf(stderr, "--light-sampling applies to --example 10\n"); return 2; }
     if (orbit && (ranks > 1 || example == 4 || example == 6)) { fprintf(stderr, "--orbit applies to one GPU and --example 10, 7, 8 and 9\n"); return 2; }
     std::vector<rt_triangle> triangles = !obj.empty() ? load_obj(obj) : load_tris(tris_path);
@@ -567,8 +581,9 @@ int main(int argc, char** argv)
         return write_ao_image(px, W, H, rgba, ppm, png);
     }
     if (example != 10 && example != 7 && example != 8 && example != 9) { fprintf(stderr, "--example 10, 7, 8, 9, 6 or 4\n"); return 2; }
-    if (mv.on && example != 10) { fprintf(stderr, "--move-lights applies to --example 10\n"); return 2; }
-    if (mv.on) light_span(triangles, mv);
+    if (mv.on && example != 10) { fprintf(stderr, "--move-lights and --move-tris apply to --example 10\n"); return 2; }
+    if (mv.all && (uint64_t)mv.first + mv.count > triangles.size()) { fprintf(stderr, "--move-tris: [%u, %llu) outside the scene's %zu triangles\n", mv.first, (unsigned long long)mv.first + mv.count, triangles.size()); return 2; }
+    if (mv.on && !mv.all) light_span(triangles, mv);
 
     if (ranks > 1)
     {
@@ -621,6 +636,7 @@ int main(int argc, char** argv)
     CK(rt_options_set(ctx, &opt));
     if (unbiased) CK(rt_spatial_unbiased(ctx, 1));
     if (reproject) CK(rt_temporal_reprojection(ctx, 1));
+    if (follow_motion) CK(rt_temporal_motion(ctx, 1));
     CK(rt_light_sampling(ctx, light_mode));
     CK(rt_timing_enable(ctx, 1));
     CK(rt_clear(ctx)); /* :222-226 */

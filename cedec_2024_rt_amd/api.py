@@ -47,6 +47,7 @@ INTERNAL_EXPORTS = [
     "rt_spatial_unbiased", "rt_spatial_unbiased_get", "rt_occluder_hints", "rt_occluder_hint_stats", "rt_neighbour_pick", "rt_neighbour_pick_stats", "rt_trace_occluders",
     "rt_light_sampling", "rt_light_sampling_get", "rt_light_table",
     "rt_temporal_reprojection", "rt_temporal_reprojection_get", "rt_reservoir_camera", "rt_temporal_reprojection_stats",
+    "rt_temporal_motion", "rt_temporal_motion_get", "rt_reservoir_scene", "rt_temporal_motion_range", "rt_temporal_motion_stats",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -205,6 +206,12 @@ def load_library(exp=False, path=None):
         L.rt_temporal_reprojection_get.argtypes = [vp, vp]
         L.rt_reservoir_camera.argtypes = [vp, ci, vp, vp]
         L.rt_temporal_reprojection_stats.argtypes = [vp, vp]
+    if hasattr(L, "rt_temporal_motion"):  # r24; likewise
+        L.rt_temporal_motion.argtypes = [vp, ci]
+        L.rt_temporal_motion_get.argtypes = [vp, vp]
+        L.rt_reservoir_scene.argtypes = [vp, ci, vp, vp, vp]
+        L.rt_temporal_motion_range.argtypes = [vp, vp, vp, vp]
+        L.rt_temporal_motion_stats.argtypes = [vp, vp]
     L.rt_visibility_rays_walked.argtypes = [vp, vp]
     L.rt_state_epoch.argtypes = [vp, vp]
     L.rt_get_stream.argtypes = [vp, vp]
@@ -867,6 +874,40 @@ class Renderer:
         a = np.zeros(3, dtype=np.uint64)
         self._ck(self.L.rt_temporal_reprojection_stats(self.h, _p(a)))
         return dict(merged=int(a[0]), valid=int(a[1]), moved=int(a[2]))
+
+    def temporal_motion(self, on=None):
+        """rt_temporal_motion: while temporal_reprojection is on, the temporal merge of a pixel on a triangle that update_scene has moved
+        since the history was written takes the history of the previous frame's pixel that saw the point it was at (DESIGN.md section
+        14). Default off. on=None queries; returns the state. Whole-frame contexts."""
+        if not hasattr(self.L, "rt_temporal_motion"):  # an older build through RT_LIB_PATH: the toggle is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_temporal_motion")
+        if on is not None:
+            self._ck(self.L.rt_temporal_motion(self.h, int(bool(on))))
+        v = C.c_int()
+        self._ck(self.L.rt_temporal_motion_get(self.h, C.byref(v)))
+        return bool(v.value)
+
+    def reservoir_scene(self, res):
+        """rt_reservoir_scene: (geometry generation, eye as 3 float32) reservoir buffer RT_RES_* was last written under, or None while it
+        carries no tag"""
+        gen, has = C.c_uint64(), C.c_int()
+        eye = np.zeros(3, dtype=np.float32)
+        self._ck(self.L.rt_reservoir_scene(self.h, int(res), C.byref(gen), _p(eye), C.byref(has)))
+        return (int(gen.value), eye) if has.value else None
+
+    def temporal_motion_range(self):
+        """rt_temporal_motion_range: dict(lo, hi, generation): the triangles update_scene has moved since `generation`, the one whose
+        vertex positions the context keeps"""
+        lo, hi, gen = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._ck(self.L.rt_temporal_motion_range(self.h, C.byref(lo), C.byref(hi), C.byref(gen)))
+        return dict(lo=int(lo.value), hi=int(hi.value), generation=int(gen.value))
+
+    def temporal_motion_stats(self):
+        """while walk_stats_enable is on: shaded pixels merged by a motion launch, those on moved triangles, and those among them that
+        found a valid history"""
+        a = np.zeros(3, dtype=np.uint64)
+        self._ck(self.L.rt_temporal_motion_stats(self.h, _p(a)))
+        return dict(merged=int(a[0]), in_range=int(a[1]), valid=int(a[2]))
 
     def primary_launches(self):
         """launches so far that traced primary rays over the context's rows (rt_raycast, stage-0 raycasts, the one-launch stage 0,

@@ -12,6 +12,7 @@
 #include "rt_device.h"
 #include "light_alias.h"
 #include "temporal_reproject.h"
+#include "temporal_motion.h"
 
 using namespace rt;
 
@@ -42,6 +43,15 @@ struct FrameParams
     /* rt_temporal_reprojection (temporal_reproject.h): the RayGenerator the history buffer of this launch was written under; read by
      * the REPROJECT instantiations only, which the host launches only where it differs from rg_* */
     f3 prev_origin, prev_right, prev_up;
+    /* rt_temporal_motion (temporal_motion.h), read by the MOTION instantiations only: the eye the history buffer was written under, the
+     * triangles [motion_lo, motion_hi) that rt_scene_update has moved since, their vertices as they were then (layout of BvhView::tv),
+     * the Visibility buffer of the launch's rows (the forms without the primary ray take (u, v) from it) and whether the history's
+     * RayGenerator has the bytes of the current one (pixels off the moved triangles then take their own pixel's record) */
+    f3 eye_prev;
+    uint32_t motion_lo, motion_hi;
+    const float4* tv_prev;
+    const float4* motion_vis;
+    int motion_same_camera;
 #ifdef RT_EXPERIMENTS
     /* rt_exp_wave_clock (measurement, experiments library only): two words per wavefront of the chosen kernel — the constant
      * 100-MHz clock when it started, and when its last lane left | hardware id << 40 (XCD, SE, CU, SIMD) */
@@ -81,7 +91,8 @@ struct WaveClock
 enum { WALK_RAYCAST = 0, WALK_GENERATE = 1, WALK_SPATIAL = 2, WALK_RESOLVE = 3, WALK_HINTS = 4 /* rt_occluder_hint_stats: {rays with a hint to test, settled by one, triangle tests, -} */,
        WALK_PICKS = 5 /* rt_neighbour_pick_stats: {neighbour picks of k_spatial_coop, near ties (lanes on the exact path), -, -} */,
        WALK_REPROJECT = 6 /* rt_temporal_reprojection_stats: {shaded pixels merged by a reprojecting launch, valid histories, gathered from another pixel, -} */,
-       WALK_SLOTS = 7 };
+       WALK_MOTION = 7 /* rt_temporal_motion_stats: {shaded pixels merged by a motion launch, on moved triangles, valid histories among those, -} */,
+       WALK_SLOTS = 8 };
 /* one ray per lane at most; works under any exec mask (ballots count the active lanes) */
 RT_DEV void count_walk_flags(unsigned long long* __restrict__ st, bool ref, bool walked, bool self, bool skipped)
 {
@@ -510,11 +521,10 @@ RT_DEV void temporal_rays(const SceneView& S, uint32_t* s_stack, const FramePara
  * that saw sp, or Reservoir{} where there is none. One per-lane gather of a 64-B aligned record + its side record, the access shape
  * of the spatial pass's neighbour read. The pixel index is formed only from coordinates tr_previous_pixel has range-checked in
  * float, and once more against the rows the buffer holds. */
-RT_DEV Res load_prev_reprojected(const FrameParams& P, f3 sp, int x, int row, const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad)
+RT_DEV Res gather_prev_pixel(const FrameParams& P, const TrPixel q, const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad, bool& have)
 {
     Res pr = res_zero();
-    const TrPixel q = tr_previous_pixel(sp, P.prev_origin, P.prev_right, P.prev_up, P.W, P.H);
-    bool have = false;
+    have = false;
     if (q.valid && (unsigned)q.xq < (unsigned)P.W && (unsigned)(q.rq - P.lrow0) < (unsigned)P.lrows)
     {
         const size_t qi = (size_t)q.xq + (size_t)(q.rq - P.lrow0) * P.W;
@@ -528,12 +538,57 @@ RT_DEV Res load_prev_reprojected(const FrameParams& P, f3 sp, int x, int row, co
             have = true;
         }
     }
+    return pr;
+}
+RT_DEV Res load_prev_reprojected(const FrameParams& P, f3 sp, int x, int row, const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad)
+{
+    const TrPixel q = tr_previous_pixel(sp, P.prev_origin, P.prev_right, P.prev_up, P.W, P.H);
+    bool have;
+    const Res pr = gather_prev_pixel(P, q, prev_rec, prev_rad, have);
     if (P.stats) count_walk_flags(P.stats + 4 * WALK_REPROJECT, true, have, have && (q.xq != x || q.rq != row), false);
     return pr;
 }
 
+/* rt_temporal_motion, a history older than the last rt_scene_update (temporal_motion.h). A pixel on a triangle
+ * outside the moved range takes what it takes without the toggle (own pixel under the history's camera bytes, else
+ * load_prev_reprojected) and leaves (h_p, h_n, h_eye) alone. A pixel on a moved triangle gathers the triangle's previous vertices
+ * (48 B per lane, these lanes only), takes the record of the previous frame's pixel that saw its previous surface point, and hands
+ * that point, its normal and the previous eye to the rejection heuristics. (u, v): the pixel's Visibility record; the forms that
+ * traced the primary ray pass theirs, the others (vis_uv == nullptr is theirs) read P.motion_vis, 16 B per pixel. */
+RT_DEV Res load_prev_motion(const FrameParams& P, f3 sp, int x, int row, size_t li, int prim, const float* uv, const float4* __restrict__ prev_rec,
+                            const float4* __restrict__ prev_rad, f3& h_p, f3& h_n, f3& h_eye)
+{
+    const bool in_range = tm_in_range(prim, P.motion_lo, P.motion_hi);
+    Res pr;
+    bool have = false;
+    if (in_range)
+    {
+        float u, v;
+        if (uv) { u = uv[0]; v = uv[1]; }
+        else { const float4 vq = P.motion_vis[li]; u = vq.x; v = vq.y; }
+        f3 v0, v1, v2;
+        load_tri(P.tv_prev, prim, v0, v1, v2);
+        const TmSurface s = tm_previous_surface(v0, v1, v2, u, v, P.eye_prev);
+        const TrPixel q = tr_previous_pixel(s.p, P.prev_origin, P.prev_right, P.prev_up, P.W, P.H);
+        pr = gather_prev_pixel(P, q, prev_rec, prev_rad, have);
+        h_p = s.p; h_n = s.n; h_eye = P.eye_prev;
+    }
+    else if (P.motion_same_camera)
+    {
+        bool dummy;
+        pr = res_load(prev_rec, li, dummy);
+        const float4 pq = prev_rad[li];
+        pr.rad = F3(pq.x, pq.y, pq.z);
+    }
+    else pr = load_prev_reprojected(P, sp, x, row, prev_rec, prev_rad);
+    if (P.stats) count_walk_flags(P.stats + 4 * WALK_MOTION, true, in_range, have, false);
+    return pr;
+}
+
+/* (h_p, h_n, h_eye): what the rejection heuristics compare the history's origin with. The reference's: the record's own origin and
+ * the current eye (temporal_merge below); rt_temporal_motion on a moved triangle: the previous surface point, in the previous frame */
 template <bool SHADOWED>
-RT_DEV bool temporal_merge(const FrameParams& P, int x, int yi, f3 sp, f3 sn, Res& r, Res pr, float V_cur, float V_prev)
+RT_DEV bool temporal_merge_at(const FrameParams& P, int x, int yi, f3 sp, f3 sn, Res& r, Res pr, float V_cur, float V_prev, f3 h_p, f3 h_n, f3 h_eye)
 {
     bool took_prev = false;
     PCG rng = pcg_init(hashPCG4((uint32_t)x, (uint32_t)yi, (uint32_t)P.frame, 1u), 0);
@@ -542,7 +597,7 @@ RT_DEV bool temporal_merge(const FrameParams& P, int x, int yi, f3 sp, f3 sn, Re
     float p_hat_y = SHADOWED ? target_shadowed(sp, sn, pr.hit_p, pr.hit_n, pr.lum, V_prev)
                              : target_unshadowed(sp, sn, pr.hit_p, pr.hit_n, pr.lum);
     if (P.vis_reuse) p_hat_y *= pr.vis ? 1.0f : 0.0f;
-    pr.M = scale_M(pr.M, rejection_heuristics(r.org_p, r.org_n, pr.org_p, pr.org_n, P.eye));
+    pr.M = scale_M(pr.M, rejection_heuristics(h_p, h_n, pr.org_p, pr.org_n, h_eye));
     const float weight = p_hat_y * pr.ucw * (float)pr.M;
     const float u = rng.uniformf();
     r.w_sum += weight;
@@ -558,6 +613,11 @@ RT_DEV bool temporal_merge(const FrameParams& P, int x, int yi, f3 sp, f3 sn, Re
                                  : target_unshadowed(sp, sn, r.hit_p, r.hit_n, r.lum);
     r.ucw = p_hat > 0.0f ? r.w_sum / ((float)r.M * p_hat) : 0.0f;
     return took_prev;
+}
+template <bool SHADOWED>
+RT_DEV bool temporal_merge(const FrameParams& P, int x, int yi, f3 sp, f3 sn, Res& r, Res pr, float V_cur, float V_prev)
+{
+    return temporal_merge_at<SHADOWED>(P, x, yi, sp, sn, r, pr, V_cur, V_prev, r.org_p, r.org_n, P.eye);
 }
 
 /* a pixel's record of remembered occluders (occluder_hint.h) as one aligned word of the hint buffer. The second form reads
@@ -627,7 +687,9 @@ RT_DEV void wave_gather_records(const float4* q, float4* s_wave, const int lane,
  * template parameter: the kernels of the uniform mode are compiled from the text they had. */
 /* REPROJECT (r23, rt_temporal_reprojection): the history record comes from load_prev_reprojected instead of the own pixel. A template
  * parameter for the reason POWER is one; launched only where the history buffer was written under another camera. */
-template <bool FUSE_TEMPORAL, bool SHADOWED, bool DEFER = false, bool PIPE = false, bool WS = false, bool RAYCAST = false, bool POWER = false, bool REPROJECT = false>
+/* MOTION (r24, rt_temporal_motion): the history record comes from load_prev_motion, which follows triangles moved by rt_scene_update;
+ * on top of REPROJECT, launched only where the history buffer is one geometry generation old (restir_rt.hip: history_motion). */
+template <bool FUSE_TEMPORAL, bool SHADOWED, bool DEFER = false, bool PIPE = false, bool WS = false, bool RAYCAST = false, bool POWER = false, bool REPROJECT = false, bool MOTION = false>
 __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED ? RT_GENERATE_SH_WAVES : RT_TRACE_WAVES)) void k_generate_candidate(
     SceneView S, FrameParams P, const float4* __restrict__ g0, const float4* __restrict__ g1,
     const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad, float4* __restrict__ out_rec,
@@ -638,6 +700,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     static_assert(!DEFER || (FUSE_TEMPORAL && !SHADOWED), "deferred visibility: fused unshadowed kernel only");
     static_assert(!RAYCAST || (WS && FUSE_TEMPORAL && !SHADOWED && !DEFER && !PIPE), "primary rays in the product's fused kernel only");
     static_assert(!REPROJECT || (FUSE_TEMPORAL && !DEFER && !PIPE), "reprojected history: the product's fused kernels only");
+    static_assert(!MOTION || REPROJECT, "history that follows moved geometry: a form of the reprojected one");
     RT_WAVE_CLOCK(P);
     constexpr bool LATE = WS && FUSE_TEMPORAL && !SHADOWED && !DEFER; /* the visibility-reuse ray after the temporal merge */
     /* shadowed target: every lane stays through the RIS loop, so that the wavefront can fetch its light records together */
@@ -653,6 +716,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     f3 late_sp = F3(0.0f, 0.0f, 0.0f), late_sn = F3(0.0f, 1.0f, 0.0f);
     Res r = res_zero();
     float4 G0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), G1 = G0;
+    float hit_uv[2] = {0.0f, 0.0f}; /* MOTION with RAYCAST: the primary hit's barycentrics stay in registers */
     if constexpr (RAYCAST)
     {
         if (in_image)
@@ -665,6 +729,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
             gbuffer_make(S, P, h.u, h.v, h.prim, G0, G1);
             g0_w[li] = G0;
             g1_w[li] = G1;
+            if constexpr (MOTION) { hit_uv[0] = h.u; hit_uv[1] = h.v; }
         }
     }
     else if (in_image) { G0 = g0[li]; G1 = g1[li]; }
@@ -880,8 +945,10 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
         r.rad = F3(ke.x, ke.y, ke.z);
     }
     Res pr = res_zero();
+    f3 h_p = r.org_p, h_n = r.org_n, h_eye = P.eye; /* the rejection heuristics' side of the current pixel (temporal_merge_at) */
     auto load_prev = [&]() {
-        if constexpr (REPROJECT) pr = load_prev_reprojected(P, sp, x, row, prev_rec, prev_rad);
+        if constexpr (MOTION) pr = load_prev_motion(P, sp, x, row, li, as_int(G0.w), RAYCAST ? hit_uv : nullptr, prev_rec, prev_rad, h_p, h_n, h_eye);
+        else if constexpr (REPROJECT) pr = load_prev_reprojected(P, sp, x, row, prev_rec, prev_rad);
         else
         {
         bool dummy;
@@ -906,7 +973,8 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     if (FUSE_TEMPORAL)
     {
         if (!SHADOWED) load_prev(); /* after the walk: not live across it */
-        const bool took_prev = temporal_merge<SHADOWED>(P, x, yi, sp, sn, r, pr, V_cur, V_prev);
+        const bool took_prev = MOTION ? temporal_merge_at<SHADOWED>(P, x, yi, sp, sn, r, pr, V_cur, V_prev, h_p, h_n, h_eye)
+                                      : temporal_merge<SHADOWED>(P, x, yi, sp, sn, r, pr, V_cur, V_prev);
         /* the previous frame's sample won: its ray from THIS surface point is known under the shadowed target only */
         if (took_prev) r.ownv = SHADOWED ? ownv_of(P.ownv_tag, V_prev != 0.0f) : 0u;
         /* unshadowed: neither the merge decision nor ucw depends on the candidate's visibility; the bit is stored
@@ -1031,7 +1099,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, RT_RESOLVE_WAVES_FWD) void k_candidate
 #endif /* RT_EXPERIMENTS */
 /* -------------------------------------------------------- temporal_resampling */
 /* examples/10_restir_di/10_restir_di.cu:137-237 (stand-alone entry point) */
-template <bool SHADOWED, bool REPROJECT = false>
+template <bool SHADOWED, bool REPROJECT = false, bool MOTION = false>
 __global__ __launch_bounds__(BLOCK) void k_temporal(SceneView S, FrameParams P, const float4* __restrict__ g0,
                                                      const float4* __restrict__ g1,
                                                      const float4* __restrict__ prev_rec,
@@ -1053,7 +1121,9 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(SceneView S, FrameParams P, 
     r.rad = F3(rq.x, rq.y, rq.z);
     r.ownv = as_uint(rq.w);
     Res pr;
-    if constexpr (REPROJECT) pr = load_prev_reprojected(P, sp, x, row, prev_rec, prev_rad);
+    f3 h_p = r.org_p, h_n = r.org_n, h_eye = P.eye;
+    if constexpr (MOTION) pr = load_prev_motion(P, sp, x, row, li, as_int(G0.w), nullptr, prev_rec, prev_rad, h_p, h_n, h_eye);
+    else if constexpr (REPROJECT) pr = load_prev_reprojected(P, sp, x, row, prev_rec, prev_rad);
     else
     {
     pr = res_load(prev_rec, li, dummy);
@@ -1062,7 +1132,8 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(SceneView S, FrameParams P, 
     }
     float V_cur = 1.0f, V_prev = 1.0f;
     if (SHADOWED) temporal_rays(S, s_stack, P, sp, sn, r, pr, true, V_cur, V_prev, as_int(G0.w));
-    const bool took_prev = temporal_merge<SHADOWED>(P, x, yi, sp, sn, r, pr, V_cur, V_prev);
+    const bool took_prev = MOTION ? temporal_merge_at<SHADOWED>(P, x, yi, sp, sn, r, pr, V_cur, V_prev, h_p, h_n, h_eye)
+                                  : temporal_merge<SHADOWED>(P, x, yi, sp, sn, r, pr, V_cur, V_prev);
     if (SHADOWED) r.ownv = ownv_of(P.ownv_tag, (took_prev ? V_prev : V_cur) != 0.0f);
     else if (took_prev) r.ownv = 0u;
     res_store(rec, radb, li, r, true);

@@ -108,6 +108,18 @@ struct rt_ctx
     rt_raygen rec_rg[5] = {};
     bool rec_rg_has[5] = {false, false, false, false, false};
     bool reproject = false;
+    /* r24, rt_temporal_motion (temporal_motion.h). geo_gen counts rt_scene_update calls since rt_scene_set; a
+     * reservoir buffer's tag also holds the generation and the eye it was written under (rec_gen, rec_eye; valid under rec_rg_has).
+     * While the toggle is on d_tv_prev (layout of d_tv) holds the vertices of generation tvp_gen: equal to d_tv outside the moved
+     * range [mv_lo, mv_hi), the cover of the spans updated since. res_dirty: a reservoir buffer was tagged since the last update, so
+     * the next update re-bases d_tv_prev to the generation it ends instead of growing the range. */
+    uint64_t geo_gen = 0, tvp_gen = 0;
+    uint64_t rec_gen[5] = {0, 0, 0, 0, 0};
+    float rec_eye[5][3] = {};
+    float4* d_tv_prev = nullptr;
+    uint32_t mv_lo = 0, mv_hi = 0;
+    bool res_dirty = false;
+    bool motion = false;
     unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters, then the slot of rt_occluder_hint_stats (WALK_SLOTS) */
     bool walk_on = false;
     /* r19, rt_occluder_hints: OCCLUDER_HINTS triangle indices per pixel of the local rows (occluder_hint.h), the triangles that occluded
@@ -393,6 +405,7 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
     P.pick_mode = c->pick_mode;
     P.stats = c->walk_on ? c->d_walk : nullptr;
     P.prev_origin = P.rg_origin; P.prev_right = P.rg_right; P.prev_up = P.rg_up; /* history_camera sets the history buffer's where it differs */
+    P.eye_prev = P.eye; P.motion_lo = 0u; P.motion_hi = 0u; P.tv_prev = nullptr; P.motion_vis = nullptr; P.motion_same_camera = 1; /* history_motion */
 #ifdef RT_EXPERIMENTS
     P.wave_clock = c->d_wave_clock && kernel == c->wave_clock_kernel && (kernel != K_SPATIAL || pass == c->wave_clock_pass) ? c->d_wave_clock : nullptr;
     /* whole launches over the context's own rows only (the grid the permutation was checked against) */
@@ -401,8 +414,17 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
     return P;
 }
 /* the reservoir buffer `phys` is written under the current camera / holds a copy of buffer `src` */
-static void tag_camera(rt_ctx* c, int phys) { c->rec_rg[phys] = c->rg; c->rec_rg_has[phys] = true; }
-static void copy_camera(rt_ctx* c, int phys, int src) { c->rec_rg[phys] = c->rec_rg[src]; c->rec_rg_has[phys] = c->rec_rg_has[src]; }
+static void tag_camera(rt_ctx* c, int phys)
+{
+    c->rec_rg[phys] = c->rg; c->rec_rg_has[phys] = true;
+    c->rec_gen[phys] = c->geo_gen; memcpy(c->rec_eye[phys], c->eye, sizeof(c->rec_eye[phys]));
+    c->res_dirty = true;
+}
+static void copy_camera(rt_ctx* c, int phys, int src)
+{
+    c->rec_rg[phys] = c->rec_rg[src]; c->rec_rg_has[phys] = c->rec_rg_has[src];
+    c->rec_gen[phys] = c->rec_gen[src]; memcpy(c->rec_eye[phys], c->rec_eye[src], sizeof(c->rec_eye[phys]));
+}
 /* rt_temporal_reprojection: does a temporal merge that reads buffer `prev_phys` as its history gather by reprojection? Only with
  * the mode on and a buffer whose 36 bytes of RayGenerator differ from the current ones (then P carries them); an untagged buffer
  * and a camera that stands still launch what they launched before the mode existed. */
@@ -415,6 +437,36 @@ static bool history_camera(const rt_ctx* c, int prev_phys, FrameParams& P)
     P.prev_right = F3(q.right[0], q.right[1], q.right[2]);
     P.prev_up = F3(q.up[0], q.up[1], q.up[2]);
     return true;
+}
+/* rt_temporal_motion: is a temporal merge that reads buffer `prev_phys` as its history a motion launch? Both toggles on, and a buffer
+ * of exactly the generation d_tv_prev describes, which is not the current one; then P carries the previous camera (also where its
+ * bytes are the current one's), the previous eye, the moved range and the previous vertices. An older history, or one of the
+ * current generation, is history_camera's. `vis`: the Visibility buffer of the launch's rows. */
+static bool history_motion(const rt_ctx* c, int prev_phys, FrameParams& P, const float4* vis)
+{
+    if (!c->motion || !c->reproject || !c->opt.use_temporal_resampling || !c->rec_rg_has[prev_phys] || !c->d_tv_prev) return false;
+    if (c->rec_gen[prev_phys] != c->tvp_gen || c->tvp_gen == c->geo_gen) return false;
+    const rt_raygen& q = c->rec_rg[prev_phys];
+    P.motion_same_camera = tr_same_camera(q.origin, c->rg.origin) ? 1 : 0;
+    P.prev_origin = F3(q.origin[0], q.origin[1], q.origin[2]);
+    P.prev_right = F3(q.right[0], q.right[1], q.right[2]);
+    P.prev_up = F3(q.up[0], q.up[1], q.up[2]);
+    P.eye_prev = F3(c->rec_eye[prev_phys][0], c->rec_eye[prev_phys][1], c->rec_eye[prev_phys][2]);
+    P.motion_lo = c->mv_lo; P.motion_hi = c->mv_hi;
+    P.tv_prev = c->d_tv_prev;
+    P.motion_vis = vis;
+    return true;
+}
+/* d_tv_prev := d_tv, all of it: the toggle going on, or a new scene while it is on. The moved range is empty afterwards. */
+static int motion_rebase_all(rt_ctx* c)
+{
+    hipFree(c->d_tv_prev);
+    c->d_tv_prev = nullptr;
+    c->tvp_gen = c->geo_gen; c->mv_lo = 0; c->mv_hi = 0;
+    if (!c->motion || !c->d_tv || c->n_tris <= 0) return RT_OK;
+    RT_HIP(c, hipMalloc(&c->d_tv_prev, (size_t)c->n_tris * 48));
+    RT_HIP(c, hipMemcpyAsync(c->d_tv_prev, c->d_tv, (size_t)c->n_tris * 48, hipMemcpyDeviceToDevice, c->stream));
+    return RT_OK;
 }
 static_assert(sizeof(rt_raygen) == 36 && offsetof(rt_raygen, right) == 12 && offsetof(rt_raygen, up) == 24, "tr_same_camera reads 9 contiguous floats");
 static uint32_t next_ownv_tag(rt_ctx* c)
@@ -521,6 +573,8 @@ static void free_scene(rt_ctx* c)
     hipFree(c->d_tris); hipFree(c->d_tv); hipFree(c->d_nodes); hipFree(c->d_trimat); hipFree(c->d_lights); hipFree(c->d_light_ke); hipFree(c->d_wide);
     hipFree(c->d_lights_power); hipFree(c->d_alias);
     c->d_lights_power = nullptr; c->d_alias = nullptr;
+    hipFree(c->d_tv_prev);
+    c->d_tv_prev = nullptr;
     c->h_light_w.clear(); c->h_alias.clear(); c->h_alias_K.clear(); c->alias_ok = false;
     hipFree(c->d_light_ids); hipFree(c->d_refit_list); hipFree(c->d_refit_box); hipFree(c->d_refit_bounds);
     c->d_light_ids = nullptr; c->d_refit_list = nullptr; c->d_refit_box = nullptr; c->d_refit_bounds = nullptr;
@@ -1216,6 +1270,7 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     drop_look_ahead(c);
     c->dt_valid = false; /* rt_denoise_temporal's history belongs to the old scene */
     for (int k = 0; k < 5; ++k) c->rec_rg_has[k] = false; /* ... and so do the reservoir buffers' camera tags: no reprojection into it */
+    c->geo_gen = 0; c->tvp_gen = 0; c->mv_lo = 0; c->mv_hi = 0; c->res_dirty = false; /* rt_temporal_motion: generations count from the new scene */
     /* the remembered occluders are indices of the old scene, which may have had more triangles (every stream is idle here) */
     if (c->d_hints) RT_HIP(c, hipMemset(c->d_hints, 0xff, local_pixels(c) * sizeof(int) * OCCLUDER_HINTS));
     const auto t_build0 = std::chrono::steady_clock::now();
@@ -1255,6 +1310,7 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     }
     const int rc = build_bvh(c, triangles, n);
     if (rc != RT_OK) return rc;
+    { const int rm = motion_rebase_all(c); if (rm != RT_OK) return rm; }
     RT_HIP(c, hipStreamSynchronize(c->stream));
     c->build_ms = (float)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_build0).count() * 1e-3f;
     c->h_lights.swap(lights);
@@ -1469,6 +1525,23 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     if (lights.size() > ((size_t)1 << 26)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "more than 2^26 emissive triangles (the light table is addressed by 32-bit byte offsets)");
     if (c->refit_off.empty()) { const int rc = refit_topology(c); if (rc != RT_OK) return rc; }
     if (c->cost_at_build < 0.0) { const int rc = refit_first_update(c); if (rc != RT_OK) return rc; }
+    /* rt_temporal_motion: d_tv still holds the old vertices here. A reservoir buffer written since the last update carries the
+     * generation this update ends: d_tv_prev is brought to it (it differs from d_tv over the old moved range only) and a new range
+     * starts. Otherwise no history of the generations in between exists, and the range grows to cover this span too. */
+    if (c->d_tv_prev)
+    {
+        if (c->res_dirty)
+        {
+            if (c->mv_hi > c->mv_lo)
+                RT_HIP(c, hipMemcpyAsync(c->d_tv_prev + 3 * (size_t)c->mv_lo, c->d_tv + 3 * (size_t)c->mv_lo, (size_t)(c->mv_hi - c->mv_lo) * 48, hipMemcpyDeviceToDevice, st));
+            c->tvp_gen = c->geo_gen;
+            c->mv_lo = first; c->mv_hi = first + count;
+        }
+        else if (c->mv_hi > c->mv_lo) { c->mv_lo = std::min(c->mv_lo, first); c->mv_hi = std::max(c->mv_hi, first + count); }
+        else { c->mv_lo = first; c->mv_hi = first + count; }
+    }
+    ++c->geo_gen;
+    c->res_dirty = false;
     /* per-triangle arrays of the span */
     RT_HIP(c, hipMemcpyAsync(c->d_tris + 15 * (size_t)first, triangles, (size_t)count * 60, hipMemcpyHostToDevice, st));
     const int gs = (int)((count + 255) / 256);
@@ -2038,7 +2111,9 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
     const bool sh = c->opt.use_shadowed_target_function;
     float4 *orec = c->d_rec[dst_phys], *orad = c->d_rad[dst_phys];
     c->rec_gserial[dst_phys] = c->gbuf.serial;
-    const bool rp = fuse && history_camera(c, prev_phys, P); /* before the tag below: dst may not be prev, but the order costs nothing */
+    /* before the tag below: dst may not be prev, but the order costs nothing. A motion launch is a reprojecting one (mo implies rp) */
+    const bool mo = fuse && history_motion(c, prev_phys, P, L.vis);
+    const bool rp = mo || (fuse && history_camera(c, prev_phys, P));
     tag_camera(c, dst_phys);
     const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
     const int g = trace_grid(c, L);
@@ -2052,12 +2127,14 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
 #define GEN_LAUNCH_RP(SH, WS_, RC, ...)                                                                                           \
     do {                                                                                                                          \
         if (!rp) GEN_LAUNCH(true, SH, false, false, WS_, RC, __VA_ARGS__);                                                         \
+        else if (mo && power) k_generate_candidate<true, SH, false, false, WS_, RC, true, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
+        else if (mo) k_generate_candidate<true, SH, false, false, WS_, RC, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
         else if (power) k_generate_candidate<true, SH, false, false, WS_, RC, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
         else k_generate_candidate<true, SH, false, false, WS_, RC, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);     \
     } while (0)
 #ifdef RT_EXPERIMENTS
     if (rp && fuse && ((!sh && c->tune_defer_vis) || (!sh && c->tune_ris_pipe)))
-        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_reprojection: the [exp] stage-0 variants (rt_tuning keys 11 and 12) gather their history from the own pixel only");
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_reprojection / rt_temporal_motion: the [exp] stage-0 variants (rt_tuning keys 11 and 12) gather their history from the own pixel only");
     if (fuse && !sh && c->tune_defer_vis)
     {
         /* fused + unshadowed: the visibility-reuse rays that survive the temporal merge go through a queue */
@@ -2136,9 +2213,14 @@ int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
     const Launch L = whole_launch(c);
     FrameParams P = make_params(c, L, frame, 0);
     const int pp = c->frame.res_map[prev], pi = c->frame.res_map[inout];
-    const bool rp = history_camera(c, pp, P);
+    const bool mo = history_motion(c, pp, P, c->gbuf.vis);
+    const bool rp = !mo && history_camera(c, pp, P);
     tag_camera(c, pi);
-    if (rp && c->opt.use_shadowed_target_function)
+    if (mo && c->opt.use_shadowed_target_function)
+        k_temporal<true, true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+    else if (mo)
+        k_temporal<false, true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+    else if (rp && c->opt.use_shadowed_target_function)
         k_temporal<true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
     else if (rp)
         k_temporal<false, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
@@ -3072,6 +3154,62 @@ int rt_temporal_reprojection_stats(rt_ctx* c, uint64_t out[3])
     int rc = rt_sync(c);
     if (rc != RT_OK) return rc;
     RT_HIP(c, hipMemcpy(out, c->d_walk + 4 * WALK_REPROJECT, 3 * 8, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+/* r24. Temporal history that follows triangles moved by rt_scene_update (temporal_motion.h), in effect only while
+ * rt_temporal_reprojection is on. Changes results, so not an rt_tuning key; counts as an option change and drops the look-ahead. Touches
+ * no reservoir buffer. On: d_tv_prev is allocated as a copy of the current vertices (no update is followed backwards); off: freed. */
+int rt_temporal_motion(rt_ctx* c, int on)
+{
+    RT_CHECK_CTX(c);
+    if (!whole_frame(c))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_motion: a strip context holds only its own rows of the history");
+    RT_HIP(c, hipSetDevice(c->device));
+    const bool was = c->motion;
+    c->motion = on != 0;
+    drop_look_ahead(c);
+    ++c->epoch;
+    if (c->motion == was) return RT_OK;
+    /* launches in flight may read d_tv_prev */
+    { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
+    return motion_rebase_all(c);
+}
+int rt_temporal_motion_get(rt_ctx* c, int* on)
+{
+    RT_CHECK_CTX(c);
+    if (!on) return RT_ERR_ARG;
+    *on = c->motion ? 1 : 0;
+    return RT_OK;
+}
+int rt_reservoir_scene(rt_ctx* c, int res, uint64_t* generation, float eye[3], int* has)
+{
+    RT_CHECK_CTX(c);
+    NEED_RES(c, res);
+    if (!generation && !eye && !has) return RT_ERR_ARG;
+    const int phys = c->frame.res_map[res];
+    const bool h = c->rec_rg_has[phys];
+    if (has) *has = h ? 1 : 0;
+    if (generation) *generation = h ? c->rec_gen[phys] : 0;
+    if (eye) for (int k = 0; k < 3; ++k) eye[k] = h ? c->rec_eye[phys][k] : 0.0f;
+    return RT_OK;
+}
+int rt_temporal_motion_range(rt_ctx* c, uint32_t* lo, uint32_t* hi, uint64_t* generation)
+{
+    RT_CHECK_CTX(c);
+    if (!lo && !hi && !generation) return RT_ERR_ARG;
+    if (lo) *lo = c->mv_lo;
+    if (hi) *hi = c->mv_hi;
+    if (generation) *generation = c->tvp_gen;
+    return RT_OK;
+}
+int rt_temporal_motion_stats(rt_ctx* c, uint64_t out[3])
+{
+    RT_CHECK_CTX(c);
+    if (!out) return RT_ERR_ARG;
+    if (!c->d_walk) RT_FAIL(c, RT_ERR_STATE, "rt_walk_stats_enable first");
+    int rc = rt_sync(c);
+    if (rc != RT_OK) return rc;
+    RT_HIP(c, hipMemcpy(out, c->d_walk + 4 * WALK_MOTION, 3 * 8, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 /* How the candidates pick their light (light_alias.h). Changes results, so not an rt_tuning key; counts as an

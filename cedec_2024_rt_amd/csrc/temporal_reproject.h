@@ -11,8 +11,9 @@
  * (frame_kernels.h): the random number is keyed by the CURRENT pixel and drawn either way, the rejection heuristics see the
  * gathered record's origin position / normal, the shadowed target function's ray goes to the gathered sample.
  *
- * Out of scope: geometry moved by rt_scene_update. The reprojection uses the two cameras only, so the history of a surface
+ * Not followed here: geometry moved by rt_scene_update. The reprojection uses the two cameras only, so the history of a surface
  * that moved is looked up where the surface is NOW, and meets the rejection heuristics exactly as it does with the mode off.
+ * rt_temporal_motion (temporal_motion.h) follows it, on top of this header.
  *
  * RT_HD functions over IEEE +, -, *, / and the correctly rounded square root of rt_device.h: compiled by hipcc and by
  * `g++ -ffp-contract=off` they give the same bits, so the CPU restatement (tests/temporal_reproject_ref.py) picks the

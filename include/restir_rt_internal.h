@@ -316,6 +316,32 @@ int rt_reservoir_camera(rt_ctx* ctx, int res, rt_raygen* out, int* has);
 /* counted while rt_walk_stats_enable is on, zeroed by it: out[0] = shaded pixels merged by a reprojecting launch, out[1] = those that
  * found a valid history, out[2] = those among them whose history came from another pixel than their own. Synchronises. */
 int rt_temporal_reprojection_stats(rt_ctx* ctx, uint64_t out[3]);
+/* (r24) Temporal reuse that follows moved geometry (csrc/temporal_motion.h), default off, in effect only while
+ * rt_temporal_reprojection is on: with it off every byte and every launch is what it was without the call. rt_scene_update counts a
+ * geometry generation (0 after rt_scene_set); every physical reservoir buffer's tag also carries the generation and the eye it was
+ * written under, set, copied and cleared with the camera tag. While the toggle is on the context keeps the vertex positions of one
+ * earlier generation (rt_temporal_motion_range: which, and the covering range [lo, hi) of the spans updated since). rt_scene_update
+ * brings them to the generation it ends when a reservoir buffer was written since the last update, and otherwise only grows the
+ * range, so that several spans moved between two frames are all followed. A temporal merge whose history buffer carries exactly
+ * that generation, and that generation is not the current one, is a motion launch: a shaded pixel whose triangle lies in [lo, hi)
+ * takes the history of the previous frame's pixel that saw the point its surface point was at (the pixel's barycentrics on the
+ * triangle's previous vertices, projected into the buffer's camera, also where that camera's bytes are the current one's), or
+ * Reservoir{} where there is none, and the rejection heuristics compare that previous point, its normal and the previous eye with
+ * the gathered record's origin. Every other pixel, and every merge that is no motion launch (an older history included), does
+ * what rt_temporal_reprojection alone does. Not followed: moved emitters as samples, stale visibility flags, the temporal
+ * denoiser, strips, changes of triangle count or order. The call changes rt_state_epoch and drops look-ahead work, touches no
+ * reservoir buffer; going on it copies the current vertices (updates before it are not followed), going off it frees them. Strip
+ * contexts: RT_ERR_UNSUPPORTED. The [exp] stage-0 variants (rt_tuning keys 11 and 12): RT_ERR_UNSUPPORTED at a motion launch. */
+int rt_temporal_motion(rt_ctx* ctx, int on);
+int rt_temporal_motion_get(rt_ctx* ctx, int* on);
+/* the scene tag of RT_RES_* (tests): *has = 1, the geometry generation and the eye the buffer was written under, or *has = 0 and
+ * zeros; any pointer may be null, not all */
+int rt_reservoir_scene(rt_ctx* ctx, int res, uint64_t* generation, float eye[3], int* has);
+/* the moved range and the generation the kept vertex positions describe (0, 0 and the current generation: nothing moved since) */
+int rt_temporal_motion_range(rt_ctx* ctx, uint32_t* lo, uint32_t* hi, uint64_t* generation);
+/* counted while rt_walk_stats_enable is on, zeroed by it: out[0] = shaded pixels merged by a motion launch, out[1] = those on a
+ * triangle of the moved range, out[2] = those among them that found a valid history. Synchronises. */
+int rt_temporal_motion_stats(rt_ctx* ctx, uint64_t out[3]);
 /* the alias table and the realised counts (thr / alias / K per light, light list order; any pointer may be null), for tests; n = the
  * scene's light count (RT_ERR_ARG otherwise); RT_ERR_STATE without a scene */
 int rt_light_table(rt_ctx* ctx, uint32_t* thr, uint32_t* alias, uint64_t* K, uint32_t n);
