@@ -11,7 +11,7 @@
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
  *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased] [--reproject]
- *              [--move-tris first count dx dy dz] [--follow-motion]
+ *              [--move-tris first count dx dy dz] [--follow-motion] [--denoise-follow-motion]
  *              [--light-sampling uniform|power]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
@@ -38,6 +38,9 @@
  *     [first, first + count) moves by (dx, dy, dz) before every frame from the second on (the same float add); not with --move-lights.
  * --follow-motion (with --reproject): rt_temporal_motion, the temporal merge of a pixel on a moved triangle takes the history of the
  *     previous frame's pixel that saw the point it was at; meant for --move-tris on non-emissive triangles.
+ * --denoise-follow-motion (with --denoise N --denoise-temporal): rt_denoise_temporal_motion, the denoiser's history of a pixel on a
+ *     moved triangle is looked up from where its surface point was; meant for --move-tris. Each frame's
+ *     denoise line then says whether the call followed.
  * --example 6: the same ambient occlusion ON THE GPU through rt_path_trace (examples/06_ao_hiprt/06_ao_hiprt.cu:35-91, the
  * same image as 04_ao's kernel). Defaults follow 06_ao_hiprt.cpp:79-80: 1920x1080, camera (8,8,8) -> (0,0,0), fovy pi/4.
  * --frames K times K launches after one warm-up (host clock around rt_sync) and prints ms per launch and Mray/s in the
@@ -449,7 +452,7 @@ int main(int argc, char** argv)
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
-    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false, follow_motion = false, move_lights_given = false;
+    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false, follow_motion = false, move_lights_given = false, denoise_follow = false;
     int light_mode = RT_LIGHTS_UNIFORM;
     float orbit_d[2] = {0.0f, 0.0f};
     LightMove mv;
@@ -498,6 +501,7 @@ int main(int argc, char** argv)
         else if (a == "--unbiased") unbiased = true;
         else if (a == "--reproject") reproject = true;
         else if (a == "--follow-motion") follow_motion = true;
+        else if (a == "--denoise-follow-motion") denoise_follow = true;
         else if (a == "--light-sampling")
         {
             const std::string m = i + 1 < argc ? argv[++i] : "";
@@ -520,6 +524,7 @@ int main(int argc, char** argv)
     if (denoise_temporal && denoise < 0) { fprintf(stderr, "--denoise-temporal needs --denoise N\n"); return 2; }
     if (unbiased && (ranks > 1 || example != 10)) { fprintf(stderr, "--unbiased applies to one GPU and --example 10\n"); return 2; }
     if (reproject && (ranks > 1 || example != 10)) { fprintf(stderr, "--reproject applies to one GPU and --example 10\n"); return 2; }
+    if (denoise_follow && !denoise_temporal) { fprintf(stderr, "--denoise-follow-motion needs --denoise N --denoise-temporal\n"); return 2; }
     if (follow_motion && !reproject) { fprintf(stderr, "--follow-motion needs --reproject\n"); return 2; }
     if (mv.all && move_lights_given) { fprintf(stderr, "--move-tris and --move-lights exclude each other\n"); return 2; }
     if (light_mode != RT_LIGHTS_UNIFORM && example != 10) { fprintf(stderr, "--light-sampling applies to --example 10\n"); return 2; }
@@ -637,6 +642,7 @@ int main(int argc, char** argv)
     if (unbiased) CK(rt_spatial_unbiased(ctx, 1));
     if (reproject) CK(rt_temporal_reprojection(ctx, 1));
     if (follow_motion) CK(rt_temporal_motion(ctx, 1));
+    if (denoise_follow) CK(rt_denoise_temporal_motion(ctx, 1));
     CK(rt_light_sampling(ctx, light_mode));
     CK(rt_timing_enable(ctx, 1));
     CK(rt_clear(ctx)); /* :222-226 */
@@ -701,8 +707,15 @@ int main(int argc, char** argv)
         {
             float tms[6];
             CK(rt_denoise_temporal_timing(ctx, tms));
-            printf("frame %d denoise: %.3f ms (guide %.3f, reprojection %.3f, variance %.3f, %d iterations %.3f)\n", frame, tms[5], tms[0], tms[1],
+            printf("frame %d denoise: %.3f ms (guide %.3f, reprojection %.3f, variance %.3f, %d iterations %.3f)", frame, tms[5], tms[0], tms[1],
                    tms[2], denoise, tms[3] + tms[4]);
+            if (denoise_follow)
+            {
+                int followed = 0;
+                CK(rt_denoise_temporal_motion_get(ctx, nullptr, &followed));
+                printf(followed ? " followed moved geometry" : " camera only");
+            }
+            printf("\n");
         }
         else if (denoise >= 0)
         {

@@ -48,6 +48,7 @@ INTERNAL_EXPORTS = [
     "rt_light_sampling", "rt_light_sampling_get", "rt_light_table",
     "rt_temporal_reprojection", "rt_temporal_reprojection_get", "rt_reservoir_camera", "rt_temporal_reprojection_stats",
     "rt_temporal_motion", "rt_temporal_motion_get", "rt_reservoir_scene", "rt_temporal_motion_range", "rt_temporal_motion_stats",
+    "rt_denoise_temporal_motion", "rt_denoise_temporal_motion_get",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -212,6 +213,9 @@ def load_library(exp=False, path=None):
         L.rt_reservoir_scene.argtypes = [vp, ci, vp, vp, vp]
         L.rt_temporal_motion_range.argtypes = [vp, vp, vp, vp]
         L.rt_temporal_motion_stats.argtypes = [vp, vp]
+    if hasattr(L, "rt_denoise_temporal_motion"):  # r25; likewise
+        L.rt_denoise_temporal_motion.argtypes = [vp, ci]
+        L.rt_denoise_temporal_motion_get.argtypes = [vp, vp, vp]
     L.rt_visibility_rays_walked.argtypes = [vp, vp]
     L.rt_state_epoch.argtypes = [vp, vp]
     L.rt_get_stream.argtypes = [vp, vp]
@@ -886,6 +890,18 @@ class Renderer:
         v = C.c_int()
         self._ck(self.L.rt_temporal_motion_get(self.h, C.byref(v)))
         return bool(v.value)
+
+    def denoise_temporal_motion(self, on=None):
+        """rt_denoise_temporal_motion: denoise_temporal's history of a pixel on a triangle that update_scene has moved since the previous
+        call is looked up from where its surface point was. Default off; independent of temporal_reprojection and
+        temporal_motion. on=None queries. Returns dict(on, followed): the state, and whether the last denoise_temporal call followed."""
+        if not hasattr(self.L, "rt_denoise_temporal_motion"):  # an older build through RT_LIB_PATH: the toggle is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_denoise_temporal_motion")
+        if on is not None:
+            self._ck(self.L.rt_denoise_temporal_motion(self.h, int(bool(on))))
+        v, f = C.c_int(), C.c_int()
+        self._ck(self.L.rt_denoise_temporal_motion_get(self.h, C.byref(v), C.byref(f)))
+        return dict(on=bool(v.value), followed=bool(f.value))
 
     def reservoir_scene(self, res):
         """rt_reservoir_scene: (geometry generation, eye as 3 float32) reservoir buffer RT_RES_* was last written under, or None while it

@@ -17,9 +17,12 @@
  *   k_denoise_temporal  reprojection into the previous camera, demodulation and integration: col = {c, 0} (or {0, 0, 0, -1}) and
  *                       the moments record {mu1, mu2, h, 0}
  *   k_denoise_var_hist  col' = {c, var}: the temporal variance where h >= 4, k_denoise_var's window elsewhere
+ *   k_denoise_temporal_motion  k_denoise_temporal for a followed call of rt_denoise_temporal_motion (denoise_motion.h): pixels on a
+ *                       triangle rt_scene_update moved look their history up from where their surface point was
  */
 #pragma once
 #include "denoise_math.h"
+#include "denoise_motion.h"
 
 /* rt_tuning key 28 default: the residue lattice in LDS (1), 1.13 against 1.19 ms of filter at 5 iterations, 1080p */
 #ifndef DN_LAYOUT_DEFAULT
@@ -136,12 +139,22 @@ struct DnTemporal
     float alpha_c, alpha_m;
     int has_history; /* 0: the first call after a reset (the previous buffers are not read) */
 };
-/* one pass per pixel: 2 guide records, the accumulation, the albedo, and per valid tap 4 records of the previous frame */
-__global__ __launch_bounds__(BLOCK) void k_denoise_temporal(FrameParams P, DnTemporal T, const float4* __restrict__ trimat,
-                                                            const float4* __restrict__ accum, const float4* __restrict__ gx,
-                                                            const float4* __restrict__ gn, const float4* __restrict__ pgx,
-                                                            const float4* __restrict__ pgn, const float4* __restrict__ hcol,
-                                                            const float4* __restrict__ hmom, float4* __restrict__ col, float4* __restrict__ mom)
+/* what a followed call adds (rt_denoise_temporal_motion, denoise_motion.h): read by k_denoise_temporal_motion only */
+struct DnMotion
+{
+    f3 eye_prev;                       /* the eye of the previous call */
+    uint32_t lo, hi;                   /* the moved range */
+    const float4* __restrict__ tv_prev; /* the vertices of the history's generation (layout of the BVH's tv: 3 records per triangle) */
+    const float4* __restrict__ vis;     /* this call's guide hits {u, v, prim, 0} */
+};
+/* one pass per pixel: 2 guide records, the accumulation, the albedo, and per valid tap 4 records of the previous frame.
+ * MOTION (a followed call): + the pixel's vis record, and for the lanes on a triangle of the moved range the 48 bytes of its previous
+ * vertices; reprojection and tap test then run on the previous surface point and normal. MOTION = false is the r10 kernel. */
+template <bool MOTION>
+RT_DEV void dn_temporal_pixel(const FrameParams& P, const DnTemporal& T, const DnMotion* M, const float4* __restrict__ trimat,
+                              const float4* __restrict__ accum, const float4* __restrict__ gx, const float4* __restrict__ gn,
+                              const float4* __restrict__ pgx, const float4* __restrict__ pgn, const float4* __restrict__ hcol,
+                              const float4* __restrict__ hmom, float4* __restrict__ col, float4* __restrict__ mom)
 {
     int x, row;
     if (!tile_pixel(P, x, row)) return;
@@ -157,7 +170,18 @@ __global__ __launch_bounds__(BLOCK) void k_denoise_temporal(FrameParams P, DnTem
     }
     const f3 e = dn_demodulate(A, dn_albedo(trimat, word));
     const float4 xp4 = gx[li];
-    const f3 xp = F3(xp4.x, xp4.y, xp4.z), np = F3(np4.x, np4.y, np4.z);
+    f3 xp = F3(xp4.x, xp4.y, xp4.z), np = F3(np4.x, np4.y, np4.z); /* the lookup point and normal (x_l, n_l) */
+    if (MOTION)
+    {
+        const float4 vq = M->vis[li];
+        const int prim = dn_tri(word);
+        if (tm_in_range(prim, M->lo, M->hi))
+        {
+            f3 v0, v1, v2;
+            load_tri(M->tv_prev, prim, v0, v1, v2);
+            dn_motion_lookup(v0, v1, v2, vq.x, vq.y, M->eye_prev, xp, np);
+        }
+    }
     DnHistory s = dn_history_init();
     float px, pr;
     if (T.has_history && dn_reproject(xp, T.rg_origin, T.rg_right, T.rg_up, P.W, P.H, px, pr))
@@ -180,6 +204,22 @@ __global__ __launch_bounds__(BLOCK) void k_denoise_temporal(FrameParams P, DnTem
     dn_temporal_integrate(s, e, T.alpha_c, T.alpha_m, c, m);
     col[li] = c;
     mom[li] = m;
+}
+__global__ __launch_bounds__(BLOCK) void k_denoise_temporal(FrameParams P, DnTemporal T, const float4* __restrict__ trimat,
+                                                            const float4* __restrict__ accum, const float4* __restrict__ gx,
+                                                            const float4* __restrict__ gn, const float4* __restrict__ pgx,
+                                                            const float4* __restrict__ pgn, const float4* __restrict__ hcol,
+                                                            const float4* __restrict__ hmom, float4* __restrict__ col, float4* __restrict__ mom)
+{
+    dn_temporal_pixel<false>(P, T, nullptr, trimat, accum, gx, gn, pgx, pgn, hcol, hmom, col, mom);
+}
+__global__ __launch_bounds__(BLOCK) void k_denoise_temporal_motion(FrameParams P, DnTemporal T, DnMotion M, const float4* __restrict__ trimat,
+                                                                   const float4* __restrict__ accum, const float4* __restrict__ gx,
+                                                                   const float4* __restrict__ gn, const float4* __restrict__ pgx,
+                                                                   const float4* __restrict__ pgn, const float4* __restrict__ hcol,
+                                                                   const float4* __restrict__ hmom, float4* __restrict__ col, float4* __restrict__ mom)
+{
+    dn_temporal_pixel<true>(P, T, &M, trimat, accum, gx, gn, pgx, pgn, hcol, hmom, col, mom);
 }
 __global__ __launch_bounds__(BLOCK) void k_denoise_var_hist(FrameParams P, DnParams D, const float4* __restrict__ gx, const float4* __restrict__ gn,
                                                             const float4* __restrict__ mom, const float4* __restrict__ cin, float4* __restrict__ cout)

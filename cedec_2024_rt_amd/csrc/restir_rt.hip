@@ -120,6 +120,9 @@ struct rt_ctx
     uint32_t mv_lo = 0, mv_hi = 0;
     bool res_dirty = false;
     bool motion = false;
+    /* r25, rt_denoise_temporal_motion (denoise_motion.h): the second consumer of d_tv_prev. The buffer exists
+     * while either toggle is on. dt_dirty: rt_denoise_temporal tagged its history since the last update (set only while dn_motion). */
+    bool dn_motion = false, dt_dirty = false;
     unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters, then the slot of rt_occluder_hint_stats (WALK_SLOTS) */
     bool walk_on = false;
     /* r19, rt_occluder_hints: OCCLUDER_HINTS triangle indices per pixel of the local rows (occluder_hint.h), the triangles that occluded
@@ -293,6 +296,9 @@ struct rt_ctx
      * dt_valid: a history exists (rt_scene_set and rt_denoise_temporal_reset clear it). It scratches d_dn_col / d_dn_vis / d_dn_hdr. */
     float4 *d_dt_gx[2] = {nullptr, nullptr}, *d_dt_gn[2] = {nullptr, nullptr}, *d_dt_mom[2] = {nullptr, nullptr}, *d_dt_col = nullptr;
     rt_raygen dt_rg;
+    uint64_t dt_gen = 0;                  /* the geometry generation and the eye the history was written under (next to dt_rg) */
+    float dt_eye[3] = {0.0f, 0.0f, 0.0f};
+    bool dt_followed = false;             /* the last rt_denoise_temporal call was a followed call */
     int dt_cur = 0;
     bool dt_valid = false, dt_timed = false;
     hipEvent_t dt_ev[6] = {};
@@ -457,13 +463,14 @@ static bool history_motion(const rt_ctx* c, int prev_phys, FrameParams& P, const
     P.motion_vis = vis;
     return true;
 }
-/* d_tv_prev := d_tv, all of it: the toggle going on, or a new scene while it is on. The moved range is empty afterwards. */
+/* d_tv_prev := d_tv, all of it: the first of the two toggles (rt_temporal_motion, rt_denoise_temporal_motion) going on, the last
+ * going off, or a new scene while either is on. The moved range is empty afterwards. */
 static int motion_rebase_all(rt_ctx* c)
 {
     hipFree(c->d_tv_prev);
     c->d_tv_prev = nullptr;
     c->tvp_gen = c->geo_gen; c->mv_lo = 0; c->mv_hi = 0;
-    if (!c->motion || !c->d_tv || c->n_tris <= 0) return RT_OK;
+    if (!(c->motion || c->dn_motion) || !c->d_tv || c->n_tris <= 0) return RT_OK;
     RT_HIP(c, hipMalloc(&c->d_tv_prev, (size_t)c->n_tris * 48));
     RT_HIP(c, hipMemcpyAsync(c->d_tv_prev, c->d_tv, (size_t)c->n_tris * 48, hipMemcpyDeviceToDevice, c->stream));
     return RT_OK;
@@ -1270,7 +1277,7 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     drop_look_ahead(c);
     c->dt_valid = false; /* rt_denoise_temporal's history belongs to the old scene */
     for (int k = 0; k < 5; ++k) c->rec_rg_has[k] = false; /* ... and so do the reservoir buffers' camera tags: no reprojection into it */
-    c->geo_gen = 0; c->tvp_gen = 0; c->mv_lo = 0; c->mv_hi = 0; c->res_dirty = false; /* rt_temporal_motion: generations count from the new scene */
+    c->geo_gen = 0; c->tvp_gen = 0; c->mv_lo = 0; c->mv_hi = 0; c->res_dirty = false; c->dt_dirty = false; /* rt_temporal_motion: generations count from the new scene */
     /* the remembered occluders are indices of the old scene, which may have had more triangles (every stream is idle here) */
     if (c->d_hints) RT_HIP(c, hipMemset(c->d_hints, 0xff, local_pixels(c) * sizeof(int) * OCCLUDER_HINTS));
     const auto t_build0 = std::chrono::steady_clock::now();
@@ -1525,12 +1532,13 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     if (lights.size() > ((size_t)1 << 26)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "more than 2^26 emissive triangles (the light table is addressed by 32-bit byte offsets)");
     if (c->refit_off.empty()) { const int rc = refit_topology(c); if (rc != RT_OK) return rc; }
     if (c->cost_at_build < 0.0) { const int rc = refit_first_update(c); if (rc != RT_OK) return rc; }
-    /* rt_temporal_motion: d_tv still holds the old vertices here. A reservoir buffer written since the last update carries the
+    /* rt_temporal_motion / rt_denoise_temporal_motion: d_tv still holds the old vertices here. A history (a reservoir buffer for the
+     * first, the denoiser's for the second) written since the last update by a consumer whose toggle is on carries the
      * generation this update ends: d_tv_prev is brought to it (it differs from d_tv over the old moved range only) and a new range
      * starts. Otherwise no history of the generations in between exists, and the range grows to cover this span too. */
     if (c->d_tv_prev)
     {
-        if (c->res_dirty)
+        if ((c->motion && c->res_dirty) || (c->dn_motion && c->dt_dirty))
         {
             if (c->mv_hi > c->mv_lo)
                 RT_HIP(c, hipMemcpyAsync(c->d_tv_prev + 3 * (size_t)c->mv_lo, c->d_tv + 3 * (size_t)c->mv_lo, (size_t)(c->mv_hi - c->mv_lo) * 48, hipMemcpyDeviceToDevice, st));
@@ -1542,6 +1550,7 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     }
     ++c->geo_gen;
     c->res_dirty = false;
+    c->dt_dirty = false;
     /* per-triangle arrays of the span */
     RT_HIP(c, hipMemcpyAsync(c->d_tris + 15 * (size_t)first, triangles, (size_t)count * 60, hipMemcpyHostToDevice, st));
     const int gs = (int)((count + 255) / 256);
@@ -2723,8 +2732,21 @@ int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_de
     T.has_history = c->dt_valid ? 1 : 0;
     const int g = launch_grid(c, whole_launch(c));
     float4 *gx = c->d_dt_gx[cur], *gn = c->d_dt_gn[cur], *mom = c->d_dt_mom[cur];
-    k_denoise_temporal<<<g, BLOCK, 0, st>>>(P, T, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
-                                            c->d_dt_mom[prev], c->d_dn_col[1], mom);
+    /* rt_denoise_temporal_motion: a history of exactly the generation d_tv_prev describes, which is not the current one */
+    const bool followed = dn_motion_followed(c->dn_motion, c->dt_valid, c->d_tv_prev != nullptr, c->dt_gen, c->tvp_gen, c->geo_gen);
+    if (followed)
+    {
+        DnMotion M;
+        M.eye_prev = F3(c->dt_eye[0], c->dt_eye[1], c->dt_eye[2]);
+        M.lo = c->mv_lo; M.hi = c->mv_hi;
+        M.tv_prev = c->d_tv_prev;
+        M.vis = c->d_dn_vis;
+        k_denoise_temporal_motion<<<g, BLOCK, 0, st>>>(P, T, M, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
+                                                       c->d_dt_mom[prev], c->d_dn_col[1], mom);
+    }
+    else
+        k_denoise_temporal<<<g, BLOCK, 0, st>>>(P, T, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
+                                                c->d_dt_mom[prev], c->d_dn_col[1], mom);
     RT_HIP(c, hipGetLastError());
     if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[2], st));
     float4* var_out = d.iterations == 0 ? c->d_dt_col : c->d_dn_col[0];
@@ -2747,10 +2769,40 @@ int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_de
     }
     if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[5], st));
     c->dt_rg = c->rg;
+    c->dt_gen = c->geo_gen; memcpy(c->dt_eye, c->eye, sizeof(c->dt_eye));
+    if (c->dn_motion) c->dt_dirty = true;
+    c->dt_followed = followed;
     c->dt_cur = cur;
     c->dt_valid = true;
     c->dt_timed = timed;
     c->dn_valid = true;
+    return RT_OK;
+}
+/* r25. rt_denoise_temporal's history follows triangles moved by rt_scene_update (denoise_motion.h). Changes
+ * results, so not an rt_tuning key. Independent of rt_temporal_reprojection / rt_temporal_motion, with which it shares d_tv_prev: the
+ * first of the two toggles going on allocates it as a copy of the current vertices with an empty range, the last going off frees it
+ * (after the stream has drained: launches in flight may read it); a toggle going on while it exists leaves it and the range alone.
+ * Touches neither rt_state_epoch nor the look-ahead nor any reservoir or history buffer. */
+int rt_denoise_temporal_motion(rt_ctx* c, int on)
+{
+    RT_CHECK_CTX(c);
+    if (!whole_frame(c))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_denoise_temporal_motion: rt_denoise_temporal is for whole-frame contexts");
+    RT_HIP(c, hipSetDevice(c->device));
+    const bool was = c->dn_motion;
+    c->dn_motion = on != 0;
+    if (c->dn_motion == was) return RT_OK;
+    c->dt_dirty = false; /* a history tagged while the toggle was off, or before this moment, re-bases nothing */
+    if (c->motion) return RT_OK; /* the buffer is rt_temporal_motion's too: it stays, with its range */
+    { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
+    return motion_rebase_all(c);
+}
+int rt_denoise_temporal_motion_get(rt_ctx* c, int* on, int* last_call_followed)
+{
+    RT_CHECK_CTX(c);
+    if (!on && !last_call_followed) return RT_ERR_ARG;
+    if (on) *on = c->dn_motion ? 1 : 0;
+    if (last_call_followed) *last_call_followed = c->dt_followed ? 1 : 0;
     return RT_OK;
 }
 int rt_denoise_temporal_reset(rt_ctx* c)
@@ -3170,6 +3222,7 @@ int rt_temporal_motion(rt_ctx* c, int on)
     drop_look_ahead(c);
     ++c->epoch;
     if (c->motion == was) return RT_OK;
+    if (c->dn_motion) return RT_OK; /* rt_denoise_temporal_motion holds d_tv_prev too: the buffer and the range stay as they are */
     /* launches in flight may read d_tv_prev */
     { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
     return motion_rebase_all(c);

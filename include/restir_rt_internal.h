@@ -94,6 +94,28 @@ int rt_denoise_temporal_reset(rt_ctx* ctx);
 /* device time of the last rt_denoise_temporal run while rt_timing_enable was on: ms[0] guide, [1] reprojection + integration,
  * [2] variance, [3] the levels before the last, [4] the last level (fused output), [5] the whole call */
 int rt_denoise_temporal_timing(rt_ctx* ctx, float ms[6]);
+/* (r25) The temporal denoiser's history follows geometry moved by rt_scene_update (csrc/denoise_motion.h),
+ * default off: with it off every byte and every launch is what it was without the call. Independent of rt_temporal_reprojection and
+ * rt_temporal_motion (the denoiser always follows the camera); it shares the kept vertex positions of one earlier generation with
+ * rt_temporal_motion (rt_temporal_motion_range): they are copied from the current ones, with an empty range, when the first of the
+ * two toggles goes on, freed when the last goes off, and left as they are, range included, by a toggle that goes on while they
+ * exist; rt_scene_set makes them anew while either is on. rt_denoise_temporal tags its history with the geometry generation and the
+ * eye it was written under. rt_scene_update brings the kept vertices to the generation it ends when a consumer whose toggle is on
+ * wrote a history since the last update (a reservoir buffer for rt_temporal_motion, the denoiser's history for this toggle), and
+ * otherwise only grows the range: with this toggle alone, all updates between two rt_denoise_temporal calls are followed, whether or
+ * not frames were rendered in between. A call is a followed call iff the toggle is on, a history exists, the kept vertices exist,
+ * the history's generation is the one they describe, and that is not the current generation. In a followed call a participating
+ * pixel whose triangle lies in the moved range looks its history up from the point its guide hit (u, v) had on the triangle's
+ * previous vertices, with the normal it had toward the previous call's eye: reprojection and the validity test of the four taps run
+ * on that point and normal (also where the two cameras have the same bytes), with the current pixel's footprint; everything else of
+ * the call uses the current guide. Every other pixel, and every call that is not followed (a history older than the kept vertices,
+ * which happens when the two consumers alternate: frame, update, denoise, update, frame), does what rt_denoise_temporal does
+ * without the toggle: the camera only, never a wrong previous vertex. NaN or infinite previous vertices, a previous point behind or
+ * outside the previous camera: no history, h = 1. Changes neither rt_state_epoch nor the look-ahead, nor any reservoir or history
+ * buffer. Strip contexts: RT_ERR_UNSUPPORTED. Not an rt_tuning key: tuning keys never change results. */
+int rt_denoise_temporal_motion(rt_ctx* ctx, int on);
+/* the toggle, and whether the last rt_denoise_temporal call was a followed call; either pointer may be null, not both */
+int rt_denoise_temporal_motion_get(rt_ctx* ctx, int* on, int* last_call_followed);
 
 /* ---- rt_frame in stages ---- */
 /* The same frame cut into stages for strip contexts (multi-GPU): stage 0 = [clear,] raycast,
@@ -328,8 +350,8 @@ int rt_temporal_reprojection_stats(rt_ctx* ctx, uint64_t out[3]);
  * triangle's previous vertices, projected into the buffer's camera, also where that camera's bytes are the current one's), or
  * Reservoir{} where there is none, and the rejection heuristics compare that previous point, its normal and the previous eye with
  * the gathered record's origin. Every other pixel, and every merge that is no motion launch (an older history included), does
- * what rt_temporal_reprojection alone does. Not followed: moved emitters as samples, stale visibility flags, the temporal
- * denoiser, strips, changes of triangle count or order. The call changes rt_state_epoch and drops look-ahead work, touches no
+ * what rt_temporal_reprojection alone does. Not followed: moved emitters as samples, stale visibility flags, strips (the temporal
+ * denoiser: rt_denoise_temporal_motion), changes of triangle count or order. The call changes rt_state_epoch and drops look-ahead work, touches no
  * reservoir buffer; going on it copies the current vertices (updates before it are not followed), going off it frees them. Strip
  * contexts: RT_ERR_UNSUPPORTED. The [exp] stage-0 variants (rt_tuning keys 11 and 12): RT_ERR_UNSUPPORTED at a motion launch. */
 int rt_temporal_motion(rt_ctx* ctx, int on);
