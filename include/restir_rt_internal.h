@@ -149,8 +149,14 @@ size_t rt_halo_bytes(rt_ctx* ctx, int n_rows);
 int rt_halo_pack(rt_ctx* ctx, int res, int row0, int n_rows, void* device_dst);
 int rt_halo_unpack(rt_ctx* ctx, int res, int row0, int n_rows, const void* device_src);
 
-/* Sparse halos: a strip only needs the neighbour records its own pixels will gather, which is a pure
- * function of the RNG and the shaded bits. The RECEIVER marks them (rt_halo_mark: side 0 = strip
+/* Sparse halos: a strip only needs the neighbour records its own pixels will load. That set is every
+ * neighbour its own rows pick that lies inside the image and is not the pixel itself, shaded or not:
+ * the spatial kernels load a record before they know its shaded bit, which they take from the record.
+ * The shaded bits enter only through the draws (a shaded neighbour consumes a third one), so the set
+ * is a pure function of the RNG and the shaded bits; a bitmap holds exactly it, no bit more or less
+ * ("the contract of a plan"). Bitmap of n_rows rows, nw = (n_rows*W+31)/32:
+ * word 0 = count, words [1, 1+nw) = bit (row - row0)*W + x, pad bits 0, words [1+nw, 1+2nw) = exclusive
+ * prefix of the per-word popcounts; nw = 0 is the count word alone. The RECEIVER marks them (rt_halo_mark: side 0 = strip
  * below, 1 = strip above; needs the neighbour's shaded flags in its G-buffer halo rows, exchanged
  * once per frame with rt_halo_flags_*), sends the bitmap (first 1 + (n_rows*W+31)/32 words; word 0 =
  * record count) to the owner, and the owner answers each pass with the marked records only

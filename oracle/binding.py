@@ -130,6 +130,7 @@ def lib():
         L.o_temporal_resampling.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp]
         L.o_save_temporal_reservoir.argtypes = [ci, ci, vp, vp, ci, ci]
         L.o_spatial_resampling.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp]
+        L.o_spatial_resampling_reads.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
         L.o_resolve.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, ci, ci, vp]
         L.o_clear.argtypes = [vp, ci, ci, ci, ci]
         L.o_tone_mapping.argtypes = [vp, vp, ci, ci, ci, ci]
@@ -244,6 +245,20 @@ class Scene:
         r0, r1 = rows or (0, H)
         lib().o_spatial_resampling(self.h, W, H, frame, pas, _p(vis), _p(eye), _p(opt), _p(rin), _p(rout), r0, r1, _p(cnt))
         return rout
+
+    def spatial_reads(self, W, H, frame, pas, vis, eye, opt, rin, rout=None, rows=None, cnt=None):
+        """spatial_resampling through the same loop, reporting the records it touches: (rout, touched, read), the two
+        (W*H, sample_count) int32, -1 = no record. touched[p, k]: buffer index of neighbour k of pixel p once it is inside the
+        image and not p itself; read[p, k]: the same index where the loop loads rin[index] (a shaded neighbour)."""
+        rout = np.zeros(W * H, dtype=RESERVOIR) if rout is None else rout
+        eye = np.asarray(eye, dtype=np.float32)
+        r0, r1 = rows or (0, H)
+        count = int(np.asarray(opt)["spatial_resampling_sample_count"].reshape(-1)[0])
+        touched = np.full((W * H, count), -1, dtype=np.int32)
+        read = np.full((W * H, count), -1, dtype=np.int32)
+        lib().o_spatial_resampling_reads(self.h, W, H, frame, pas, _p(vis), _p(eye), _p(opt), _p(rin), _p(rout), r0, r1, _p(cnt),
+                                         _p(touched), _p(read))
+        return rout, touched, read
 
     def resolve(self, accum, W, H, vis, eye, opt, res, rows=None, cnt=None):
         eye = np.asarray(eye, dtype=np.float32)

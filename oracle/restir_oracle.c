@@ -1134,11 +1134,15 @@ ORACLE_API void o_save_temporal_reservoir(int W, int H, const OReservoir* src, O
     (void)H;
 }
 
-/* examples/10_restir_di/10_restir_di.cu:256-388 */
-ORACLE_API void o_spatial_resampling(const OScene* s, int W, int H, int frame, int pass,
-                                     const OVisibility* vis, const float* eye3, const OOptions* opt,
-                                     const OReservoir* in, OReservoir* out, int row0, int row1,
-                                     OCounters* cnt)
+/* examples/10_restir_di/10_restir_di.cu:256-388
+ * touched / read (either may be NULL): spatial_resampling_sample_count slots per pixel of the WHOLE
+ * frame, set to -1 by the caller. touched[pixel][k] = buffer index of neighbour k once it is inside
+ * the image and not the pixel itself; read[pixel][k] = the same index where the loop goes on to load
+ * in[pid] (the neighbour is shaded). Every pixel writes its own slots only. */
+static void spatial_resampling_body(const OScene* s, int W, int H, int frame, int pass,
+                                    const OVisibility* vis, const float* eye3, const OOptions* opt,
+                                    const OReservoir* in, OReservoir* out, int row0, int row1,
+                                    OCounters* cnt, int32_t* touched, int32_t* read)
 {
     const v3 eye = V3(eye3[0], eye3[1], eye3[2]);
     long rays = 0, bytes = 0, accepted = 0, merged = 0;
@@ -1174,8 +1178,10 @@ ORACLE_API void o_spatial_resampling(const OScene* s, int W, int H, int frame, i
                 const OVisibility nv = vis[pid];
                 bytes += 16;
                 ++accepted;
+                if (touched) touched[(size_t)pixel_idx * (size_t)opt->spatial_resampling_sample_count + (size_t)k] = pid;
                 if (nv.index == -1) continue;
                 if (has_emission(&s->tris[nv.index])) continue;
+                if (read) read[(size_t)pixel_idx * (size_t)opt->spatial_resampling_sample_count + (size_t)k] = pid;
                 OReservoir nr = in[pid];
                 bytes += 76;
                 float weight;
@@ -1204,6 +1210,23 @@ ORACLE_API void o_spatial_resampling(const OScene* s, int W, int H, int frame, i
         cnt->rays += rays; cnt->spatial_bytes += bytes;
         cnt->spatial_accepted += accepted; cnt->spatial_merged += merged;
     }
+}
+
+ORACLE_API void o_spatial_resampling(const OScene* s, int W, int H, int frame, int pass,
+                                     const OVisibility* vis, const float* eye3, const OOptions* opt,
+                                     const OReservoir* in, OReservoir* out, int row0, int row1,
+                                     OCounters* cnt)
+{
+    spatial_resampling_body(s, W, H, frame, pass, vis, eye3, opt, in, out, row0, row1, cnt, NULL, NULL);
+}
+
+/* The same loop, reporting which records it touches (test infrastructure of the sparse-halo tests). */
+ORACLE_API void o_spatial_resampling_reads(const OScene* s, int W, int H, int frame, int pass,
+                                           const OVisibility* vis, const float* eye3, const OOptions* opt,
+                                           const OReservoir* in, OReservoir* out, int row0, int row1,
+                                           OCounters* cnt, int32_t* touched, int32_t* read)
+{
+    spatial_resampling_body(s, W, H, frame, pass, vis, eye3, opt, in, out, row0, row1, cnt, touched, read);
 }
 
 /* examples/10_restir_di/10_restir_di.cu:390-459 */
