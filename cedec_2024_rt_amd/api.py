@@ -365,7 +365,10 @@ class MultiGpu:
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.rt_mg_destroy(self.h)
+            # rt_mg_destroy waits on its context's streams: a driver whose Renderer is already closed (the garbage collector finalises
+            # the members of a reference cycle oldest first, and the Renderer is older than its driver) is dropped, not destroyed
+            if getattr(self.r, "h", None):
+                self.L.rt_mg_destroy(self.h)
             self.h = None
 
     def __del__(self):

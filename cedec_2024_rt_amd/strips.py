@@ -402,9 +402,10 @@ def make_hip_strip(width, height, rank, world, triangles, eye, center, options, 
     return r, StripFrame(be, bounds, rank, DistTransport(dist) if world > 1 else None)
 
 
-def run_frame_local(renderers, bounds, frame, device, halo=HALO_ROWS, sparse=False, stats=None):
+def run_frame_local(renderers, bounds, frame, device, halo=HALO_ROWS, sparse=False, stats=None, clear_first=False):
     """Single-process variant for tests: several strip contexts on ONE GPU driven in lock-step
-    through the same StripFrame logic, halos moved through an in-process mailbox."""
+    through the same StripFrame logic, halos moved through an in-process mailbox. clear_first: every
+    strip clears its rows of the accumulation buffer in stage 0 (the frame after a camera move)."""
     import torch
 
     class _Sync(HipStripBackend):
@@ -455,7 +456,7 @@ def run_frame_local(renderers, bounds, frame, device, halo=HALO_ROWS, sparse=Fal
         r.sync()
         r.set_stream(torch.cuda.current_stream().cuda_stream)
     frames = [StripFrame(_Sync(r, device), bounds, k, tr, halo, sparse=sparse) for k, r in enumerate(renderers)]
-    gens = [f.frame_gen(frame) for f in frames]
+    gens = [f.frame_gen(frame, clear_first) for f in frames]
     live = list(range(len(gens)))
     while live:
         for k in list(live):

@@ -79,6 +79,34 @@ def test_library_exports_strip_driver_symbols():
         assert hasattr(L, sym), sym
 
 
+def test_a_driver_outliving_its_renderer_is_dropped_not_destroyed():
+    """rt_mg_destroy waits on its context's streams, so MultiGpu.close calls it only while the Renderer is open. The garbage collector
+    finalises the members of a reference cycle oldest first - the Renderer before its driver - which is what a failed test leaves
+    behind (the traceback holds the frame that holds both). Checked on stand-ins: no library call once the Renderer's handle is gone."""
+    api = _api()
+
+    class _Lib:
+        destroyed = []
+
+        def rt_mg_destroy(self, h):
+            self.destroyed.append(h)
+
+    class _Renderer:
+        h = 1
+
+    for renderer_open in (True, False):
+        lib, r = _Lib(), _Renderer()
+        lib.destroyed = []
+        m = api.MultiGpu.__new__(api.MultiGpu)
+        m.L, m.r, m.h = lib, r, 7
+        if not renderer_open:
+            r.h = None  # Renderer.close()
+        m.close()
+        assert lib.destroyed == ([7] if renderer_open else []) and m.h is None
+        m.close()  # a second close does nothing
+        assert lib.destroyed == ([7] if renderer_open else [])
+
+
 # ------------------------------------------------------------------------------------------ GPU
 def _eq_bits(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
