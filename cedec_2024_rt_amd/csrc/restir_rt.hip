@@ -25,6 +25,7 @@
 #include "../../include/restir_rt_internal.h"
 #include "bvh.h"
 #include "frame_roles.h"
+#include "history_provenance.h"
 #include "rt_device.h"
 
 using namespace rt;
@@ -87,7 +88,7 @@ struct rt_ctx
         int cur = 0;
         float4 *vis = nullptr, *g0 = nullptr, *g1 = nullptr;
         bool valid = false, shaded_bits_stale = true; /* a G-buffer has been traced or uploaded / d_shaded_bits predates it */
-        /* which G-buffer a reservoir buffer's shaded bits belong to (k_refresh_shaded, rec_gserial): serial counts G-buffer writes; epoch: the one the current G-buffer was traced under */
+        /* which G-buffer a reservoir buffer's shaded bits belong to (k_refresh_shaded, HistoryTag::gserial): serial counts G-buffer writes; epoch: the one the current G-buffer was traced under */
         uint64_t serial = 0, epoch = 0;
         /* r13, rt_gbuffer_reuse: the primary ray of a pixel has no jitter and no frame number in it (frame_kernels.h, shoot(xi / W, yi / H)),
          * so Visibility / g0 / g1 are a function of camera, scene and image size: of `epoch`. A staged frame of a whole-frame context whose
@@ -101,28 +102,15 @@ struct rt_ctx
     /* tags of the own-visibility flags (rt_device.h): one number per staged frame and per pipelined stage 0; the launches of
      * a staged frame carry frame.tag (Launch::tag), the per-kernel entry points carry 0 */
     uint32_t ownv_serial = 0;
-    uint64_t rec_gserial[5] = {0, 0, 0, 0, 0}; /* gbuf.serial of the G-buffer each reservoir buffer's shaded bits belong to */
-    /* r23, rt_temporal_reprojection (temporal_reproject.h): the RayGenerator each physical reservoir buffer was
-     * last written under (rec_rg_has: it carries one), kept whether the mode is on or not. A temporal merge whose history buffer
-     * carries another camera than the current one launches the REPROJECT kernels while the mode is on (history_camera). */
-    rt_raygen rec_rg[5] = {};
-    bool rec_rg_has[5] = {false, false, false, false, false};
+    /* history_provenance.h. res_tag: what each physical reservoir buffer was last written under, kept whether a mode is on or not
+     * (r23, rt_temporal_reprojection, DESIGN.md section 13: a temporal merge whose history buffer carries another camera than the
+     * current one launches the REPROJECT kernels while the mode is on, history_camera), and the G-buffer its shaded bits belong to.
+     * moved: the geometry generation, both motion toggles and the moved range (r24, rt_temporal_motion, section 14; r25,
+     * rt_denoise_temporal_motion, section 15); d_tv_prev (layout of d_tv) holds the kept vertices while moved.kept. */
+    HistoryTag res_tag[5];
     bool reproject = false;
-    /* r24, rt_temporal_motion (temporal_motion.h). geo_gen counts rt_scene_update calls since rt_scene_set; a
-     * reservoir buffer's tag also holds the generation and the eye it was written under (rec_gen, rec_eye; valid under rec_rg_has).
-     * While the toggle is on d_tv_prev (layout of d_tv) holds the vertices of generation tvp_gen: equal to d_tv outside the moved
-     * range [mv_lo, mv_hi), the cover of the spans updated since. res_dirty: a reservoir buffer was tagged since the last update, so
-     * the next update re-bases d_tv_prev to the generation it ends instead of growing the range. */
-    uint64_t geo_gen = 0, tvp_gen = 0;
-    uint64_t rec_gen[5] = {0, 0, 0, 0, 0};
-    float rec_eye[5][3] = {};
+    MovedGeometry moved;
     float4* d_tv_prev = nullptr;
-    uint32_t mv_lo = 0, mv_hi = 0;
-    bool res_dirty = false;
-    bool motion = false;
-    /* r25, rt_denoise_temporal_motion (denoise_motion.h): the second consumer of d_tv_prev. The buffer exists
-     * while either toggle is on. dt_dirty: rt_denoise_temporal tagged its history since the last update (set only while dn_motion). */
-    bool dn_motion = false, dt_dirty = false;
     unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters, then the slot of rt_occluder_hint_stats (WALK_SLOTS) */
     bool walk_on = false;
     /* r19, rt_occluder_hints: OCCLUDER_HINTS triangle indices per pixel of the local rows (occluder_hint.h), the triangles that occluded
@@ -295,9 +283,7 @@ struct rt_ctx
      * current [dt_cur] and the previous [1 - dt_cur] call, the colour history (level 1's output), the previous RayGenerator;
      * dt_valid: a history exists (rt_scene_set and rt_denoise_temporal_reset clear it). It scratches d_dn_col / d_dn_vis / d_dn_hdr. */
     float4 *d_dt_gx[2] = {nullptr, nullptr}, *d_dt_gn[2] = {nullptr, nullptr}, *d_dt_mom[2] = {nullptr, nullptr}, *d_dt_col = nullptr;
-    rt_raygen dt_rg;
-    uint64_t dt_gen = 0;                  /* the geometry generation and the eye the history was written under (next to dt_rg) */
-    float dt_eye[3] = {0.0f, 0.0f, 0.0f};
+    HistoryTag dt_tag;                    /* the camera, geometry generation and eye the history was written under */
     bool dt_followed = false;             /* the last rt_denoise_temporal call was a followed call */
     int dt_cur = 0;
     bool dt_valid = false, dt_timed = false;
@@ -370,6 +356,10 @@ static bool covers_owned_rows(const rt_ctx* c, const Launch& L) { return L.row0 
 /* the look-ahead is no longer good: the next staged frame runs its own stage 0 (ahead.gen_valid is read under ahead.valid only) */
 static void drop_look_ahead(rt_ctx* c) { c->ahead.valid = false; c->ahead.gen_valid = false; }
 
+static f3 f3_of(const float v[3]) { return F3(v[0], v[1], v[2]); }
+/* a RayGenerator record as the kernels' three vectors */
+static void unpack_camera(const rt_raygen& q, f3& origin, f3& right, f3& up) { origin = f3_of(q.origin); right = f3_of(q.right); up = f3_of(q.up); }
+
 enum { K_RAYCAST = 0, K_GENERATE = 1, K_SPATIAL = 2, K_RESOLVE = 3, K_OTHER = 4 };
 static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int pass, int kernel = K_OTHER)
 {
@@ -379,10 +369,8 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
     P.rowb0 = L.rowb0; P.rowb1 = L.rowb1;
     P.lrow0 = c->lrow0; P.lrows = c->lrows;
     P.frame = frame; P.pass = pass;
-    P.eye = F3(c->eye[0], c->eye[1], c->eye[2]);
-    P.rg_origin = F3(c->rg.origin[0], c->rg.origin[1], c->rg.origin[2]);
-    P.rg_right = F3(c->rg.right[0], c->rg.right[1], c->rg.right[2]);
-    P.rg_up = F3(c->rg.up[0], c->rg.up[1], c->rg.up[2]);
+    P.eye = f3_of(c->eye);
+    unpack_camera(c->rg, P.rg_origin, P.rg_right, P.rg_up);
     P.n_lights = c->n_lights;
     P.accumulate = c->opt.accumulate; P.ris_sample_count = c->opt.ris_sample_count;
     P.use_temporal = c->opt.use_temporal_resampling; P.use_spatial = c->opt.use_spatial_resampling;
@@ -419,29 +407,22 @@ static FrameParams make_params(const rt_ctx* c, const Launch& L, int frame, int 
 #endif
     return P;
 }
-/* the reservoir buffer `phys` is written under the current camera / holds a copy of buffer `src` */
-static void tag_camera(rt_ctx* c, int phys)
+/* the reservoir buffer `phys` is written under the current camera and generation; its shaded bits belong to G-buffer `gserial` */
+static void tag_reservoir(rt_ctx* c, int phys, uint64_t gserial)
 {
-    c->rec_rg[phys] = c->rg; c->rec_rg_has[phys] = true;
-    c->rec_gen[phys] = c->geo_gen; memcpy(c->rec_eye[phys], c->eye, sizeof(c->rec_eye[phys]));
-    c->res_dirty = true;
+    c->res_tag[phys].write(c->rg, c->moved.geo_gen, c->eye, gserial);
+    c->moved.tagged(FOLLOW_RESTIR);
 }
-static void copy_camera(rt_ctx* c, int phys, int src)
-{
-    c->rec_rg[phys] = c->rec_rg[src]; c->rec_rg_has[phys] = c->rec_rg_has[src];
-    c->rec_gen[phys] = c->rec_gen[src]; memcpy(c->rec_eye[phys], c->rec_eye[src], sizeof(c->rec_eye[phys]));
-}
+static void tag_reservoir(rt_ctx* c, int phys) { tag_reservoir(c, phys, c->gbuf.serial); }
 /* rt_temporal_reprojection: does a temporal merge that reads buffer `prev_phys` as its history gather by reprojection? Only with
  * the mode on and a buffer whose 36 bytes of RayGenerator differ from the current ones (then P carries them); an untagged buffer
  * and a camera that stands still launch what they launched before the mode existed. */
 static bool history_camera(const rt_ctx* c, int prev_phys, FrameParams& P)
 {
-    if (!c->reproject || !c->opt.use_temporal_resampling || !c->rec_rg_has[prev_phys]) return false;
-    const rt_raygen& q = c->rec_rg[prev_phys];
+    if (!c->reproject || !c->opt.use_temporal_resampling || !c->res_tag[prev_phys].has) return false;
+    const rt_raygen& q = c->res_tag[prev_phys].rg;
     if (tr_same_camera(q.origin, c->rg.origin)) return false; /* origin, right, up: 9 contiguous floats */
-    P.prev_origin = F3(q.origin[0], q.origin[1], q.origin[2]);
-    P.prev_right = F3(q.right[0], q.right[1], q.right[2]);
-    P.prev_up = F3(q.up[0], q.up[1], q.up[2]);
+    unpack_camera(q, P.prev_origin, P.prev_right, P.prev_up);
     return true;
 }
 /* rt_temporal_motion: is a temporal merge that reads buffer `prev_phys` as its history a motion launch? Both toggles on, and a buffer
@@ -450,30 +431,34 @@ static bool history_camera(const rt_ctx* c, int prev_phys, FrameParams& P)
  * current generation, is history_camera's. `vis`: the Visibility buffer of the launch's rows. */
 static bool history_motion(const rt_ctx* c, int prev_phys, FrameParams& P, const float4* vis)
 {
-    if (!c->motion || !c->reproject || !c->opt.use_temporal_resampling || !c->rec_rg_has[prev_phys] || !c->d_tv_prev) return false;
-    if (c->rec_gen[prev_phys] != c->tvp_gen || c->tvp_gen == c->geo_gen) return false;
-    const rt_raygen& q = c->rec_rg[prev_phys];
-    P.motion_same_camera = tr_same_camera(q.origin, c->rg.origin) ? 1 : 0;
-    P.prev_origin = F3(q.origin[0], q.origin[1], q.origin[2]);
-    P.prev_right = F3(q.right[0], q.right[1], q.right[2]);
-    P.prev_up = F3(q.up[0], q.up[1], q.up[2]);
-    P.eye_prev = F3(c->rec_eye[prev_phys][0], c->rec_eye[prev_phys][1], c->rec_eye[prev_phys][2]);
-    P.motion_lo = c->mv_lo; P.motion_hi = c->mv_hi;
+    const HistoryTag& t = c->res_tag[prev_phys];
+    if (!c->reproject || !c->opt.use_temporal_resampling || !c->moved.follows(FOLLOW_RESTIR, t)) return false;
+    P.motion_same_camera = tr_same_camera(t.rg.origin, c->rg.origin) ? 1 : 0;
+    unpack_camera(t.rg, P.prev_origin, P.prev_right, P.prev_up);
+    P.eye_prev = f3_of(t.eye);
+    P.motion_lo = c->moved.lo; P.motion_hi = c->moved.hi;
     P.tv_prev = c->d_tv_prev;
     P.motion_vis = vis;
     return true;
 }
-/* d_tv_prev := d_tv, all of it: the first of the two toggles (rt_temporal_motion, rt_denoise_temporal_motion) going on, the last
- * going off, or a new scene while either is on. The moved range is empty afterwards. */
-static int motion_rebase_all(rt_ctx* c)
+static bool scene_has_vertices(const rt_ctx* c) { return c->d_tv && c->n_tris > 0; }
+/* the device half of MovedGeometry's "free" and "free and copy": d_tv_prev := nothing, or d_tv, all of it (the first of the two
+ * toggles going on, the last going off, or a new scene while either is on) */
+static int kept_vertices_replace(rt_ctx* c, bool copy)
 {
     hipFree(c->d_tv_prev);
     c->d_tv_prev = nullptr;
-    c->tvp_gen = c->geo_gen; c->mv_lo = 0; c->mv_hi = 0;
-    if (!(c->motion || c->dn_motion) || !c->d_tv || c->n_tris <= 0) return RT_OK;
+    if (!copy) return RT_OK;
     RT_HIP(c, hipMalloc(&c->d_tv_prev, (size_t)c->n_tris * 48));
     RT_HIP(c, hipMemcpyAsync(c->d_tv_prev, c->d_tv, (size_t)c->n_tris * 48, hipMemcpyDeviceToDevice, c->stream));
     return RT_OK;
+}
+/* what a changed toggle asks for (KeptAction): launches in flight may read d_tv_prev, so the stream drains first */
+static int kept_vertices_toggled(rt_ctx* c, KeptAction a)
+{
+    if (a == KEPT_NOTHING) return RT_OK;
+    { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
+    return kept_vertices_replace(c, a == KEPT_DRAIN_FREE_COPY);
 }
 static_assert(sizeof(rt_raygen) == 36 && offsetof(rt_raygen, right) == 12 && offsetof(rt_raygen, up) == 24, "tr_same_camera reads 9 contiguous floats");
 static uint32_t next_ownv_tag(rt_ctx* c)
@@ -1276,8 +1261,9 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
     drop_look_ahead(c);
     c->dt_valid = false; /* rt_denoise_temporal's history belongs to the old scene */
-    for (int k = 0; k < 5; ++k) c->rec_rg_has[k] = false; /* ... and so do the reservoir buffers' camera tags: no reprojection into it */
-    c->geo_gen = 0; c->tvp_gen = 0; c->mv_lo = 0; c->mv_hi = 0; c->res_dirty = false; c->dt_dirty = false; /* rt_temporal_motion: generations count from the new scene */
+    for (HistoryTag& t : c->res_tag) t.has = false; /* ... and so do the reservoir buffers' camera tags: no reprojection into it */
+    /* generations count from the new scene; free_scene frees the old kept vertices, the new ones are copied once they exist (below) */
+    const bool keep_vertices = c->moved.scene_set(count > 0);
     /* the remembered occluders are indices of the old scene, which may have had more triangles (every stream is idle here) */
     if (c->d_hints) RT_HIP(c, hipMemset(c->d_hints, 0xff, local_pixels(c) * sizeof(int) * OCCLUDER_HINTS));
     const auto t_build0 = std::chrono::steady_clock::now();
@@ -1317,7 +1303,7 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
     }
     const int rc = build_bvh(c, triangles, n);
     if (rc != RT_OK) return rc;
-    { const int rm = motion_rebase_all(c); if (rm != RT_OK) return rm; }
+    { const int rm = kept_vertices_replace(c, keep_vertices); if (rm != RT_OK) return rm; }
     RT_HIP(c, hipStreamSynchronize(c->stream));
     c->build_ms = (float)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_build0).count() * 1e-3f;
     c->h_lights.swap(lights);
@@ -1536,21 +1522,9 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
      * first, the denoiser's for the second) written since the last update by a consumer whose toggle is on carries the
      * generation this update ends: d_tv_prev is brought to it (it differs from d_tv over the old moved range only) and a new range
      * starts. Otherwise no history of the generations in between exists, and the range grows to cover this span too. */
-    if (c->d_tv_prev)
-    {
-        if ((c->motion && c->res_dirty) || (c->dn_motion && c->dt_dirty))
-        {
-            if (c->mv_hi > c->mv_lo)
-                RT_HIP(c, hipMemcpyAsync(c->d_tv_prev + 3 * (size_t)c->mv_lo, c->d_tv + 3 * (size_t)c->mv_lo, (size_t)(c->mv_hi - c->mv_lo) * 48, hipMemcpyDeviceToDevice, st));
-            c->tvp_gen = c->geo_gen;
-            c->mv_lo = first; c->mv_hi = first + count;
-        }
-        else if (c->mv_hi > c->mv_lo) { c->mv_lo = std::min(c->mv_lo, first); c->mv_hi = std::max(c->mv_hi, first + count); }
-        else { c->mv_lo = first; c->mv_hi = first + count; }
-    }
-    ++c->geo_gen;
-    c->res_dirty = false;
-    c->dt_dirty = false;
+    const MovedUpdate mu = c->moved.update(first, count);
+    if (mu.kind == MovedUpdate::REBASE && mu.hi > mu.lo)
+        RT_HIP(c, hipMemcpyAsync(c->d_tv_prev + 3 * (size_t)mu.lo, c->d_tv + 3 * (size_t)mu.lo, (size_t)(mu.hi - mu.lo) * 48, hipMemcpyDeviceToDevice, st));
     /* per-triangle arrays of the span */
     RT_HIP(c, hipMemcpyAsync(c->d_tris + 15 * (size_t)first, triangles, (size_t)count * 60, hipMemcpyHostToDevice, st));
     const int gs = (int)((count + 255) / 256);
@@ -2060,7 +2034,7 @@ static int raycast_or_take(rt_ctx* c, Launch& L, int frame, bool may_defer, Stag
         drop_look_ahead(c);
         if (!traced) return RT_OK; /* the same set, its serial and its shaded bits; the candidates carry its serial (launch_generate) */
         gbuffer_written(c, L, GBUF_TAKEN);
-        if (got.taken) c->rec_gserial[c->frame.Y] = c->gbuf.serial; /* the candidates were made from this G-buffer set */
+        if (got.taken) c->res_tag[c->frame.Y].gserial = c->gbuf.serial; /* the candidates were made from this G-buffer set */
         if (c->ahead.timed[c->gbuf.cur]) c->ahead.timed_set = c->gbuf.cur;
         return RT_OK;
     }
@@ -2119,11 +2093,10 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
     FrameParams P = make_params(c, L, frame, 0, K_GENERATE);
     const bool sh = c->opt.use_shadowed_target_function;
     float4 *orec = c->d_rec[dst_phys], *orad = c->d_rad[dst_phys];
-    c->rec_gserial[dst_phys] = c->gbuf.serial;
     /* before the tag below: dst may not be prev, but the order costs nothing. A motion launch is a reprojecting one (mo implies rp) */
     const bool mo = fuse && history_motion(c, prev_phys, P, L.vis);
     const bool rp = mo || (fuse && history_camera(c, prev_phys, P));
-    tag_camera(c, dst_phys);
+    tag_reservoir(c, dst_phys);
     const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
     const int g = trace_grid(c, L);
     /* every form of the kernel in both light samplings: <fused, shadowed, deferred, pipelined, work-sharing, with primary rays> */
@@ -2224,7 +2197,7 @@ int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
     const int pp = c->frame.res_map[prev], pi = c->frame.res_map[inout];
     const bool mo = history_motion(c, pp, P, c->gbuf.vis);
     const bool rp = !mo && history_camera(c, pp, P);
-    tag_camera(c, pi);
+    tag_reservoir(c, pi, c->res_tag[pi].gserial); /* merged in place: its shaded bits stay those of the G-buffer it was made from */
     if (mo && c->opt.use_shadowed_target_function)
         k_temporal<true, true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
     else if (mo)
@@ -2254,8 +2227,7 @@ int rt_save_temporal_reservoir(rt_ctx* c, int src, int dst)
     const size_t off = (size_t)(c->row_begin - c->lrow0) * c->W;
     const size_t n = (size_t)(c->row_end - c->row_begin) * c->W;
     const int ps = c->frame.res_map[src], pd = c->frame.res_map[dst];
-    c->rec_gserial[pd] = c->rec_gserial[ps];
-    copy_camera(c, pd, ps);
+    c->res_tag[pd] = c->res_tag[ps];
     RT_HIP(c, hipMemcpyAsync(c->d_rec[pd] + 4 * off, c->d_rec[ps] + 4 * off, n * 64, hipMemcpyDeviceToDevice, c->stream));
     RT_HIP(c, hipMemcpyAsync(c->d_rad[pd] + off, c->d_rad[ps] + off, n * 16, hipMemcpyDeviceToDevice, c->stream));
     return RT_OK;
@@ -2341,8 +2313,7 @@ static int launch_spatial(rt_ctx* c, const Launch& L, int frame, int pass, int i
     const FrameParams P = make_params(c, L, frame, pass, K_SPATIAL);
     const bool lds_variant = use_lds_spatial(c);
     (void)lds_variant; /* the product build has no LDS-staged form */
-    c->rec_gserial[out_phys] = c->gbuf.serial;
-    tag_camera(c, out_phys); /* a pass's output lies on the current camera's pixels (the history is never a pass's output) */
+    tag_reservoir(c, out_phys); /* a pass's output lies on the current camera's pixels (the history is never a pass's output) */
     if (unbiased_applies(c))
         /* one kernel whatever keys 8 and 23 say: the A/B forms restate the reference's pass */
         k_spatial_unbiased<<<trace_grid(c, L), TRACE_BLOCK, 0, L.stream>>>(S, P, L.g0, L.g1, c->d_rec[in_phys], c->d_rad[in_phys], c->d_rec[out_phys], c->d_rad[out_phys]);
@@ -2438,7 +2409,7 @@ int rt_spatial_resampling(rt_ctx* c, int frame, int pass, int in, int out)
     if (in == out) RT_FAIL(c, RT_ERR_ARG, "in and out must differ");
     c->last_frame = frame;
     c->fuse = HaloFuse{};
-    if (c->rec_gserial[c->frame.res_map[in]] != c->gbuf.serial)
+    if (c->res_tag[c->frame.res_map[in]].gserial != c->gbuf.serial)
     {
         /* the G-buffer changed since `in` was written: its neighbour test must see the current shaded flags (frame_kernels.h) */
         /* own rows always; a strip's halo rows only where the neighbour's flags in g1 are of the current epoch (rt_halo_flags_unpack
@@ -2449,7 +2420,7 @@ int rt_spatial_resampling(rt_ctx* c, int frame, int pass, int in, int out)
         const int n = (last_row - first_row) * c->W;
         k_refresh_shaded<<<(n + 255) / 256, 256, 0, c->stream>>>(n, c->gbuf.g1 + off, c->d_rec[c->frame.res_map[in]] + 4 * off);
         RT_HIP(c, hipGetLastError());
-        c->rec_gserial[c->frame.res_map[in]] = c->gbuf.serial;
+        c->res_tag[c->frame.res_map[in]].gserial = c->gbuf.serial;
     }
     return launch_spatial(c, whole_launch(c), frame, pass, c->frame.res_map[in], c->frame.res_map[out]);
 }
@@ -2724,21 +2695,19 @@ int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_de
     const FrameParams P = make_params(c, whole_launch(c), 0, 0, K_SPATIAL);
     const DnParams D = {d.iterations, d.sigma_luminance, d.sigma_plane, d.normal_power_log2, d.variance_radius};
     DnTemporal T;
-    T.rg_origin = F3(c->dt_rg.origin[0], c->dt_rg.origin[1], c->dt_rg.origin[2]);
-    T.rg_right = F3(c->dt_rg.right[0], c->dt_rg.right[1], c->dt_rg.right[2]);
-    T.rg_up = F3(c->dt_rg.up[0], c->dt_rg.up[1], c->dt_rg.up[2]);
+    unpack_camera(c->dt_tag.rg, T.rg_origin, T.rg_right, T.rg_up);
     T.alpha_c = t.alpha_color;
     T.alpha_m = t.alpha_moments;
     T.has_history = c->dt_valid ? 1 : 0;
     const int g = launch_grid(c, whole_launch(c));
     float4 *gx = c->d_dt_gx[cur], *gn = c->d_dt_gn[cur], *mom = c->d_dt_mom[cur];
     /* rt_denoise_temporal_motion: a history of exactly the generation d_tv_prev describes, which is not the current one */
-    const bool followed = dn_motion_followed(c->dn_motion, c->dt_valid, c->d_tv_prev != nullptr, c->dt_gen, c->tvp_gen, c->geo_gen);
+    const bool followed = c->moved.follows(FOLLOW_DENOISER, c->dt_tag, c->dt_valid);
     if (followed)
     {
         DnMotion M;
-        M.eye_prev = F3(c->dt_eye[0], c->dt_eye[1], c->dt_eye[2]);
-        M.lo = c->mv_lo; M.hi = c->mv_hi;
+        M.eye_prev = f3_of(c->dt_tag.eye);
+        M.lo = c->moved.lo; M.hi = c->moved.hi;
         M.tv_prev = c->d_tv_prev;
         M.vis = c->d_dn_vis;
         k_denoise_temporal_motion<<<g, BLOCK, 0, st>>>(P, T, M, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
@@ -2768,9 +2737,8 @@ int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_de
         DN_CK(denoise_level(c, P, D, st, 1 << i, last, gx, gn, cin, cout));
     }
     if (timed) RT_HIP(c, hipEventRecord(c->dt_ev[5], st));
-    c->dt_rg = c->rg;
-    c->dt_gen = c->geo_gen; memcpy(c->dt_eye, c->eye, sizeof(c->dt_eye));
-    if (c->dn_motion) c->dt_dirty = true;
+    c->dt_tag.write(c->rg, c->moved.geo_gen, c->eye, 0);
+    c->moved.tagged(FOLLOW_DENOISER);
     c->dt_followed = followed;
     c->dt_cur = cur;
     c->dt_valid = true;
@@ -2789,19 +2757,13 @@ int rt_denoise_temporal_motion(rt_ctx* c, int on)
     if (!whole_frame(c))
         RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_denoise_temporal_motion: rt_denoise_temporal is for whole-frame contexts");
     RT_HIP(c, hipSetDevice(c->device));
-    const bool was = c->dn_motion;
-    c->dn_motion = on != 0;
-    if (c->dn_motion == was) return RT_OK;
-    c->dt_dirty = false; /* a history tagged while the toggle was off, or before this moment, re-bases nothing */
-    if (c->motion) return RT_OK; /* the buffer is rt_temporal_motion's too: it stays, with its range */
-    { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
-    return motion_rebase_all(c);
+    return kept_vertices_toggled(c, c->moved.toggle(FOLLOW_DENOISER, on != 0, scene_has_vertices(c)));
 }
 int rt_denoise_temporal_motion_get(rt_ctx* c, int* on, int* last_call_followed)
 {
     RT_CHECK_CTX(c);
     if (!on && !last_call_followed) return RT_ERR_ARG;
-    if (on) *on = c->dn_motion ? 1 : 0;
+    if (on) *on = c->moved.on[FOLLOW_DENOISER] ? 1 : 0;
     if (last_call_followed) *last_call_followed = c->dt_followed ? 1 : 0;
     return RT_OK;
 }
@@ -3056,8 +3018,7 @@ int rt_frame_stage_end(rt_ctx* c, int stage)
          * reference's save_temporal_reservoir makes (10_restir_di.cpp:314-321) */
         const size_t n = local_pixels(c);
         { const int jr = join_tail_for(c, whole_launch(c), X); if (jr != RT_OK) return jr; }
-        c->rec_gserial[X] = c->rec_gserial[Y];
-        copy_camera(c, X, Y);
+        c->res_tag[X] = c->res_tag[Y];
         RT_HIP(c, hipMemcpyAsync(c->d_rec[X], c->d_rec[Y], n * 64, hipMemcpyDeviceToDevice, c->stream));
         RT_HIP(c, hipMemcpyAsync(c->d_rad[X], c->d_rad[Y], n * 16, hipMemcpyDeviceToDevice, c->stream));
     }
@@ -3193,9 +3154,9 @@ int rt_reservoir_camera(rt_ctx* c, int res, rt_raygen* out, int* has)
     RT_CHECK_CTX(c);
     NEED_RES(c, res);
     if (!out && !has) return RT_ERR_ARG;
-    const int phys = c->frame.res_map[res];
-    if (has) *has = c->rec_rg_has[phys] ? 1 : 0;
-    if (out) { if (c->rec_rg_has[phys]) *out = c->rec_rg[phys]; else memset(out, 0, sizeof(*out)); }
+    const HistoryTag& t = c->res_tag[c->frame.res_map[res]];
+    if (has) *has = t.has ? 1 : 0;
+    if (out) { if (t.has) *out = t.rg; else memset(out, 0, sizeof(*out)); }
     return RT_OK;
 }
 int rt_temporal_reprojection_stats(rt_ctx* c, uint64_t out[3])
@@ -3217,21 +3178,15 @@ int rt_temporal_motion(rt_ctx* c, int on)
     if (!whole_frame(c))
         RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_motion: a strip context holds only its own rows of the history");
     RT_HIP(c, hipSetDevice(c->device));
-    const bool was = c->motion;
-    c->motion = on != 0;
     drop_look_ahead(c);
     ++c->epoch;
-    if (c->motion == was) return RT_OK;
-    if (c->dn_motion) return RT_OK; /* rt_denoise_temporal_motion holds d_tv_prev too: the buffer and the range stay as they are */
-    /* launches in flight may read d_tv_prev */
-    { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
-    return motion_rebase_all(c);
+    return kept_vertices_toggled(c, c->moved.toggle(FOLLOW_RESTIR, on != 0, scene_has_vertices(c)));
 }
 int rt_temporal_motion_get(rt_ctx* c, int* on)
 {
     RT_CHECK_CTX(c);
     if (!on) return RT_ERR_ARG;
-    *on = c->motion ? 1 : 0;
+    *on = c->moved.on[FOLLOW_RESTIR] ? 1 : 0;
     return RT_OK;
 }
 int rt_reservoir_scene(rt_ctx* c, int res, uint64_t* generation, float eye[3], int* has)
@@ -3239,20 +3194,19 @@ int rt_reservoir_scene(rt_ctx* c, int res, uint64_t* generation, float eye[3], i
     RT_CHECK_CTX(c);
     NEED_RES(c, res);
     if (!generation && !eye && !has) return RT_ERR_ARG;
-    const int phys = c->frame.res_map[res];
-    const bool h = c->rec_rg_has[phys];
-    if (has) *has = h ? 1 : 0;
-    if (generation) *generation = h ? c->rec_gen[phys] : 0;
-    if (eye) for (int k = 0; k < 3; ++k) eye[k] = h ? c->rec_eye[phys][k] : 0.0f;
+    const HistoryTag& t = c->res_tag[c->frame.res_map[res]];
+    if (has) *has = t.has ? 1 : 0;
+    if (generation) *generation = t.has ? t.gen : 0;
+    if (eye) for (int k = 0; k < 3; ++k) eye[k] = t.has ? t.eye[k] : 0.0f;
     return RT_OK;
 }
 int rt_temporal_motion_range(rt_ctx* c, uint32_t* lo, uint32_t* hi, uint64_t* generation)
 {
     RT_CHECK_CTX(c);
     if (!lo && !hi && !generation) return RT_ERR_ARG;
-    if (lo) *lo = c->mv_lo;
-    if (hi) *hi = c->mv_hi;
-    if (generation) *generation = c->tvp_gen;
+    if (lo) *lo = c->moved.lo;
+    if (hi) *hi = c->moved.hi;
+    if (generation) *generation = c->moved.kept_gen;
     return RT_OK;
 }
 int rt_temporal_motion_stats(rt_ctx* c, uint64_t out[3])
@@ -3397,8 +3351,7 @@ int rt_upload(rt_ctx* c, int buf, const void* src, size_t bytes)
             if (!c->gbuf.valid) RT_FAIL(c, RT_ERR_STATE, "upload RT_BUF_VISIBILITY (or rt_raycast) before reservoirs");
             ++c->res_epoch;
             const int phys = c->frame.res_map[buf - RT_BUF_RES_0];
-            c->rec_gserial[phys] = c->gbuf.serial;
-            tag_camera(c, phys); /* its shaded bits come from the current G-buffer: the current camera's pixels */
+            tag_reservoir(c, phys); /* its shaded bits come from the current G-buffer: the current camera's pixels */
             /* the record keeps M in 30 bits: refuse what it cannot hold rather than truncate */
             for (size_t i = 0; i < n; ++i)
             {
@@ -3870,7 +3823,10 @@ int rt_walk_stats_enable(rt_ctx* c, int on)
     if (on)
     {
         if (!c->d_walk) RT_HIP(c, hipMalloc(&c->d_walk, 4 * WALK_SLOTS * 8));
-        RT_HIP(c, hipMemset(c->d_walk, 0, 4 * WALK_SLOTS * 8));
+        /* on the context's stream, and complete before the call returns: a memset of device memory on the null stream may still be
+         * running when the next launch on the (non-blocking) stream counts into it */
+        RT_HIP(c, hipMemsetAsync(c->d_walk, 0, 4 * WALK_SLOTS * 8, c->stream));
+        RT_HIP(c, hipStreamSynchronize(c->stream));
     }
     c->walk_on = on != 0;
     /* a pipelined stage 0 enqueued before the switch carries the other setting: the next frame runs its own */
