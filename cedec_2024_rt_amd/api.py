@@ -178,6 +178,7 @@ def load_library(exp=False, path=None):
     L.rt_halo_fuse_set.argtypes = [vp, vp]
     L.rt_side_stream.argtypes = [vp, ci, vp]
     L.rt_copy_parts.argtypes = [vp, ci, vp, vp, vp]
+    L.rt_wire_delay.argtypes = [vp, ci, ci, C.c_ulonglong]
     L.rt_build_id.argtypes = []
     L.rt_build_id.restype = C.c_char_p
     L.rt_row_shaded.argtypes = [vp, vp]
@@ -648,6 +649,27 @@ class Renderer:
 
     def set_stream_own(self):
         self._ck(self.L.rt_set_stream_own(self.h))
+
+    def get_stream(self):
+        """the HIP stream the context enqueues on right now, as an int handle (0 = HIP's null stream)"""
+        s = C.c_void_p()
+        self._ck(self.L.rt_get_stream(self.h, C.byref(s)))
+        return int(s.value or 0)
+
+    def side_stream(self, which=0):
+        """rt_side_stream: 0 = the context's tail stream, as an int handle; the look-ahead stream is not handed out"""
+        s = C.c_void_p()
+        self._ck(self.L.rt_side_stream(self.h, int(which), C.byref(s)))
+        return int(s.value or 0)
+
+    def lane(self, on):
+        """rt_lane: between lane(True) and lane(False) every enqueue of the context goes to its second stream"""
+        self._ck(self.L.rt_lane(self.h, int(bool(on))))
+
+    def wire_delay(self, phase, slot, ns):
+        """rt_wire_delay on the current stream: phase 0 stamps the GPU clock into slot 0..7, phase 1 holds the stream until `ns`
+        (at most 5 ms) after that stamp; a slot belongs to one stream"""
+        self._ck(self.L.rt_wire_delay(self.h, int(phase), int(slot), int(ns)))
 
     def frame_stage_fork(self):
         self._ck(self.L.rt_frame_stage_fork(self.h))
