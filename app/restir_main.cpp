@@ -12,6 +12,7 @@
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
  *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased] [--reproject]
  *              [--move-tris first count dx dy dz] [--follow-motion] [--denoise-follow-motion]
+ *              [--denoise-antilag [radius lo hi floor]]
  *              [--light-sampling uniform|power]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
@@ -41,6 +42,9 @@
  * --denoise-follow-motion (with --denoise N --denoise-temporal): rt_denoise_temporal_motion, the denoiser's history of a pixel on a
  *     moved triangle is looked up from where its surface point was; meant for --move-tris. Each frame's
  *     denoise line then says whether the call followed.
+ * --denoise-antilag [radius lo hi floor] (with --denoise N --denoise-temporal): rt_denoise_temporal_antilag, the temporal denoiser
+ *     raises its blend factors where the current frame and the reprojected history disagree over a window;
+ *     without the four numbers: the library's defaults. Each frame's denoise line then says whether the call was an adapted call.
  * --example 6: the same ambient occlusion ON THE GPU through rt_path_trace (examples/06_ao_hiprt/06_ao_hiprt.cu:35-91, the
  * same image as 04_ao's kernel). Defaults follow 06_ao_hiprt.cpp:79-80: 1920x1080, camera (8,8,8) -> (0,0,0), fovy pi/4.
  * --frames K times K launches after one warm-up (host clock around rt_sync) and prints ms per launch and Mray/s in the
@@ -64,6 +68,7 @@
  * triangle fans, per-face usemtl -> Kd/Ke).
  */
 #include <atomic>
+#include <cctype>
 #include <cmath>
 #include <chrono>
 #include <cstdio>
@@ -453,6 +458,8 @@ int main(int argc, char** argv)
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
     bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false, follow_motion = false, move_lights_given = false, denoise_follow = false;
+    bool denoise_antilag = false, antilag_given = false;
+    rt_denoise_antilag_params antilag = {4, 0.2f, 0.8f, 0.05f};
     int light_mode = RT_LIGHTS_UNIFORM;
     float orbit_d[2] = {0.0f, 0.0f};
     LightMove mv;
@@ -502,6 +509,21 @@ int main(int argc, char** argv)
         else if (a == "--reproject") reproject = true;
         else if (a == "--follow-motion") follow_motion = true;
         else if (a == "--denoise-follow-motion") denoise_follow = true;
+        else if (a == "--denoise-antilag")
+        {
+            denoise_antilag = true;
+            /* the four numbers are optional: taken if the next argument starts a number */
+            if (i + 1 < argc && (isdigit((unsigned char)argv[i + 1][0]) || argv[i + 1][0] == '.'))
+            {
+                if (i + 4 >= argc) { fprintf(stderr, "--denoise-antilag takes no numbers or four: radius lo hi floor\n"); return 2; }
+                antilag.radius = atoi(argv[i + 1]);
+                antilag.gradient_lo = (float)atof(argv[i + 2]);
+                antilag.gradient_hi = (float)atof(argv[i + 3]);
+                antilag.floor = (float)atof(argv[i + 4]);
+                antilag_given = true;
+                i += 4;
+            }
+        }
         else if (a == "--light-sampling")
         {
             const std::string m = i + 1 < argc ? argv[++i] : "";
@@ -525,6 +547,7 @@ int main(int argc, char** argv)
     if (unbiased && (ranks > 1 || example != 10)) { fprintf(stderr, "--unbiased applies to one GPU and --example 10\n"); return 2; }
     if (reproject && (ranks > 1 || example != 10)) { fprintf(stderr, "--reproject applies to one GPU and --example 10\n"); return 2; }
     if (denoise_follow && !denoise_temporal) { fprintf(stderr, "--denoise-follow-motion needs --denoise N --denoise-temporal\n"); return 2; }
+    if (denoise_antilag && !denoise_temporal) { fprintf(stderr, "--denoise-antilag needs --denoise N --denoise-temporal\n"); return 2; }
     if (follow_motion && !reproject) { fprintf(stderr, "--follow-motion needs --reproject\n"); return 2; }
     if (mv.all && move_lights_given) { fprintf(stderr, "--move-tris and --move-lights exclude each other\n"); return 2; }
     if (light_mode != RT_LIGHTS_UNIFORM && example != 10) { fprintf(stderr, "--light-sampling applies to --example 10\n"); return 2; }
@@ -643,6 +666,7 @@ int main(int argc, char** argv)
     if (reproject) CK(rt_temporal_reprojection(ctx, 1));
     if (follow_motion) CK(rt_temporal_motion(ctx, 1));
     if (denoise_follow) CK(rt_denoise_temporal_motion(ctx, 1));
+    if (denoise_antilag) CK(rt_denoise_temporal_antilag(ctx, 1, antilag_given ? &antilag : nullptr));
     CK(rt_light_sampling(ctx, light_mode));
     CK(rt_timing_enable(ctx, 1));
     CK(rt_clear(ctx)); /* :222-226 */
@@ -714,6 +738,15 @@ int main(int argc, char** argv)
                 int followed = 0;
                 CK(rt_denoise_temporal_motion_get(ctx, nullptr, &followed));
                 printf(followed ? " followed moved geometry" : " camera only");
+            }
+            if (denoise_antilag)
+            {
+                int adapted = 0;
+                float al_ms = 0.0f;
+                CK(rt_denoise_temporal_antilag_get(ctx, nullptr, nullptr, &adapted));
+                if (adapted) CK(rt_denoise_temporal_antilag_timing(ctx, &al_ms));
+                if (adapted) printf(" anti-lag adapted (%.3f ms)", al_ms);
+                else printf(" anti-lag not adapted (no history)");
             }
             printf("\n");
         }

@@ -49,6 +49,7 @@ INTERNAL_EXPORTS = [
     "rt_temporal_reprojection", "rt_temporal_reprojection_get", "rt_reservoir_camera", "rt_temporal_reprojection_stats",
     "rt_temporal_motion", "rt_temporal_motion_get", "rt_reservoir_scene", "rt_temporal_motion_range", "rt_temporal_motion_stats",
     "rt_denoise_temporal_motion", "rt_denoise_temporal_motion_get",
+    "rt_denoise_temporal_antilag", "rt_denoise_temporal_antilag_get", "rt_denoise_temporal_antilag_timing",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -61,6 +62,10 @@ RT_MG_DENSE, RT_MG_ONE_LANE, RT_MG_SEPARATE_PACK = 1, 2, 4
 
 class RtError(RuntimeError):
     pass
+
+
+class _AntilagParams(C.Structure):  # rt_denoise_antilag_params
+    _fields_ = [("radius", C.c_int32), ("gradient_lo", C.c_float), ("gradient_hi", C.c_float), ("floor", C.c_float)]
 
 
 EXP_LIB_PATH = os.path.join(HERE, "librestir_rt_exp.so")
@@ -217,6 +222,10 @@ def load_library(exp=False, path=None):
     if hasattr(L, "rt_denoise_temporal_motion"):  # r25; likewise
         L.rt_denoise_temporal_motion.argtypes = [vp, ci]
         L.rt_denoise_temporal_motion_get.argtypes = [vp, vp, vp]
+    if hasattr(L, "rt_denoise_temporal_antilag"):  # r30; likewise
+        L.rt_denoise_temporal_antilag.argtypes = [vp, ci, vp]
+        L.rt_denoise_temporal_antilag_get.argtypes = [vp, vp, vp, vp]
+        L.rt_denoise_temporal_antilag_timing.argtypes = [vp, vp]
     L.rt_visibility_rays_walked.argtypes = [vp, vp]
     L.rt_state_epoch.argtypes = [vp, vp]
     L.rt_get_stream.argtypes = [vp, vp]
@@ -927,6 +936,36 @@ class Renderer:
         v, f = C.c_int(), C.c_int()
         self._ck(self.L.rt_denoise_temporal_motion_get(self.h, C.byref(v), C.byref(f)))
         return dict(on=bool(v.value), followed=bool(f.value))
+
+    def denoise_temporal_antilag(self, on=None, **params):
+        """rt_denoise_temporal_antilag: denoise_temporal raises its blend factors where the current frame and the reprojected history
+        disagree over a window. Default off. params: radius (1..4), gradient_lo, gradient_hi, floor; the ones not
+        given keep their values, on=None keeps the toggle, and no argument at all queries. Returns dict(on, adapted, radius,
+        gradient_lo, gradient_hi, floor): the state, and whether the last denoise_temporal call was an adapted call."""
+        if not hasattr(self.L, "rt_denoise_temporal_antilag"):  # an older build through RT_LIB_PATH: the toggle is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_denoise_temporal_antilag")
+        unknown = set(params) - {"radius", "gradient_lo", "gradient_hi", "floor"}
+        if unknown:
+            raise RtError(f"denoise_temporal_antilag: unknown parameters {sorted(unknown)}")
+
+        def get():
+            v, f, a = C.c_int(), C.c_int(), _AntilagParams()
+            self._ck(self.L.rt_denoise_temporal_antilag_get(self.h, C.byref(v), C.byref(a), C.byref(f)))
+            return dict(on=bool(v.value), adapted=bool(f.value), radius=int(a.radius), gradient_lo=float(a.gradient_lo),
+                        gradient_hi=float(a.gradient_hi), floor=float(a.floor))
+
+        if on is not None or params:
+            cur = get()
+            cur.update(params)
+            a = _AntilagParams(int(cur["radius"]), float(cur["gradient_lo"]), float(cur["gradient_hi"]), float(cur["floor"]))
+            self._ck(self.L.rt_denoise_temporal_antilag(self.h, int(bool(cur["on"] if on is None else on)), C.byref(a)))
+        return get()
+
+    def denoise_temporal_antilag_timing(self):
+        """device ms of k_denoise_antilag in the last denoise_temporal call (a timed adapted call)"""
+        ms = C.c_float()
+        self._ck(self.L.rt_denoise_temporal_antilag_timing(self.h, C.byref(ms)))
+        return float(ms.value)
 
     def reservoir_scene(self, res):
         """rt_reservoir_scene: (geometry generation, eye as 3 float32) reservoir buffer RT_RES_* was last written under, or None while it

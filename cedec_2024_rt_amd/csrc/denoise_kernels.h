@@ -19,10 +19,17 @@
  *   k_denoise_var_hist  col' = {c, var}: the temporal variance where h >= 4, k_denoise_var's window elsewhere
  *   k_denoise_temporal_motion  k_denoise_temporal for a followed call of rt_denoise_temporal_motion (denoise_motion.h): pixels on a
  *                       triangle rt_scene_update moved look their history up from where their surface point was
+ *
+ * An adapted call of rt_denoise_temporal_antilag (denoise_antilag.h) puts two kernels in place of k_denoise_temporal{,_motion}:
+ *   k_denoise_antilag_gather<MOTION>  dn_temporal_pixel up to the blend: {e, l_h} -> d_dn_col[0] (free until k_denoise_var_hist),
+ *                       {c_prev, 0} -> d_dn_col[1], {mu1_prev, mu2_prev, h_prev, 0} -> the current moments
+ *   k_denoise_antilag   32 x 8 pixels per workgroup; {n, l_h} and l_e of the tile and a halo of `radius` in LDS; lambda', the blend,
+ *                       colour and moments in place at the pixel itself
  */
 #pragma once
 #include "denoise_math.h"
 #include "denoise_motion.h"
+#include "denoise_antilag.h"
 
 /* rt_tuning key 28 default: the residue lattice in LDS (1), 1.13 against 1.19 ms of filter at 5 iterations, 1080p */
 #ifndef DN_LAYOUT_DEFAULT
@@ -149,12 +156,14 @@ struct DnMotion
 };
 /* one pass per pixel: 2 guide records, the accumulation, the albedo, and per valid tap 4 records of the previous frame.
  * MOTION (a followed call): + the pixel's vis record, and for the lanes on a triangle of the moved range the 48 bytes of its previous
- * vertices; reprojection and tap test then run on the previous surface point and normal. MOTION = false is the r10 kernel. */
-template <bool MOTION>
+ * vertices; reprojection and tap test then run on the previous surface point and normal. MOTION = false is the r10 kernel.
+ * GATHER (an adapted call of rt_denoise_temporal_antilag): everything up to the blend; k_denoise_antilag finishes the pixel. */
+template <bool MOTION, bool GATHER = false>
 RT_DEV void dn_temporal_pixel(const FrameParams& P, const DnTemporal& T, const DnMotion* M, const float4* __restrict__ trimat,
                               const float4* __restrict__ accum, const float4* __restrict__ gx, const float4* __restrict__ gn,
                               const float4* __restrict__ pgx, const float4* __restrict__ pgn, const float4* __restrict__ hcol,
-                              const float4* __restrict__ hmom, float4* __restrict__ col, float4* __restrict__ mom)
+                              const float4* __restrict__ hmom, float4* __restrict__ col, float4* __restrict__ mom,
+                              float4* __restrict__ ecol = nullptr)
 {
     int x, row;
     if (!tile_pixel(P, x, row)) return;
@@ -164,6 +173,7 @@ RT_DEV void dn_temporal_pixel(const FrameParams& P, const DnTemporal& T, const D
     const float4 A = accum[li];
     if (dn_kind(word) != DN_KIND_SURFACE || A.w == 0.0f)
     {
+        if (GATHER) ecol[li] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         col[li] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         mom[li] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
@@ -200,6 +210,22 @@ RT_DEV void dn_temporal_pixel(const FrameParams& P, const DnTemporal& T, const D
             dn_history_add(s, w[k], hcol[qi], mq);
         }
     }
+    if (GATHER)
+    {
+        /* the quotients of dn_temporal_integrate, kept for dn_antilag_integrate; l_h = -1: no history */
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float lh = -1.0f;
+        if (s.sw >= DN_TEMPORAL_WEIGHT_MIN)
+        {
+            c = make_float4(s.r / s.sw, s.g / s.sw, s.b / s.sw, 0.0f);
+            m = make_float4(s.m1 / s.sw, s.m2 / s.sw, s.h, 0.0f);
+            lh = dn_luminance(c);
+        }
+        ecol[li] = make_float4(e.x, e.y, e.z, lh);
+        col[li] = c;
+        mom[li] = m;
+        return;
+    }
     float4 c, m;
     dn_temporal_integrate(s, e, T.alpha_c, T.alpha_m, c, m);
     col[li] = c;
@@ -220,6 +246,79 @@ __global__ __launch_bounds__(BLOCK) void k_denoise_temporal_motion(FrameParams P
                                                                    const float4* __restrict__ hmom, float4* __restrict__ col, float4* __restrict__ mom)
 {
     dn_temporal_pixel<true>(P, T, &M, trimat, accum, gx, gn, pgx, pgn, hcol, hmom, col, mom);
+}
+/* ---- rt_denoise_temporal_antilag: the two kernels of an adapted call ---- */
+template <bool MOTION>
+__global__ __launch_bounds__(BLOCK) void k_denoise_antilag_gather(FrameParams P, DnTemporal T, DnMotion M, const float4* __restrict__ trimat,
+                                                                  const float4* __restrict__ accum, const float4* __restrict__ gx,
+                                                                  const float4* __restrict__ gn, const float4* __restrict__ pgx,
+                                                                  const float4* __restrict__ pgn, const float4* __restrict__ hcol,
+                                                                  const float4* __restrict__ hmom, float4* __restrict__ ecol,
+                                                                  float4* __restrict__ col, float4* __restrict__ mom)
+{
+    dn_temporal_pixel<MOTION, true>(P, T, &M, trimat, accum, gx, gn, pgx, pgn, hcol, hmom, col, mom, ecol);
+}
+/* Workgroup b = tile (b % ntx, b / ntx) of DN_AL_TILE_W x DN_AL_TILE_H pixels, one per lane. LDS: per entry of the tile and its halo
+ * of `radius` {n, l_h} (16 B) and l_e (4 B), l_h = -1 outside the image: (32 + 8) x (8 + 8) entries at radius 4 = 12 800 B. ecol =
+ * {e, l_h}, col = {c_prev, 0} / {0, 0, 0, -1} and mom = {mu1_prev, mu2_prev, h_prev, 0} as k_denoise_antilag_gather left them; col
+ * and mom are rewritten at the lane's own pixel only, which no other lane reads. The tile: 32 x 8 measured 0.071 ms at 1920 x 1080
+ * and radius 4 against 0.077 for 16 x 16 and 0.074 for 32 x 16; two or four pixels of a column per lane, which read each LDS entry
+ * once for all of them, measured slower (0.082 to 0.128: docs/MEASUREMENT_LOG_r30.md). */
+constexpr int DN_AL_TILE_W = 32, DN_AL_TILE_H = 8, DN_AL_THREADS = DN_AL_TILE_W * DN_AL_TILE_H;
+constexpr int DN_AL_ENTRIES = (DN_AL_TILE_W + 2 * DN_ANTILAG_RADIUS_MAX) * (DN_AL_TILE_H + 2 * DN_ANTILAG_RADIUS_MAX);
+__global__ __launch_bounds__(DN_AL_THREADS) void k_denoise_antilag(int W, int H, int ntx, DnAntilag L, float alpha_c, float alpha_m,
+                                                                   const float4* __restrict__ gn, const float4* __restrict__ ecol,
+                                                                   float4* __restrict__ col, float4* __restrict__ mom)
+{
+    __shared__ float4 s_n[DN_AL_ENTRIES];
+    __shared__ float s_le[DN_AL_ENTRIES];
+    const int R = L.radius, A = DN_AL_TILE_W + 2 * R, N = A * (DN_AL_TILE_H + 2 * R);
+    const int by = (int)blockIdx.x / ntx, bx = (int)blockIdx.x - by * ntx;
+    const int x0 = bx * DN_AL_TILE_W - R, r0 = by * DN_AL_TILE_H - R; /* pixel of apron entry (0, 0) */
+    for (int k = (int)threadIdx.x; k < N; k += DN_AL_THREADS)
+    {
+        const int jj = k / A, ii = k - jj * A;
+        const int qx = x0 + ii, qr = r0 + jj;
+        float4 nq = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        float le = 0.0f;
+        if (qx >= 0 && qx < W && qr >= 0 && qr < H)
+        {
+            const size_t qi = (size_t)qx + (size_t)qr * W;
+            const float4 eq = ecol[qi], g = gn[qi];
+            nq = make_float4(g.x, g.y, g.z, eq.w);
+            le = dn_luminance(eq);
+        }
+        s_n[k] = nq;
+        s_le[k] = le;
+    }
+    __syncthreads();
+    const int ti = (int)threadIdx.x % DN_AL_TILE_W, tj = (int)threadIdx.x / DN_AL_TILE_W;
+    const int x = x0 + R + ti, row = r0 + R + tj;
+    if (x >= W || row >= H) return;
+    const int c0 = (tj + R) * A + (ti + R);
+    const float4 np4 = s_n[c0];
+    const f3 np = F3(np4.x, np4.y, np4.z);
+    const bool window = dn_antilag_has_history(np4.w); /* l_h = -1 also where the pixel does not participate */
+    DnGradient g = dn_gradient_init();
+    if (window)
+        for (int dy = -R; dy <= R; ++dy)
+            for (int dx = -R; dx <= R; ++dx)
+            {
+                const int k = c0 + dy * A + dx;
+                const float4 nq = s_n[k];
+                const float le = s_le[k]; /* read with nq, not behind the test: both LDS reads are in flight together */
+                if (dn_antilag_member(np, F3(nq.x, nq.y, nq.z), nq.w)) dn_gradient_add(g, le, nq.w);
+            }
+    const size_t li = (size_t)x + (size_t)row * W;
+    const float4 cprev = col[li];
+    if (cprev.w < 0.0f) return; /* does not participate: {0, 0, 0, -1} and zero moments are in place */
+    const float4 ep = ecol[li];
+    const f3 e = F3(ep.x, ep.y, ep.z);
+    float4 c, m;
+    if (!window) dn_antilag_first(e, c, m);
+    else dn_antilag_integrate(cprev, mom[li], e, alpha_c, alpha_m, dn_antilag_response(dn_gradient_lambda(g, L.floor), L.lo, L.hi), c, m);
+    col[li] = c;
+    mom[li] = m;
 }
 __global__ __launch_bounds__(BLOCK) void k_denoise_var_hist(FrameParams P, DnParams D, const float4* __restrict__ gx, const float4* __restrict__ gn,
                                                             const float4* __restrict__ mom, const float4* __restrict__ cin, float4* __restrict__ cout)

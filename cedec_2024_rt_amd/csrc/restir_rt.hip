@@ -288,6 +288,11 @@ struct rt_ctx
     int dt_cur = 0;
     bool dt_valid = false, dt_timed = false;
     hipEvent_t dt_ev[6] = {};
+    /* rt_denoise_temporal_antilag (denoise_antilag.h): the toggle and its parameters; al_adapted: the last rt_denoise_temporal call was
+     * an adapted call; al_ev: the start of k_denoise_antilag in a timed adapted call (its end is dt_ev[2]) */
+    bool al_on = false, al_adapted = false, al_timed = false;
+    rt_denoise_antilag_params al_params = {4, 0.2f, 0.8f, 0.05f};
+    hipEvent_t al_ev = nullptr;
     void* d_stage = nullptr;
     size_t stage_bytes = 0;
 
@@ -616,6 +621,7 @@ int rt_destroy(rt_ctx* c)
     for (int k = 0; k < 2; ++k) { hipFree(c->d_dt_gx[k]); hipFree(c->d_dt_gn[k]); hipFree(c->d_dt_mom[k]); }
     hipFree(c->d_dt_col);
     for (auto& e : c->dt_ev) if (e) hipEventDestroy(e);
+    if (c->al_ev) hipEventDestroy(c->al_ev);
     hipFree(c->d_counter); hipFree(c->d_stage); hipFree(c->d_paths[0]); hipFree(c->d_paths[1]); hipFree(c->d_pt_counters);
     if (c->ev_created) for (auto& e : c->ev) hipEventDestroy(e);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -2703,13 +2709,37 @@ int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_de
     float4 *gx = c->d_dt_gx[cur], *gn = c->d_dt_gn[cur], *mom = c->d_dt_mom[cur];
     /* rt_denoise_temporal_motion: a history of exactly the generation d_tv_prev describes, which is not the current one */
     const bool followed = c->moved.follows(FOLLOW_DENOISER, c->dt_tag, c->dt_valid);
+    /* rt_denoise_temporal_antilag: an adapted call gathers first and blends in k_denoise_antilag; any other call is the one it was */
+    const bool adapted = c->al_on && c->dt_valid;
+    DnMotion M = {};
     if (followed)
     {
-        DnMotion M;
         M.eye_prev = f3_of(c->dt_tag.eye);
         M.lo = c->moved.lo; M.hi = c->moved.hi;
         M.tv_prev = c->d_tv_prev;
         M.vis = c->d_dn_vis;
+    }
+    if (adapted)
+    {
+        const rt_denoise_antilag_params& a = c->al_params;
+        const DnAntilag L = {a.radius, a.gradient_lo, a.gradient_hi, a.floor};
+        if (followed)
+            k_denoise_antilag_gather<true><<<g, BLOCK, 0, st>>>(P, T, M, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
+                                                                c->d_dt_mom[prev], c->d_dn_col[0], c->d_dn_col[1], mom);
+        else
+            k_denoise_antilag_gather<false><<<g, BLOCK, 0, st>>>(P, T, M, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
+                                                                 c->d_dt_mom[prev], c->d_dn_col[0], c->d_dn_col[1], mom);
+        RT_HIP(c, hipGetLastError());
+        if (timed)
+        {
+            if (!c->al_ev) RT_HIP(c, hipEventCreate(&c->al_ev));
+            RT_HIP(c, hipEventRecord(c->al_ev, st));
+        }
+        const int ntx = (c->W + DN_AL_TILE_W - 1) / DN_AL_TILE_W, nty = (c->H + DN_AL_TILE_H - 1) / DN_AL_TILE_H;
+        k_denoise_antilag<<<ntx * nty, DN_AL_THREADS, 0, st>>>(c->W, c->H, ntx, L, T.alpha_c, T.alpha_m, gn, c->d_dn_col[0], c->d_dn_col[1], mom);
+    }
+    else if (followed)
+    {
         k_denoise_temporal_motion<<<g, BLOCK, 0, st>>>(P, T, M, c->d_trimat, c->d_accum, gx, gn, c->d_dt_gx[prev], c->d_dt_gn[prev], c->d_dt_col,
                                                        c->d_dt_mom[prev], c->d_dn_col[1], mom);
     }
@@ -2740,6 +2770,8 @@ int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* spatial, const rt_de
     c->dt_tag.write(c->rg, c->moved.geo_gen, c->eye, 0);
     c->moved.tagged(FOLLOW_DENOISER);
     c->dt_followed = followed;
+    c->al_adapted = adapted;
+    c->al_timed = timed && adapted;
     c->dt_cur = cur;
     c->dt_valid = true;
     c->dt_timed = timed;
@@ -2765,6 +2797,42 @@ int rt_denoise_temporal_motion_get(rt_ctx* c, int* on, int* last_call_followed)
     if (!on && !last_call_followed) return RT_ERR_ARG;
     if (on) *on = c->moved.on[FOLLOW_DENOISER] ? 1 : 0;
     if (last_call_followed) *last_call_followed = c->dt_followed ? 1 : 0;
+    return RT_OK;
+}
+/* r30. rt_denoise_temporal raises its blend factors where the current frame and the reprojected history disagree over a window
+ * (denoise_antilag.h). Changes results, so not an rt_tuning key. Host state only: it reads the history
+ * rt_denoise_temporal keeps anyway, so it touches neither rt_state_epoch nor the look-ahead nor any buffer, and needs no reset. */
+int rt_denoise_temporal_antilag(rt_ctx* c, int on, const rt_denoise_antilag_params* params)
+{
+    RT_CHECK_CTX(c);
+    if (!whole_frame(c))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_denoise_temporal_antilag: rt_denoise_temporal is for whole-frame contexts");
+    rt_denoise_antilag_params a = {4, 0.2f, 0.8f, 0.05f};
+    if (params) a = *params;
+    if (a.radius < 1 || a.radius > DN_ANTILAG_RADIUS_MAX) RT_FAIL(c, RT_ERR_ARG, "radius %d outside 1..%d", a.radius, DN_ANTILAG_RADIUS_MAX);
+    if (!(a.gradient_lo >= 0.0f) || !(a.gradient_hi < INFINITY) || !(a.gradient_lo < a.gradient_hi))
+        RT_FAIL(c, RT_ERR_ARG, "gradient_lo and gradient_hi must be finite with 0 <= lo < hi");
+    if (!(a.floor >= 0.0f) || !(a.floor < INFINITY)) RT_FAIL(c, RT_ERR_ARG, "floor must be finite and >= 0");
+    c->al_on = on != 0;
+    c->al_params = a;
+    return RT_OK;
+}
+int rt_denoise_temporal_antilag_get(rt_ctx* c, int* on, rt_denoise_antilag_params* params, int* last_call_adapted)
+{
+    RT_CHECK_CTX(c);
+    if (!on && !params && !last_call_adapted) return RT_ERR_ARG;
+    if (on) *on = c->al_on ? 1 : 0;
+    if (params) *params = c->al_params;
+    if (last_call_adapted) *last_call_adapted = c->al_adapted ? 1 : 0;
+    return RT_OK;
+}
+int rt_denoise_temporal_antilag_timing(rt_ctx* c, float* ms)
+{
+    RT_CHECK_CTX(c);
+    if (!ms) return RT_ERR_ARG;
+    if (!c->dt_timed || !c->al_timed) RT_FAIL(c, RT_ERR_STATE, "no timed adapted rt_denoise_temporal (rt_timing_enable + rt_denoise_temporal_antilag + a call with a history first)");
+    RT_HIP(c, hipEventSynchronize(c->dt_ev[2]));
+    RT_HIP(c, hipEventElapsedTime(ms, c->al_ev, c->dt_ev[2]));
     return RT_OK;
 }
 int rt_denoise_temporal_reset(rt_ctx* c)

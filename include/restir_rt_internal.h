@@ -79,7 +79,8 @@ typedef struct
 } rt_denoise_temporal_params;
 enum
 {
-    RT_BUF_DENOISE_HISTORY = 8 /* float4[W*H] {mu1, mu2, history length, 0} of the last rt_denoise_temporal call; download only */
+    RT_BUF_DENOISE_HISTORY = 8 /* float4[W*H] {mu1, mu2, history length, lambda'} of the last rt_denoise_temporal call; download only.
+                                  lambda' is rt_denoise_temporal_antilag's response: 0 unless that toggle is on */
 };
 /* rt_denoise's contract, for one frame of a sequence: the accumulation buffer as it stands is the new frame (call it once per
  * frame). Per pixel the demodulated value is blended with its history, reprojected from the previous call's guide and camera
@@ -116,6 +117,31 @@ int rt_denoise_temporal_timing(rt_ctx* ctx, float ms[6]);
 int rt_denoise_temporal_motion(rt_ctx* ctx, int on);
 /* the toggle, and whether the last rt_denoise_temporal call was a followed call; either pointer may be null, not both */
 int rt_denoise_temporal_motion_get(rt_ctx* ctx, int* on, int* last_call_followed);
+/* (r30) Anti-lag for the temporal denoiser (csrc/denoise_antilag.h), default off: with it off every byte and
+ * every launch is what it was without the call. rt_denoise_temporal blends with alpha = max(alpha, 1 / h) and cannot tell that its
+ * history no longer describes the lighting (a moved object's shadow on a wall that did not move). An adapted call is one with the
+ * toggle on and a history (not the first call after a reset); followed calls of rt_denoise_temporal_motion count. In an adapted call
+ * every participating pixel with a history compares, over the (2 radius + 1)^2 window of pixels that have a history and whose normal
+ * is within n . n' >= 0.9 of its own, the summed luminance of the current demodulated frame (mc) with that of the reprojected history
+ * (mh): lambda = |mc - mh| / (max(mc, mh) + floor * members), lambda' = clamp((lambda - gradient_lo) / (gradient_hi - gradient_lo),
+ * 0, 1), and both alphas become alpha + (1 - alpha) lambda' before max(., 1 / h). The history length is unchanged.
+ * RT_BUF_DENOISE_HISTORY's fourth component carries lambda' (0 without history, in calls that are not adapted, with the toggle off).
+ * The cost in a static scene is real (a firefly in a dark window is a relative gradient of 1; the floor trades it against the
+ * response): DESIGN.md section 19 has the numbers. Parameters out of range or not finite: RT_ERR_ARG (nothing changes). Strip
+ * contexts: RT_ERR_UNSUPPORTED. Changes neither rt_state_epoch nor the look-ahead, nor any reservoir or history buffer, and needs no
+ * reset. Not an rt_tuning key: tuning keys never change results. */
+typedef struct
+{
+    int32_t radius;                  /* 1..4, default 4 */
+    float gradient_lo, gradient_hi; /* 0 <= lo < hi, defaults 0.2 and 0.8 */
+    float floor;                     /* >= 0, default 0.05 */
+} rt_denoise_antilag_params;
+int rt_denoise_temporal_antilag(rt_ctx* ctx, int on, const rt_denoise_antilag_params* params /* NULL = defaults */);
+/* the toggle, its parameters, and whether the last rt_denoise_temporal call was an adapted call; any pointer may be null, not all */
+int rt_denoise_temporal_antilag_get(rt_ctx* ctx, int* on, rt_denoise_antilag_params* params, int* last_call_adapted);
+/* device ms of k_denoise_antilag in the last rt_denoise_temporal call, if that was a timed adapted call (else RT_ERR_STATE);
+ * rt_denoise_temporal_timing's ms[1] covers the gather kernel and this one */
+int rt_denoise_temporal_antilag_timing(rt_ctx* ctx, float* ms);
 
 /* ---- rt_frame in stages ---- */
 /* The same frame cut into stages for strip contexts (multi-GPU): stage 0 = [clear,] raycast,

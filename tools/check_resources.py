@@ -54,6 +54,9 @@ BUDGET = [
     (r"^k_denoise_output", 0, 8),
     (r"^k_denoise_temporal", 0, 8),      # r10 rt_denoise_temporal: reprojection + integration
     (r"^k_denoise_var_hist", 0, 8),      # variance with history
+    # r30 rt_denoise_temporal_antilag: dn_temporal_pixel up to the blend (41 VGPRs as its siblings), and the window kernel, 12 800 B of LDS
+    (r"^k_denoise_antilag_gather<", 0, 8),
+    (r"^k_denoise_antilag$", 0, 8),
     (r"^k_denoise_temporal_motion", 0, 8),  # r25 rt_denoise_temporal_motion: the followed call's form, 41 VGPRs / 46 SGPRs (its sibling: 41 / 44)
 ]
 
