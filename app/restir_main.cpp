@@ -10,7 +10,7 @@
  *              [--shadowed 0|1] [--visreuse 0|1] [--accumulate 0|1] [--by-kernel]
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
- *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased] [--reproject]
+ *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased] [--reproject] [--unbiased-temporal]
  *              [--move-tris first count dx dy dz] [--follow-motion] [--denoise-follow-motion]
  *              [--denoise-antilag [radius lo hi floor]]
  *              [--light-sampling uniform|power]
@@ -30,6 +30,9 @@
  * --reproject (--example 10, one GPU): rt_temporal_reprojection, after a camera move the temporal merge takes a pixel's history from the
  *     previous frame's pixel that saw the same surface point; meant for --orbit, a camera that stands still
  *     renders what it renders without the flag.
+ * --unbiased-temporal (with --reproject): rt_temporal_unbiased, a temporal merge whose history comes from another pixel normalises by
+ *     1/Z, at the price of at most one shadow ray from the history's origin; meant for --orbit dx dy
+ *     --reproject, and with --unbiased for a frame whose every reuse step normalises by 1/Z. Not with --follow-motion.
  * --orbit dx dy (one GPU): before every frame from the second on, rt_camera_orbit(dx, dy) (a left-button drag); with
  * --accumulate 1 that frame starts a new accumulation, as the example clears on a camera update.
  * --move-lights dx dy dz (--example 10, also with --ranks): before every frame from the second on, the emissive triangles move
@@ -457,7 +460,7 @@ int main(int argc, char** argv)
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
-    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false, follow_motion = false, move_lights_given = false, denoise_follow = false;
+    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false, unbiased_temporal = false, follow_motion = false, move_lights_given = false, denoise_follow = false;
     bool denoise_antilag = false, antilag_given = false;
     rt_denoise_antilag_params antilag = {4, 0.2f, 0.8f, 0.05f};
     int light_mode = RT_LIGHTS_UNIFORM;
@@ -507,6 +510,7 @@ int main(int argc, char** argv)
         else if (a == "--denoise-temporal") denoise_temporal = true;
         else if (a == "--unbiased") unbiased = true;
         else if (a == "--reproject") reproject = true;
+        else if (a == "--unbiased-temporal") unbiased_temporal = true;
         else if (a == "--follow-motion") follow_motion = true;
         else if (a == "--denoise-follow-motion") denoise_follow = true;
         else if (a == "--denoise-antilag")
@@ -549,6 +553,8 @@ int main(int argc, char** argv)
     if (denoise_follow && !denoise_temporal) { fprintf(stderr, "--denoise-follow-motion needs --denoise N --denoise-temporal\n"); return 2; }
     if (denoise_antilag && !denoise_temporal) { fprintf(stderr, "--denoise-antilag needs --denoise N --denoise-temporal\n"); return 2; }
     if (follow_motion && !reproject) { fprintf(stderr, "--follow-motion needs --reproject\n"); return 2; }
+    if (unbiased_temporal && !reproject) { fprintf(stderr, "--unbiased-temporal needs --reproject\n"); return 2; }
+    if (unbiased_temporal && follow_motion) { fprintf(stderr, "--unbiased-temporal and --follow-motion exclude each other\n"); return 2; }
     if (mv.all && move_lights_given) { fprintf(stderr, "--move-tris and --move-lights exclude each other\n"); return 2; }
     if (light_mode != RT_LIGHTS_UNIFORM && example != 10) { fprintf(stderr, "--light-sampling applies to --example 10\n"); return 2; }
     if (orbit && (ranks > 1 || example == 4 || example == 6)) { fprintf(stderr, "--orbit applies to one GPU and --example 10, 7, 8 and 9\n"); return 2; }
@@ -665,6 +671,7 @@ int main(int argc, char** argv)
     if (unbiased) CK(rt_spatial_unbiased(ctx, 1));
     if (reproject) CK(rt_temporal_reprojection(ctx, 1));
     if (follow_motion) CK(rt_temporal_motion(ctx, 1));
+    if (unbiased_temporal) CK(rt_temporal_unbiased(ctx, 1));
     if (denoise_follow) CK(rt_denoise_temporal_motion(ctx, 1));
     if (denoise_antilag) CK(rt_denoise_temporal_antilag(ctx, 1, antilag_given ? &antilag : nullptr));
     CK(rt_light_sampling(ctx, light_mode));

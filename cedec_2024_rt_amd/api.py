@@ -48,6 +48,7 @@ INTERNAL_EXPORTS = [
     "rt_light_sampling", "rt_light_sampling_get", "rt_light_table",
     "rt_temporal_reprojection", "rt_temporal_reprojection_get", "rt_reservoir_camera", "rt_temporal_reprojection_stats",
     "rt_temporal_motion", "rt_temporal_motion_get", "rt_reservoir_scene", "rt_temporal_motion_range", "rt_temporal_motion_stats",
+    "rt_temporal_unbiased", "rt_temporal_unbiased_get", "rt_temporal_unbiased_stats",
     "rt_denoise_temporal_motion", "rt_denoise_temporal_motion_get",
     "rt_denoise_temporal_antilag", "rt_denoise_temporal_antilag_get", "rt_denoise_temporal_antilag_timing",
 ]
@@ -219,6 +220,10 @@ def load_library(exp=False, path=None):
         L.rt_reservoir_scene.argtypes = [vp, ci, vp, vp, vp]
         L.rt_temporal_motion_range.argtypes = [vp, vp, vp, vp]
         L.rt_temporal_motion_stats.argtypes = [vp, vp]
+    if hasattr(L, "rt_temporal_unbiased"):  # r31; likewise
+        L.rt_temporal_unbiased.argtypes = [vp, ci]
+        L.rt_temporal_unbiased_get.argtypes = [vp, vp]
+        L.rt_temporal_unbiased_stats.argtypes = [vp, vp]
     if hasattr(L, "rt_denoise_temporal_motion"):  # r25; likewise
         L.rt_denoise_temporal_motion.argtypes = [vp, ci]
         L.rt_denoise_temporal_motion_get.argtypes = [vp, vp, vp]
@@ -924,6 +929,28 @@ class Renderer:
         v = C.c_int()
         self._ck(self.L.rt_temporal_motion_get(self.h, C.byref(v)))
         return bool(v.value)
+
+    def temporal_unbiased(self, on=None):
+        """rt_temporal_unbiased: while temporal_reprojection is on, a temporal merge whose history comes from another pixel normalises
+        by 1/Z: the gathered record counts only if the selected sample lies in its support, at the price of at most one shadow ray
+        from its origin. Default off. on=None queries; returns the state. Whole-frame contexts; refuses to go on
+        beside temporal_motion."""
+        if not hasattr(self.L, "rt_temporal_unbiased"):  # an older build through RT_LIB_PATH: the toggle is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_temporal_unbiased")
+        if on is not None:
+            self._ck(self.L.rt_temporal_unbiased(self.h, int(bool(on))))
+        v = C.c_int()
+        self._ck(self.L.rt_temporal_unbiased_get(self.h, C.byref(v)))
+        return bool(v.value)
+
+    def temporal_unbiased_stats(self):
+        """while walk_stats_enable is on: shaded pixels merged by unbiased launches, those whose history kept an M > 0, those among them
+        whose history was kept out of Z, and rays walked from a history's origin"""
+        if not hasattr(self.L, "rt_temporal_unbiased_stats"):  # an older build through RT_LIB_PATH, as above
+            raise RtError("this build of librestir_rt has no rt_temporal_unbiased_stats")
+        a = np.zeros(4, dtype=np.uint64)
+        self._ck(self.L.rt_temporal_unbiased_stats(self.h, _p(a)))
+        return dict(merged=int(a[0]), valid=int(a[1]), excluded=int(a[2]), history_rays=int(a[3]))
 
     def denoise_temporal_motion(self, on=None):
         """rt_denoise_temporal_motion: denoise_temporal's history of a pixel on a triangle that update_scene has moved since the previous

@@ -13,6 +13,7 @@
 #include "light_alias.h"
 #include "temporal_reproject.h"
 #include "temporal_motion.h"
+#include "temporal_unbiased.h"
 
 using namespace rt;
 
@@ -92,7 +93,8 @@ enum { WALK_RAYCAST = 0, WALK_GENERATE = 1, WALK_SPATIAL = 2, WALK_RESOLVE = 3, 
        WALK_PICKS = 5 /* rt_neighbour_pick_stats: {neighbour picks of k_spatial_coop, near ties (lanes on the exact path), -, -} */,
        WALK_REPROJECT = 6 /* rt_temporal_reprojection_stats: {shaded pixels merged by a reprojecting launch, valid histories, gathered from another pixel, -} */,
        WALK_MOTION = 7 /* rt_temporal_motion_stats: {shaded pixels merged by a motion launch, on moved triangles, valid histories among those, -} */,
-       WALK_SLOTS = 8 };
+       WALK_TUNBIASED = 8 /* rt_temporal_unbiased_stats: {shaded pixels merged by an unbiased launch, with Mk > 0, history kept out of Z, rays walked from a history origin} */,
+       WALK_SLOTS = 9 };
 /* one ray per lane at most; works under any exec mask (ballots count the active lanes) */
 RT_DEV void count_walk_flags(unsigned long long* __restrict__ st, bool ref, bool walked, bool self, bool skipped)
 {
@@ -1137,6 +1139,85 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(SceneView S, FrameParams P, 
     if (SHADOWED) r.ownv = ownv_of(P.ownv_tag, (took_prev ? V_prev : V_cur) != 0.0f);
     else if (took_prev) r.ownv = 0u;
     res_store(rec, radb, li, r, true);
+}
+
+/* rt_temporal_unbiased (temporal_unbiased.h): the temporal merge with the 1/Z normalisation, launched only where
+ * the history is gathered by reprojection (history_camera) and the toggle is on. Merges in place on `rec` / `radb`, which hold the
+ * pixel's candidates; the history buffer is another one (rt_temporal_resampling refuses prev == inout, a staged frame's stage 0 never
+ * writes its history). The form is k_spatial_unbiased's: one-wavefront workgroups on 8 x 8 tiles, two phases (the rays depend on which
+ * sample won), the <= 2 rays of a pixel through occluded_rays with an origin each, every lane stays to the end and helps the others'
+ * walks. The history is gathered per lane as load_prev_reprojected does it (the index exists only behind tr_previous_pixel's float
+ * range test and gather_prev_pixel's integer test against the rows held). The ray from the history's origin has no triangle known
+ * to start from, so it takes no self-occlusion pre-test; the own ray takes the pixel's. At most one ray per pixel starts at a surface
+ * other than its own, and the own ray is walked only where the history's sample won: resolve finds its answer in the own-visibility
+ * flags and does not walk it again. Unshadowed target function only.
+ * count_merged: the launch counts its shaded pixels in rt_temporal_reprojection_stats' first counter (rt_temporal_resampling); in a
+ * staged frame the candidates' launch in front of this one has counted them already, and this launch adds the valid and the
+ * moved histories only.
+ * No register budget: the resource log shows no spill without one (tools/check_resources.py). */
+__global__ __launch_bounds__(TRACE_BLOCK) void k_temporal_unbiased(SceneView S, FrameParams P, const float4* __restrict__ g0,
+                                                     const float4* __restrict__ g1, const float4* __restrict__ prev_rec,
+                                                     const float4* __restrict__ prev_rad, float4* __restrict__ rec, float4* __restrict__ radb,
+                                                     const int count_merged)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_stack[WIDE_LDS_ROWS * TRACE_BLOCK];
+    int x = 0, row = P.lrow0;
+    const bool in_image = tile_pixel<TRACE_BLOCK>(P, x, row);
+    const int yi = P.H - 1 - row;
+    const size_t li = in_image ? (size_t)x + (size_t)(row - P.lrow0) * P.W : 0;
+    float4 G0 = make_float4(0.0f, 0.0f, 0.0f, as_float(-1)), G1 = make_float4(0.0f, 1.0f, 0.0f, 0.0f);
+    if (in_image) { G0 = g0[li]; G1 = g1[li]; }
+    const bool active = in_image && (as_uint(G1.w) & GB_SHADED) && P.use_temporal;
+    if (__ballot(active) == 0ull) return; /* one wavefront per workgroup: nobody is left to help */
+    const f3 sp = F3(G0.x, G0.y, G0.z), sn = F3(G1.x, G1.y, G1.z);
+
+    /* phase 1: the merge chain */
+    Res r = res_zero(), pr = res_zero();
+    TuChain c;
+    c.Mk = 0; c.Z = 0; c.from_hist = false;
+    bool in_geo = false;
+    if (active)
+    {
+        bool dummy;
+        r = res_load(rec, li, dummy);
+        const float4 rq = radb[li];
+        r.rad = F3(rq.x, rq.y, rq.z);
+        r.ownv = as_uint(rq.w);
+        {
+            /* load_prev_reprojected, with its counters split as count_merged says */
+            const TrPixel q = tr_previous_pixel(sp, P.prev_origin, P.prev_right, P.prev_up, P.W, P.H);
+            bool have;
+            pr = gather_prev_pixel(P, q, prev_rec, prev_rad, have);
+            if (P.stats) count_walk_flags(P.stats + 4 * WALK_REPROJECT, count_merged != 0, have, have && (q.xq != x || q.rq != row), false);
+        }
+        PCG rng = pcg_init(hashPCG4((uint32_t)x, (uint32_t)yi, (uint32_t)P.frame, 1u), 0);
+        const float u = rng.uniformf();
+        c = tu_merge_chain(r, pr, sp, sn, P.eye, P.ris_sample_count, P.vis_reuse != 0, u);
+        if (c.from_hist) r.rad = pr.rad;
+        in_geo = tu_hist_geometry(c, r, pr);
+    }
+
+    /* phase 2: ray 0 from the history's origin, ray 1 from the pixel's own surface, both to the selected sample */
+    const f3 y = r.hit_p;
+    const bool vr = P.vis_reuse != 0;
+    const bool want_hist = active && tu_needs_hist_ray(c, in_geo, vr), want_own = active && tu_needs_own_ray(c, vr);
+    const uint32_t need = (want_hist ? 1u : 0u) | (want_own ? 2u : 0u);
+    f3 org[2], dir[2];
+    org[0] = pr.org_p + 0.001f * pr.org_n; dir[0] = y - pr.org_p;
+    org[1] = sp + 0.001f * sn;             dir[1] = y - sp;
+    uint32_t occl = self_occluded(S.bvh.tv, as_int(G0.w), org[1], dir[1], sn, want_own) ? 2u : 0u;
+    /* the reference's merge traces nothing here: 0 reference rays; walked / settled by the pixel's own triangle */
+    if (P.stats) count_walk_counts(P.stats + 4 * WALK_GENERATE, 0u, (uint32_t)__popc(need & ~occl), (uint32_t)__popc(occl), 0u);
+    occl |= occluded_rays<2, TRACE_BLOCK>(S.wide, s_stack, org, dir, need & ~occl);
+    bool in_z = false;
+    if (active)
+    {
+        const bool own_visible = !(occl & 2u);
+        in_z = tu_finish(r, pr, c, in_geo, vr, !(occl & 1u), own_visible, sp, sn);
+        if (c.from_hist) r.ownv = vr ? ownv_of(P.ownv_tag, own_visible) : 0u;
+        res_store(rec, radb, li, r, true);
+    }
+    if (P.stats) count_walk_counts(P.stats + 4 * WALK_TUNBIASED, active ? 1u : 0u, (active && c.Mk > 0) ? 1u : 0u, (active && c.Mk > 0 && !in_z) ? 1u : 0u, want_hist ? 1u : 0u);
 }
 
 /* --------------------------------------------------------- spatial_resampling */

@@ -109,6 +109,7 @@ struct rt_ctx
      * rt_denoise_temporal_motion, section 15); d_tv_prev (layout of d_tv) holds the kept vertices while moved.kept. */
     HistoryTag res_tag[5];
     bool reproject = false;
+    bool temporal_unbiased = false; /* rt_temporal_unbiased (r31, section 20): a reprojecting merge normalises by 1/Z (k_temporal_unbiased) */
     MovedGeometry moved;
     float4* d_tv_prev = nullptr;
     unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters, then the slot of rt_occluder_hint_stats (WALK_SLOTS) */
@@ -2102,6 +2103,24 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
     /* before the tag below: dst may not be prev, but the order costs nothing. A motion launch is a reprojecting one (mo implies rp) */
     const bool mo = fuse && history_motion(c, prev_phys, P, L.vis);
     const bool rp = mo || (fuse && history_camera(c, prev_phys, P));
+    /* rt_temporal_unbiased: a reprojecting launch becomes two, the candidates without the merge and k_temporal_unbiased in place on
+     * their buffer (below). A motion launch cannot be one: the two toggles refuse each other. */
+    const bool ub = rp && !mo && c->temporal_unbiased;
+    if (ub && sh) RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_unbiased: the shadowed target function is not built for the 1/Z merge");
+    const FrameParams Pu = P; /* the merge's: the history buffer's camera */
+    if (ub)
+    {
+        /* the product's fused form, whichever the tuning picks, made to merge nothing: the reprojecting instantiation under a history
+         * camera of NaNs. The fused kernels merge by template, not by FrameParams::use_temporal, so the NaN camera alone does it: the
+         * launch still projects, draws and runs the rejection heuristics per pixel, but every gather fails the float range test
+         * (temporal_reproject.h) and the merge sees Reservoir{}: weight 0 is never accepted, M + 0, and ucw is recomputed by the
+         * expression that made it, so what the launch stores is the candidates' records bit for bit, each with its own
+         * visibility-reuse ray walked. No instantiation changes and none is added to k_generate_candidate. The launch counts its
+         * shaded pixels as merged by a reprojecting launch, without a valid history (rt_temporal_reprojection_stats); the merge
+         * below adds the valid and the moved ones and does not count the pixels again. */
+        const float qnan = __builtin_nanf("");
+        P.prev_origin = P.prev_right = P.prev_up = F3(qnan, qnan, qnan);
+    }
     tag_reservoir(c, dst_phys);
     const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
     const int g = trace_grid(c, L);
@@ -2172,6 +2191,12 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
 #undef GEN_LAUNCH_RP
 #undef GEN_LAUNCH
     RT_HIP(c, hipGetLastError());
+    if (ub)
+    {
+        /* same stream, same rows, same tag: reads the G-buffer the launch above read or wrote, merges the history in place */
+        k_temporal_unbiased<<<g, TRACE_BLOCK, 0, L.stream>>>(S, Pu, L.g0, L.g1, prec, prad, orec, orad, 0 /* the launch above has counted the merged pixels */);
+        RT_HIP(c, hipGetLastError());
+    }
     return RT_OK;
 }
 
@@ -2203,8 +2228,17 @@ int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
     const int pp = c->frame.res_map[prev], pi = c->frame.res_map[inout];
     const bool mo = history_motion(c, pp, P, c->gbuf.vis);
     const bool rp = !mo && history_camera(c, pp, P);
+    const bool ub = rp && c->temporal_unbiased; /* rt_temporal_unbiased: the 1/Z merge wherever the history is gathered by reprojection */
+    if (ub && c->opt.use_shadowed_target_function)
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_unbiased: the shadowed target function is not built for the 1/Z merge");
     tag_reservoir(c, pi, c->res_tag[pi].gserial); /* merged in place: its shaded bits stay those of the G-buffer it was made from */
-    if (mo && c->opt.use_shadowed_target_function)
+    if (ub)
+    {
+        P = make_params(c, L, frame, 0, K_GENERATE); /* a tracing kernel on 8 x 8 tiles: the candidates' tile order */
+        history_camera(c, pp, P);
+        k_temporal_unbiased<<<trace_grid(c, L), TRACE_BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi], 1);
+    }
+    else if (mo && c->opt.use_shadowed_target_function)
         k_temporal<true, true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
     else if (mo)
         k_temporal<false, true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
@@ -3245,6 +3279,8 @@ int rt_temporal_motion(rt_ctx* c, int on)
     RT_CHECK_CTX(c);
     if (!whole_frame(c))
         RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_motion: a strip context holds only its own rows of the history");
+    if (on && c->temporal_unbiased)
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_motion: rt_temporal_unbiased is on, and its ray from the history's origin would start in geometry that no longer exists");
     RT_HIP(c, hipSetDevice(c->device));
     drop_look_ahead(c);
     ++c->epoch;
@@ -3285,6 +3321,39 @@ int rt_temporal_motion_stats(rt_ctx* c, uint64_t out[3])
     int rc = rt_sync(c);
     if (rc != RT_OK) return rc;
     RT_HIP(c, hipMemcpy(out, c->d_walk + 4 * WALK_MOTION, 3 * 8, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+/* r31. The temporal merge with the 1/Z normalisation wherever its history is gathered by reprojection (temporal_unbiased.h, DESIGN.md
+ * section 20), in effect only while rt_temporal_reprojection is on. Changes results, so not an rt_tuning key; counts as an option change
+ * and drops the look-ahead. Touches no buffer: a history written with the toggle off may carry a travelled origin into the first
+ * unbiased merge, and fades with the M cap. */
+int rt_temporal_unbiased(rt_ctx* c, int on)
+{
+    RT_CHECK_CTX(c);
+    if (!whole_frame(c))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_unbiased: a strip context holds only its own rows of the history");
+    if (on && c->moved.on[FOLLOW_RESTIR])
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_unbiased: rt_temporal_motion is on, and the ray from the history's origin would start in geometry that no longer exists");
+    c->temporal_unbiased = on != 0;
+    drop_look_ahead(c);
+    ++c->epoch;
+    return RT_OK;
+}
+int rt_temporal_unbiased_get(rt_ctx* c, int* on)
+{
+    RT_CHECK_CTX(c);
+    if (!on) return RT_ERR_ARG;
+    *on = c->temporal_unbiased ? 1 : 0;
+    return RT_OK;
+}
+int rt_temporal_unbiased_stats(rt_ctx* c, uint64_t out[4])
+{
+    RT_CHECK_CTX(c);
+    if (!out) return RT_ERR_ARG;
+    if (!c->d_walk) RT_FAIL(c, RT_ERR_STATE, "rt_walk_stats_enable first");
+    int rc = rt_sync(c);
+    if (rc != RT_OK) return rc;
+    RT_HIP(c, hipMemcpy(out, c->d_walk + 4 * WALK_TUNBIASED, 4 * 8, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 /* How the candidates pick their light (light_alias.h). Changes results, so not an rt_tuning key; counts as an

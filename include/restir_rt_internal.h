@@ -396,6 +396,30 @@ int rt_temporal_motion_range(rt_ctx* ctx, uint32_t* lo, uint32_t* hi, uint64_t* 
 /* counted while rt_walk_stats_enable is on, zeroed by it: out[0] = shaded pixels merged by a motion launch, out[1] = those on a
  * triangle of the moved range, out[2] = those among them that found a valid history. Synchronises. */
 int rt_temporal_motion_stats(rt_ctx* ctx, uint64_t out[3]);
+/* (r31) The temporal merge normalised by 1/Z where its history comes from another pixel (DESIGN.md section 20;
+ * csrc/temporal_unbiased.h), default off, in effect only while rt_temporal_reprojection is on: with it off every byte and every launch
+ * is what it was without the call. An unbiased launch is a temporal merge (rt_temporal_resampling, stage 0 of rt_frame /
+ * rt_frame_stage*) that is a reprojecting launch (its history buffer's camera tag differs from the current camera in its 36 bytes)
+ * while the toggle is on; with equal bytes or no tag the launches are the ones of the toggle off, so a camera that stands still, the
+ * look-ahead stage 0 and rt_gbuffer_reuse frames cost and compute what they did. The merge chain is the reference's (same draw, cap
+ * and rejection heuristics); afterwards the gathered record counts in Z only if the selected sample y lies in its support: geometry
+ * term > 0 from the record's origin and, under use_visibility_reuse, y visible from there (the record's flag if y is its own sample,
+ * one shadow ray from its origin otherwise). W = w_sum / (Z p-hat), M stays the sum. Where the history's sample wins, the ray from the
+ * pixel's own surface is walked in the merge (resolve finds its answer and does not walk it again), the stored visibility flag is its
+ * answer, and the record's origin is the writer's surface whoever the sample came from. In a staged frame stage 0 is then two launches
+ * on the frame's stream (the candidates without the merge, then k_temporal_unbiased), both inside rt_timing's ms[2]. The first unbiased
+ * launch after frames rendered with the toggle off may meet an origin that travelled with its sample; nothing repairs it, it fades
+ * with the M cap. RT_ERR_UNSUPPORTED: strip contexts (at the toggle); use_shadowed_target_function = 1 and the [exp] stage-0 variants
+ * (rt_tuning keys 11 and 12), at an unbiased launch; rt_temporal_motion and this toggle both on (the second call refuses: the
+ * history's origin would lie in geometry that no longer exists). The call changes rt_state_epoch and drops look-ahead work, touches no
+ * buffer. rt_ray_count keeps counting the reference's rays. Not an rt_tuning key: tuning keys never change results. */
+int rt_temporal_unbiased(rt_ctx* ctx, int on);
+int rt_temporal_unbiased_get(rt_ctx* ctx, int* on);
+/* counted while rt_walk_stats_enable is on, zeroed by it: out[0] = shaded pixels merged by unbiased launches, out[1] = those whose
+ * history kept an M > 0 after the cap and the rejection heuristics, out[2] = those among them whose history was kept out of Z,
+ * out[3] = rays walked from a history's origin. An unbiased launch is a reprojecting launch and counts in
+ * rt_temporal_reprojection_stats as one, each shaded pixel once. Synchronises. */
+int rt_temporal_unbiased_stats(rt_ctx* ctx, uint64_t out[4]);
 /* the alias table and the realised counts (thr / alias / K per light, light list order; any pointer may be null), for tests; n = the
  * scene's light count (RT_ERR_ARG otherwise); RT_ERR_STATE without a scene */
 int rt_light_table(rt_ctx* ctx, uint32_t* thr, uint32_t* alias, uint64_t* K, uint32_t n);

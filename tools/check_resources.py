@@ -36,6 +36,7 @@ BUDGET = [
     (r"^k_generate_candidate<true, true, false, false, false, false, (true|false), true, true>", 0, 4),   # shadowed target function
     (r"^k_temporal<false, true, true>", 0, 7),                                # rt_temporal_resampling
     (r"^k_temporal<true, true, true>", 0, 4),                                 # ... shadowed
+    (r"^k_temporal_unbiased", 0, 4),     # r31 rt_temporal_unbiased: 101 VGPRs without a budget, no spill (budget 5: 95, no spill; 6: 80 and 15 spilled)
     (r"^k_spatial_coop<6, false, 256>", 0, 6),                                # the roofline kernel
     (r"^k_spatial_coop<6, true, 256>", 0, 5),                                 # strips: halo lists read / written in the pass
     (r"^k_resolve<", 0, 8),
