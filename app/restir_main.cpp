@@ -11,7 +11,7 @@
  *              [--example 10|7|8|9|6|4] [--ppm out.ppm] [--png out.png] [--pfm out.pfm] [--rgba out.raw] [--dump-tris out.tris]
  *              [--ranks N [--mirror | --shm] [--bounds 0,a,b,...,H | --cost-strips]] [--threads N]
  *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased] [--reproject] [--unbiased-temporal]
- *              [--move-tris first count dx dy dz] [--follow-motion] [--denoise-follow-motion]
+ *              [--move-tris first count dx dy dz] [--follow-motion] [--follow-lights] [--denoise-follow-motion]
  *              [--denoise-antilag [radius lo hi floor]]
  *              [--light-sampling uniform|power]
  *
@@ -42,6 +42,9 @@
  *     [first, first + count) moves by (dx, dy, dz) before every frame from the second on (the same float add); not with --move-lights.
  * --follow-motion (with --reproject): rt_temporal_motion, the temporal merge of a pixel on a moved triangle takes the history of the
  *     previous frame's pixel that saw the point it was at; meant for --move-tris on non-emissive triangles.
+ * --follow-lights (--example 10, one GPU; needs neither --reproject nor --follow-motion): rt_temporal_light_motion, for --move-lights and
+ *     for --move-tris over emissive triangles: the light samples of the temporal history are carried along with the emitters they
+ *     lie on at every update. Prints the re-based / located / moved / emptied totals at the end.
  * --denoise-follow-motion (with --denoise N --denoise-temporal): rt_denoise_temporal_motion, the denoiser's history of a pixel on a
  *     moved triangle is looked up from where its surface point was; meant for --move-tris. Each frame's
  *     denoise line then says whether the call followed.
@@ -460,7 +463,7 @@ int main(int argc, char** argv)
     bool by_kernel = false, mirror = false, shm = false, equal_strips = true, size_set = false, cam_set = false;
     std::vector<int> given_bounds;
     int example = 10, ranks = 1, threads = 0, denoise = -1;
-    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false, unbiased_temporal = false, follow_motion = false, move_lights_given = false, denoise_follow = false;
+    bool denoise_temporal = false, orbit = false, unbiased = false, reproject = false, unbiased_temporal = false, follow_motion = false, follow_lights = false, move_lights_given = false, denoise_follow = false;
     bool denoise_antilag = false, antilag_given = false;
     rt_denoise_antilag_params antilag = {4, 0.2f, 0.8f, 0.05f};
     int light_mode = RT_LIGHTS_UNIFORM;
@@ -512,6 +515,7 @@ int main(int argc, char** argv)
         else if (a == "--reproject") reproject = true;
         else if (a == "--unbiased-temporal") unbiased_temporal = true;
         else if (a == "--follow-motion") follow_motion = true;
+        else if (a == "--follow-lights") follow_lights = true;
         else if (a == "--denoise-follow-motion") denoise_follow = true;
         else if (a == "--denoise-antilag")
         {
@@ -552,6 +556,8 @@ int main(int argc, char** argv)
     if (reproject && (ranks > 1 || example != 10)) { fprintf(stderr, "--reproject applies to one GPU and --example 10\n"); return 2; }
     if (denoise_follow && !denoise_temporal) { fprintf(stderr, "--denoise-follow-motion needs --denoise N --denoise-temporal\n"); return 2; }
     if (denoise_antilag && !denoise_temporal) { fprintf(stderr, "--denoise-antilag needs --denoise N --denoise-temporal\n"); return 2; }
+    if (follow_lights && example != 10) { fprintf(stderr, "--follow-lights needs --example 10\n"); return 2; }
+    if (follow_lights && ranks > 1) { fprintf(stderr, "--follow-lights applies to one GPU: strip contexts are not re-based\n"); return 2; }
     if (follow_motion && !reproject) { fprintf(stderr, "--follow-motion needs --reproject\n"); return 2; }
     if (unbiased_temporal && !reproject) { fprintf(stderr, "--unbiased-temporal needs --reproject\n"); return 2; }
     if (unbiased_temporal && follow_motion) { fprintf(stderr, "--unbiased-temporal and --follow-motion exclude each other\n"); return 2; }
@@ -671,6 +677,7 @@ int main(int argc, char** argv)
     if (unbiased) CK(rt_spatial_unbiased(ctx, 1));
     if (reproject) CK(rt_temporal_reprojection(ctx, 1));
     if (follow_motion) CK(rt_temporal_motion(ctx, 1));
+    if (follow_lights) CK(rt_temporal_light_motion(ctx, 1));
     if (unbiased_temporal) CK(rt_temporal_unbiased(ctx, 1));
     if (denoise_follow) CK(rt_denoise_temporal_motion(ctx, 1));
     if (denoise_antilag) CK(rt_denoise_temporal_antilag(ctx, 1, antilag_given ? &antilag : nullptr));
@@ -769,6 +776,13 @@ int main(int argc, char** argv)
     {
         CK(rt_ray_count(ctx, &rays, &shaded));
         printf("rays/frame: %llu (shaded pixels %llu)\n", (unsigned long long)rays, (unsigned long long)shaded);
+        if (follow_lights)
+        {
+            uint64_t lf[5] = {0, 0, 0, 0, 0};
+            CK(rt_temporal_light_motion_stats(ctx, lf));
+            printf("follow-lights: %llu buffers re-based; records examined %llu, located %llu, moved %llu, emptied %llu\n", (unsigned long long)lf[0],
+                   (unsigned long long)lf[1], (unsigned long long)lf[2], (unsigned long long)lf[3], (unsigned long long)lf[4]);
+        }
     }
     else
     {

@@ -51,6 +51,8 @@ INTERNAL_EXPORTS = [
     "rt_temporal_unbiased", "rt_temporal_unbiased_get", "rt_temporal_unbiased_stats",
     "rt_denoise_temporal_motion", "rt_denoise_temporal_motion_get",
     "rt_denoise_temporal_antilag", "rt_denoise_temporal_antilag_get", "rt_denoise_temporal_antilag_timing",
+    "rt_temporal_light_motion", "rt_temporal_light_motion_get", "rt_temporal_light_motion_stats", "rt_temporal_light_motion_timing",
+    "rt_temporal_light_motion_path",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -224,6 +226,12 @@ def load_library(exp=False, path=None):
         L.rt_temporal_unbiased.argtypes = [vp, ci]
         L.rt_temporal_unbiased_get.argtypes = [vp, vp]
         L.rt_temporal_unbiased_stats.argtypes = [vp, vp]
+    if hasattr(L, "rt_temporal_light_motion"):  # r32; likewise
+        L.rt_temporal_light_motion.argtypes = [vp, ci]
+        L.rt_temporal_light_motion_get.argtypes = [vp, vp, vp]
+        L.rt_temporal_light_motion_stats.argtypes = [vp, vp]
+        L.rt_temporal_light_motion_timing.argtypes = [vp, vp]
+        L.rt_temporal_light_motion_path.argtypes = [vp, ci]
     if hasattr(L, "rt_denoise_temporal_motion"):  # r25; likewise
         L.rt_denoise_temporal_motion.argtypes = [vp, ci]
         L.rt_denoise_temporal_motion_get.argtypes = [vp, vp, vp]
@@ -929,6 +937,38 @@ class Renderer:
         v = C.c_int()
         self._ck(self.L.rt_temporal_motion_get(self.h, C.byref(v)))
         return bool(v.value)
+
+    def temporal_light_motion(self, on=None):
+        """rt_temporal_light_motion: update_scene over a span that holds emissive triangles carries the light samples of the reservoir
+        histories along with the emitters they lie on. Default off; needs neither temporal_reprojection nor
+        temporal_motion. on=None queries. Returns dict(on, rebased): the state, and how many buffers the last update_scene re-based.
+        Whole-frame contexts."""
+        if not hasattr(self.L, "rt_temporal_light_motion"):  # an older build through RT_LIB_PATH: the toggle is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_temporal_light_motion")
+        if on is not None:
+            self._ck(self.L.rt_temporal_light_motion(self.h, int(bool(on))))
+        v, n = C.c_int(), C.c_int()
+        self._ck(self.L.rt_temporal_light_motion_get(self.h, C.byref(v), C.byref(n)))
+        return dict(on=bool(v.value), rebased=int(n.value))
+
+    def temporal_light_motion_stats(self):
+        """totals since the toggle went on: dict(buffers, examined, located, moved, emptied)"""
+        if not hasattr(self.L, "rt_temporal_light_motion_stats"):  # an older build through RT_LIB_PATH, as above
+            raise RtError("this build of librestir_rt has no rt_temporal_light_motion_stats")
+        a = np.zeros(5, dtype=np.uint64)
+        self._ck(self.L.rt_temporal_light_motion_stats(self.h, _p(a)))
+        return dict(zip(("buffers", "examined", "located", "moved", "emptied"), (int(x) for x in a)))
+
+    def temporal_light_motion_timing(self):
+        """device ms of the re-basing launches of the last update_scene (timing_enable and the toggle on during it)"""
+        ms = C.c_float()
+        self._ck(self.L.rt_temporal_light_motion_timing(self.h, C.byref(ms)))
+        return float(ms.value)
+
+    def temporal_light_motion_path(self, direct_max=-1):
+        """tests and measurements: spans of at most direct_max old lights loop over them, larger ones query the old tree (0: always the
+        tree, negative: the default). Same bytes either way."""
+        self._ck(self.L.rt_temporal_light_motion_path(self.h, int(direct_max)))
 
     def temporal_unbiased(self, on=None):
         """rt_temporal_unbiased: while temporal_reprojection is on, a temporal merge whose history comes from another pixel normalises

@@ -14,7 +14,10 @@ namespace rt
 {
 /* What a history buffer was written under: the RayGenerator, the geometry generation and the eye (valid under `has`). A reservoir
  * buffer also carries gserial, the serial of the G-buffer its shaded bits belong to (k_refresh_shaded): valid whether `has` or not,
- * and set alone where only the bits were refreshed. A copy of a buffer takes the whole tag: plain assignment. */
+ * and set alone where only the bits were refreshed. A copy of a buffer takes the whole tag: plain assignment.
+ * light_gen (rt_temporal_light_motion): the generation up to which the LIGHT side of the records (sample point,
+ * normal, radiance) is current. Set with gen by write, advanced alone by an update that re-based the buffer's samples onto the new
+ * emitters; gen stays what it was, rt_temporal_motion reads it. */
 struct HistoryTag
 {
     rt_raygen rg = {};
@@ -22,10 +25,16 @@ struct HistoryTag
     uint64_t gen = 0;
     float eye[3] = {0.0f, 0.0f, 0.0f};
     uint64_t gserial = 0;
+    uint64_t light_gen = 0;
     void write(const rt_raygen& rg_, uint64_t gen_, const float eye_[3], uint64_t gserial_)
     {
-        rg = rg_; has = true; gen = gen_; memcpy(eye, eye_, sizeof(eye)); gserial = gserial_;
+        rg = rg_; has = true; gen = gen_; memcpy(eye, eye_, sizeof(eye)); gserial = gserial_; light_gen = gen_;
     }
+    /* do the records' light samples describe generation geo_gen, the one an update is about to end? Written under it, or carried
+     * to it by the update before: two updates with no frame between them are both followed. An older or untagged buffer is not. */
+    bool light_current(uint64_t geo_gen) const { return has && std::max(gen, light_gen) == geo_gen; }
+    /* the update that ends generation geo_gen has re-based this buffer's samples (only a light_current buffer is re-based) */
+    void light_rebased(uint64_t geo_gen) { light_gen = geo_gen + 1; }
 };
 
 /* the two consumers of the kept vertices: the ReSTIR history (rt_temporal_motion) and the denoiser's (rt_denoise_temporal_motion) */

@@ -46,6 +46,7 @@ static_assert(ROLE_RES_0 == RT_RES_0 && ROLE_RES_1 == RT_RES_1 && ROLE_RES_TEMPO
 #include "bvh_build_device.h"
 #include "bvh_refit.h"
 #include "denoise_kernels.h"
+#include "light_follow_kernels.h"
 
 /* ======================================================================= host */
 
@@ -112,6 +113,19 @@ struct rt_ctx
     bool temporal_unbiased = false; /* rt_temporal_unbiased (r31, section 20): a reprojecting merge normalises by 1/Z (k_temporal_unbiased) */
     MovedGeometry moved;
     float4* d_tv_prev = nullptr;
+    /* rt_temporal_light_motion (r32, light_follow.h): the toggle; spans of at most lf_direct_max old lights take
+     * the direct loop, larger ones the point query on the old tree; d_lf_words: the device counters (LF_COUNTER_WORDS of 64 bit), then the six
+     * words of the early-out box; d_lf_stage: the span's new triangles and old light ids during an update; lf_stats[0]: buffers
+     * re-based since the toggle went on (the other four are the device counters); lf_last: buffers the last update re-based */
+    bool light_follow = false;
+    int lf_direct_max = LF_DIRECT_MAX_DEFAULT;
+    int lf_last = 0;
+    uint64_t lf_stats0 = 0;
+    unsigned long long* d_lf_words = nullptr;
+    void* d_lf_stage = nullptr;
+    size_t lf_stage_bytes = 0;
+    hipEvent_t lf_ev[2] = {nullptr, nullptr};
+    bool lf_timed = false, lf_launched = false;
     unsigned long long* d_walk = nullptr; /* rt_walk_stats: 4 kernel slots x 4 counters, then the slot of rt_occluder_hint_stats (WALK_SLOTS) */
     bool walk_on = false;
     /* r19, rt_occluder_hints: OCCLUDER_HINTS triangle indices per pixel of the local rows (occluder_hint.h), the triangles that occluded
@@ -623,6 +637,8 @@ int rt_destroy(rt_ctx* c)
     hipFree(c->d_dt_col);
     for (auto& e : c->dt_ev) if (e) hipEventDestroy(e);
     if (c->al_ev) hipEventDestroy(c->al_ev);
+    hipFree(c->d_lf_words); hipFree(c->d_lf_stage);
+    for (hipEvent_t e : c->lf_ev) if (e) hipEventDestroy(e);
     hipFree(c->d_counter); hipFree(c->d_stage); hipFree(c->d_paths[0]); hipFree(c->d_paths[1]); hipFree(c->d_pt_counters);
     if (c->ev_created) for (auto& e : c->ev) hipEventDestroy(e);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -1484,6 +1500,68 @@ static int refit_first_update(rt_ctx* c)
     return RT_OK;
 }
 
+/* rt_temporal_light_motion inside rt_scene_update(first, count), after the streams are drained and before anything of the old scene is
+ * overwritten (light_follow.h, light_follow_kernels.h). Runs iff the toggle is on and the span holds an emissive
+ * triangle in the OLD array; then every physical reservoir buffer whose light samples describe the generation this update ends
+ * (HistoryTag::light_current) is re-based in place with its radiance side record, one launch each, and its light_gen advances. */
+static int light_follow_rebase(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uint32_t count)
+{
+    c->lf_last = 0;
+    c->lf_timed = c->light_follow && c->timing;
+    c->lf_launched = false;
+    if (!c->light_follow) return RT_OK;
+    const auto lo = std::lower_bound(c->h_lights.begin(), c->h_lights.end(), first);
+    const auto hi = std::lower_bound(lo, c->h_lights.end(), first + count);
+    const uint32_t n_ids = (uint32_t)(hi - lo);
+    if (n_ids == 0u) return RT_OK;
+    int phys[5], np = 0;
+    for (int p = 0; p < 5; ++p)
+        if (c->d_rec[p] && c->d_rad[p] && c->res_tag[p].light_current(c->moved.geo_gen)) phys[np++] = p;
+    if (np == 0) return RT_OK;
+    hipStream_t st = c->stream;
+    const size_t tri_bytes = (size_t)count * 60, need = tri_bytes + (size_t)n_ids * 4;
+    if (need > c->lf_stage_bytes)
+    {
+        hipFree(c->d_lf_stage);
+        c->d_lf_stage = nullptr; c->lf_stage_bytes = 0;
+        RT_HIP(c, hipMalloc(&c->d_lf_stage, need));
+        c->lf_stage_bytes = need;
+    }
+    unsigned int* d_box = (unsigned int*)(c->d_lf_words + LF_COUNTER_WORDS);
+    RT_HIP(c, hipMemcpyAsync(c->d_lf_stage, triangles, tri_bytes, hipMemcpyHostToDevice, st));
+    RT_HIP(c, hipMemcpyAsync((char*)c->d_lf_stage + tri_bytes, &*lo, (size_t)n_ids * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(c, hipMemsetAsync(d_box, 0xff, 12, st));
+    RT_HIP(c, hipMemsetAsync(d_box + 3, 0, 12, st));
+    if (c->lf_timed)
+    {
+        for (hipEvent_t& e : c->lf_ev) if (!e) RT_HIP(c, hipEventCreate(&e));
+        RT_HIP(c, hipEventRecord(c->lf_ev[0], st));
+    }
+    k_light_follow_box<<<(count + 255) / 256, 256, 0, st>>>(c->d_tris, first, count, d_box);
+    LightFollowParams P;
+    P.n_records = (uint32_t)local_pixels(c);
+    P.first = first; P.count = count;
+    P.tris_old = c->d_tris; P.tris_new = (const float*)c->d_lf_stage;
+    P.ids = (const uint32_t*)((const char*)c->d_lf_stage + tri_bytes); P.n_ids = n_ids;
+    P.wide = c->d_wide; P.n_wide = c->d_wide ? (uint32_t)c->n_wide : 0u;
+    P.box = d_box; P.counters = c->d_lf_words;
+    const bool direct = (int64_t)n_ids <= (int64_t)c->lf_direct_max;
+    const unsigned grid = (P.n_records + BLOCK_THREADS - 1) / BLOCK_THREADS;
+    for (int k = 0; k < np && grid > 0u; ++k)
+    {
+        if (direct) k_light_follow<true><<<grid, BLOCK_THREADS, 0, st>>>(P, c->d_rec[phys[k]], c->d_rad[phys[k]]);
+        else k_light_follow<false><<<grid, BLOCK_THREADS, 0, st>>>(P, c->d_rec[phys[k]], c->d_rad[phys[k]]);
+        c->res_tag[phys[k]].light_rebased(c->moved.geo_gen);
+    }
+    RT_HIP(c, hipGetLastError());
+    if (c->lf_timed) RT_HIP(c, hipEventRecord(c->lf_ev[1], st));
+    c->lf_launched = true;
+    c->lf_last = np;
+    c->lf_stats0 += (uint64_t)np;
+    ++c->res_epoch; /* reservoir buffers written outside the staged frame */
+    return RT_OK;
+}
+
 int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uint32_t count)
 {
     RT_CHECK_CTX(c);
@@ -1525,6 +1603,8 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     if (lights.size() > ((size_t)1 << 26)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "more than 2^26 emissive triangles (the light table is addressed by 32-bit byte offsets)");
     if (c->refit_off.empty()) { const int rc = refit_topology(c); if (rc != RT_OK) return rc; }
     if (c->cost_at_build < 0.0) { const int rc = refit_first_update(c); if (rc != RT_OK) return rc; }
+    /* rt_temporal_light_motion: the old triangles and the old tree are still in place here */
+    { const int rc = light_follow_rebase(c, triangles, first, count); if (rc != RT_OK) return rc; }
     /* rt_temporal_motion / rt_denoise_temporal_motion: d_tv still holds the old vertices here. A history (a reservoir buffer for the
      * first, the denoiser's for the second) written since the last update by a consumer whose toggle is on carries the
      * generation this update ends: d_tv_prev is brought to it (it differs from d_tv over the old moved range only) and a new range
@@ -3321,6 +3401,66 @@ int rt_temporal_motion_stats(rt_ctx* c, uint64_t out[3])
     int rc = rt_sync(c);
     if (rc != RT_OK) return rc;
     RT_HIP(c, hipMemcpy(out, c->d_walk + 4 * WALK_MOTION, 3 * 8, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+/* r32. History samples that follow emitters moved by rt_scene_update (light_follow.h). Changes results, so not an
+ * rt_tuning key; counts as an option change and drops the look-ahead. Touches no reservoir buffer: the work happens in rt_scene_update. */
+int rt_temporal_light_motion(rt_ctx* c, int on)
+{
+    RT_CHECK_CTX(c);
+    if (!whole_frame(c))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_light_motion: strip contexts are not re-based");
+    RT_HIP(c, hipSetDevice(c->device));
+    if (on && !c->d_lf_words) RT_HIP(c, hipMalloc(&c->d_lf_words, LF_COUNTER_WORDS * 8 + 32));
+    if (on && !c->light_follow)
+    {
+        /* totals since the toggle went on */
+        RT_HIP(c, hipMemsetAsync(c->d_lf_words, 0, LF_COUNTER_WORDS * 8 + 32, c->stream));
+        c->lf_stats0 = 0;
+    }
+    c->light_follow = on != 0;
+    drop_look_ahead(c);
+    ++c->epoch;
+    return RT_OK;
+}
+int rt_temporal_light_motion_get(rt_ctx* c, int* on, int* last_update_rebased)
+{
+    RT_CHECK_CTX(c);
+    if (!on && !last_update_rebased) return RT_ERR_ARG;
+    if (on) *on = c->light_follow ? 1 : 0;
+    if (last_update_rebased) *last_update_rebased = c->lf_last;
+    return RT_OK;
+}
+int rt_temporal_light_motion_stats(rt_ctx* c, uint64_t out[5])
+{
+    RT_CHECK_CTX(c);
+    if (!out) return RT_ERR_ARG;
+    if (!c->d_lf_words) RT_FAIL(c, RT_ERR_STATE, "rt_temporal_light_motion first");
+    const int rc = rt_sync(c);
+    if (rc != RT_OK) return rc;
+    unsigned long long slots[LF_COUNTER_WORDS];
+    RT_HIP(c, hipMemcpy(slots, c->d_lf_words, sizeof(slots), hipMemcpyDeviceToHost));
+    out[0] = c->lf_stats0;
+    for (int k = 0; k < 4; ++k)
+    {
+        out[1 + k] = 0;
+        for (int s = 0; s < LF_COUNTER_SLOTS; ++s) out[1 + k] += slots[4 * s + k];
+    }
+    return RT_OK;
+}
+int rt_temporal_light_motion_timing(rt_ctx* c, float* ms)
+{
+    RT_CHECK_CTX(c);
+    if (!ms) return RT_ERR_ARG;
+    if (!c->lf_timed) RT_FAIL(c, RT_ERR_STATE, "rt_temporal_light_motion_timing: the last rt_scene_update did not run with the toggle and rt_timing_enable on");
+    *ms = 0.0f;
+    if (c->lf_launched) RT_HIP(c, hipEventElapsedTime(ms, c->lf_ev[0], c->lf_ev[1])); /* rt_scene_update synchronised behind them */
+    return RT_OK;
+}
+int rt_temporal_light_motion_path(rt_ctx* c, int direct_max)
+{
+    RT_CHECK_CTX(c);
+    c->lf_direct_max = direct_max < 0 ? LF_DIRECT_MAX_DEFAULT : direct_max;
     return RT_OK;
 }
 /* r31. The temporal merge with the 1/Z normalisation wherever its history is gathered by reprojection (temporal_unbiased.h, DESIGN.md

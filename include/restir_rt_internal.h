@@ -420,6 +420,32 @@ int rt_temporal_unbiased_get(rt_ctx* ctx, int* on);
  * out[3] = rays walked from a history's origin. An unbiased launch is a reprojecting launch and counts in
  * rt_temporal_reprojection_stats as one, each shaded pixel once. Synchronises. */
 int rt_temporal_unbiased_stats(rt_ctx* ctx, uint64_t out[4]);
+/* (r32) History samples that follow moved emitters (csrc/light_follow.h), default off: with it off every byte and
+ * every launch is what it was without the call. A history record stores its light sample as a world-space point, a normal and a
+ * radiance; after rt_scene_update moved the emitter it still points at where the emitter was. While the toggle is on,
+ * rt_scene_update(first, count) whose span holds an emissive triangle in the OLD array re-bases, before it overwrites anything, every
+ * physical reservoir buffer whose light samples describe the generation the update ends (written under it, or re-based to it by the
+ * update before: two updates with no frame between them are both followed; an older or untagged buffer is left alone): a shaded
+ * record with M > 0 whose sample lies on an old emissive triangle of the span (same normal and radiance bytes, on its plane and inside
+ * it within measured tolerances; the nearest plane, then the lowest index) keeps every byte if the triangle's 60 bytes do not change,
+ * becomes Reservoir{} (shaded bit kept) if the new triangle is non-emissive, degenerate or not finite, and is otherwise carried by
+ * its barycentrics: new point, normal, luminance and radiance, ucw times the ratio of the areas, own-visibility word cleared; M,
+ * w_sum, the origin and the visibility flag stay. No frame kernel changes. Independent of rt_temporal_reprojection,
+ * rt_temporal_motion, rt_temporal_unbiased, rt_spatial_unbiased, rt_light_sampling and the target-function options. The toggle
+ * changes rt_state_epoch and drops look-ahead work, touches no buffer. Strip contexts: RT_ERR_UNSUPPORTED. Not followed: visibility
+ * flags, strips, the denoisers, lights whose count or order changes, older histories. Not an rt_tuning key. */
+int rt_temporal_light_motion(rt_ctx* ctx, int on);
+/* *on: the toggle; *last_update_rebased: buffers the last rt_scene_update re-based (0: none). Either pointer may be null, not both */
+int rt_temporal_light_motion_get(rt_ctx* ctx, int* on, int* last_update_rebased);
+/* totals since the toggle went on: out[0] = buffers re-based, out[1] = records examined (shaded, M > 0), out[2] = records located on a
+ * triangle of the span, out[3] = records moved, out[4] = records emptied. RT_ERR_STATE before the toggle was ever on. Synchronises. */
+int rt_temporal_light_motion_stats(rt_ctx* ctx, uint64_t out[5]);
+/* device ms of the re-basing launches of the last rt_scene_update (0 if it re-based nothing) if the toggle and rt_timing_enable were
+ * on during it, else RT_ERR_STATE */
+int rt_temporal_light_motion_timing(rt_ctx* ctx, float* ms);
+/* which locate path an update takes (tests, measurements): spans of at most direct_max old lights loop over them, larger ones query
+ * the old tree; 0 = always the tree, negative = the default. Same bytes either way. */
+int rt_temporal_light_motion_path(rt_ctx* ctx, int direct_max);
 /* the alias table and the realised counts (thr / alias / K per light, light list order; any pointer may be null), for tests; n = the
  * scene's light count (RT_ERR_ARG otherwise); RT_ERR_STATE without a scene */
 int rt_light_table(rt_ctx* ctx, uint32_t* thr, uint32_t* alias, uint64_t* K, uint32_t n);

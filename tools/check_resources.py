@@ -59,6 +59,9 @@ BUDGET = [
     (r"^k_denoise_antilag_gather<", 0, 8),
     (r"^k_denoise_antilag$", 0, 8),
     (r"^k_denoise_temporal_motion", 0, 8),  # r25 rt_denoise_temporal_motion: the followed call's form, 41 VGPRs / 46 SGPRs (its sibling: 41 / 44)
+    # r32 rt_temporal_light_motion: the re-basing pass of rt_scene_update
+    (r"^k_light_follow<true>", 0, 8),    # loop over the span's lights: 49 VGPRs
+    (r"^k_light_follow<false>", 0, 7),   # point query on the old tree: 66 VGPRs, 14 336 B of LDS (the stack), 208 B of scratch (its overflow, as trace_wide)
 ]
 
 
