@@ -53,6 +53,7 @@ INTERNAL_EXPORTS = [
     "rt_denoise_temporal_antilag", "rt_denoise_temporal_antilag_get", "rt_denoise_temporal_antilag_timing",
     "rt_temporal_light_motion", "rt_temporal_light_motion_get", "rt_temporal_light_motion_stats", "rt_temporal_light_motion_timing",
     "rt_temporal_light_motion_path",
+    "rt_light_grid", "rt_light_grid_get", "rt_light_grid_build_ms", "rt_light_grid_table",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -60,6 +61,7 @@ RT_MG_TRANSPORT_RCCL, RT_MG_TRANSPORT_LOCAL, RT_MG_TRANSPORT_MIRROR, RT_MG_TRANS
 RT_MG_TRANSPORT_MIRROR_WIRE = 6
 RT_LIGHTS_UNIFORM, RT_LIGHTS_POWER = 0, 1  # rt_light_sampling
 LIGHT_SAMPLING = {"uniform": RT_LIGHTS_UNIFORM, "power": RT_LIGHTS_POWER}
+LIGHT_GRID_DEFAULT = (16, 64)  # rt_light_grid: cells per axis, clusters
 RT_MG_DENSE, RT_MG_ONE_LANE, RT_MG_SEPARATE_PACK = 1, 2, 4
 
 
@@ -226,6 +228,11 @@ def load_library(exp=False, path=None):
         L.rt_temporal_unbiased.argtypes = [vp, ci]
         L.rt_temporal_unbiased_get.argtypes = [vp, vp]
         L.rt_temporal_unbiased_stats.argtypes = [vp, vp]
+    if hasattr(L, "rt_light_grid"):  # r33; likewise
+        L.rt_light_grid.argtypes = [vp, ci, ci]
+        L.rt_light_grid_get.argtypes = [vp, vp, vp, vp]
+        L.rt_light_grid_build_ms.argtypes = [vp, vp]
+        L.rt_light_grid_table.argtypes = [vp] * 12 + [C.c_uint32, C.c_uint32]
     if hasattr(L, "rt_temporal_light_motion"):  # r32; likewise
         L.rt_temporal_light_motion.argtypes = [vp, ci]
         L.rt_temporal_light_motion_get.argtypes = [vp, vp, vp]
@@ -1055,6 +1062,40 @@ class Renderer:
         a = np.zeros(3, dtype=np.uint64)
         self._ck(self.L.rt_temporal_motion_stats(self.h, _p(a)))
         return dict(merged=int(a[0]), in_range=int(a[1]), valid=int(a[2]))
+
+    def light_grid(self, cells=None, clusters=None):
+        """rt_light_grid: distance-aware light selection for the candidates (DESIGN.md section 22). cells: grid cells per axis, 1..32;
+        clusters: spatial clusters of lights, 1..256; either left None takes its default (LIGHT_GRID_DEFAULT). cells=0 switches it
+        off; both None queries. Returns (cells, clusters, clusters built), (0, 0, 0) while off."""
+        if not hasattr(self.L, "rt_light_grid"):  # an older build through RT_LIB_PATH: the call is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_light_grid")
+        if cells is not None or clusters is not None:
+            cells = LIGHT_GRID_DEFAULT[0] if cells is None else int(cells)
+            clusters = LIGHT_GRID_DEFAULT[1] if clusters is None else int(clusters)
+            self._ck(self.L.rt_light_grid(self.h, cells, clusters))
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._ck(self.L.rt_light_grid_get(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def light_grid_build_ms(self):
+        """wall time of the last build of the light grid's tables (host tables and upload), ms"""
+        ms = C.c_float()
+        self._ck(self.L.rt_light_grid_build_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def light_grid_table(self):
+        """rt_light_grid_table: dict of bounds (lo, hi, inv), cluster_of, perm, run_start, run_thr / run_alias / run_K (sorted position)
+        and cell_thr / cell_alias / cell_K / cell_prob (cells^3 x clusters built, cell-major)"""
+        cells, _, B = self.light_grid()
+        n, m = self.scene_info()["lights"], cells ** 3 * B
+        u32, u64 = np.uint32, np.uint64
+        t = dict(bounds=np.zeros(9, np.float32), cluster_of=np.zeros(n, u32), perm=np.zeros(n, u32), run_start=np.zeros(B + 1, u32),
+                 run_thr=np.zeros(n, u32), run_alias=np.zeros(n, u32), run_K=np.zeros(n, u64), cell_thr=np.zeros(m, u32),
+                 cell_alias=np.zeros(m, u32), cell_K=np.zeros(m, u64), cell_prob=np.zeros(m, np.float32))
+        self._ck(self.L.rt_light_grid_table(self.h, *[_p(a) for a in t.values()], n, m))
+        b = t.pop("bounds")
+        t.update(lo=b[0:3].copy(), hi=b[3:6].copy(), inv=b[6:9].copy(), cells=cells, clusters=B)
+        return t
 
     def primary_launches(self):
         """launches so far that traced primary rays over the context's rows (rt_raycast, stage-0 raycasts, the one-launch stage 0,

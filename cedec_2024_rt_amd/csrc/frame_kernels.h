@@ -11,6 +11,9 @@
 #include "occluder_hint.h"
 #include "rt_device.h"
 #include "light_alias.h"
+#include "light_grid.h"
+
+#include <type_traits>
 #include "temporal_reproject.h"
 #include "temporal_motion.h"
 #include "temporal_unbiased.h"
@@ -144,6 +147,13 @@ struct SceneView
     /* rt_light_sampling = RT_LIGHTS_POWER, the candidates' launches only (light_alias.h): one slot per light, and `lights` is then the
      * table whose pdf is the realised one; nullptr otherwise */
     const AliasSlot* __restrict__ light_alias;
+};
+/* rt_light_grid: what k_generate_candidate<.., GRID> takes in SceneView's place (light_grid.h): the cells' and the runs' tables beside
+ * it; `lights` and `light_ke` are then the tables in the runs' position order, the record's pdf being the run's factor. A type of its
+ * own, so that no other kernel's arguments change. */
+struct SceneViewGrid : SceneView
+{
+    GridView grid;
 };
 
 #ifndef RT_TILE_W
@@ -687,13 +697,16 @@ RT_DEV void wave_gather_records(const float4* q, float4* s_wave, const int lane,
 /* POWER (r21, rt_light_sampling): the light of a candidate comes from the alias table (light_alias.h) instead of
  * the uniform index: a fifth draw `ra` directly after rv0, one 8-byte slot gathered per lane, and S.lights holds the realised pdf. A
  * template parameter: the kernels of the uniform mode are compiled from the text they had. */
+/* GRID (r33, rt_light_grid): the light comes from the two-level tables of light_grid.h: the cell of the pixel's
+ * surface point once per pixel, then per candidate the draws rv0, ra, rc, rb and three dependent gathers (cell slot, run, run slot)
+ * where POWER has its one; the pdf is the cell's factor times the record's. A template parameter for the reason POWER is one. */
 /* REPROJECT (r23, rt_temporal_reprojection): the history record comes from load_prev_reprojected instead of the own pixel. A template
  * parameter for the reason POWER is one; launched only where the history buffer was written under another camera. */
 /* MOTION (r24, rt_temporal_motion): the history record comes from load_prev_motion, which follows triangles moved by rt_scene_update;
  * on top of REPROJECT, launched only where the history buffer is one geometry generation old (restir_rt.hip: history_motion). */
-template <bool FUSE_TEMPORAL, bool SHADOWED, bool DEFER = false, bool PIPE = false, bool WS = false, bool RAYCAST = false, bool POWER = false, bool REPROJECT = false, bool MOTION = false>
+template <bool FUSE_TEMPORAL, bool SHADOWED, bool DEFER = false, bool PIPE = false, bool WS = false, bool RAYCAST = false, bool POWER = false, bool REPROJECT = false, bool MOTION = false, bool GRID = false>
 __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED ? RT_GENERATE_SH_WAVES : RT_TRACE_WAVES)) void k_generate_candidate(
-    SceneView S, FrameParams P, const float4* __restrict__ g0, const float4* __restrict__ g1,
+    typename std::conditional<GRID, SceneViewGrid, SceneView>::type S, FrameParams P, const float4* __restrict__ g0, const float4* __restrict__ g1,
     const float4* __restrict__ prev_rec, const float4* __restrict__ prev_rad, float4* __restrict__ out_rec,
     float4* __restrict__ out_rad, uint32_t* __restrict__ vis_queue = nullptr, unsigned int* __restrict__ vis_count = nullptr,
     float4* __restrict__ vis_w = nullptr, float4* __restrict__ g0_w = nullptr, float4* __restrict__ g1_w = nullptr,
@@ -703,6 +716,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     static_assert(!RAYCAST || (WS && FUSE_TEMPORAL && !SHADOWED && !DEFER && !PIPE), "primary rays in the product's fused kernel only");
     static_assert(!REPROJECT || (FUSE_TEMPORAL && !DEFER && !PIPE), "reprojected history: the product's fused kernels only");
     static_assert(!MOTION || REPROJECT, "history that follows moved geometry: a form of the reprojected one");
+    static_assert(!GRID || (!POWER && !DEFER && !PIPE), "light grid: in place of the alias table, in the product's forms only");
     RT_WAVE_CLOCK(P);
     constexpr bool LATE = WS && FUSE_TEMPORAL && !SHADOWED && !DEFER; /* the visibility-reuse ray after the temporal merge */
     /* shadowed target: every lane stays through the RIS loop, so that the wavefront can fetch its light records together */
@@ -747,6 +761,13 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     const f3 sp = F3(G0.x, G0.y, G0.z), sn = F3(G1.x, G1.y, G1.z);
     PCG rng = pcg_init(hashPCG4((uint32_t)x, (uint32_t)yi, (uint32_t)P.frame, 0u), 0);
     const float fL = (float)(size_t)P.n_lights;
+    uint32_t gcell = 0u; /* GRID: the cell of the surface point */
+    if constexpr (GRID) gcell = grid_cell_of(S.grid.b, sp);
+    /* GRID: the pdf and its reciprocal for div_by from the cell's factor and the record's pdf, as k_light_table makes L[3].w */
+    auto grid_pdf_of = [](float cell_prob, float rec_pdf, float& pdf, float& r1) {
+        pdf = grid_pdf(cell_prob, rec_pdf);
+        r1 = div_den_ok(pdf) ? rcp_refined(pdf) : as_float(0x7fc00000u);
+    };
     int sel = -1;
     float sel_bx = 0.0f, sel_by = 0.0f; /* warped barycentrics of the selected candidate */
     /* RIS loop of the work-sharing kernel (every lane stays to the end): the wavefront fetches the 64 light records of a round
@@ -765,19 +786,25 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
          * requested before candidate i's arithmetic, which then runs with the fetch in flight (the record of candidate i
          * is in registers by then: one 4-KB image per wavefront is enough). Same draws in the same order. */
         float bx_n = 0.0f, by_n = 0.0f, u_n = 0.0f;
+        float cp_n = 0.0f; /* GRID: the cell's factor of the requested candidate's pdf */
         uint32_t nth_n = 0u;
         auto draw_and_request = [&]() {
             if (act)
             {
                 const float rv0 = rng.uniformf_chained();
-                float ra = 0.0f;
-                if constexpr (POWER) ra = rng.uniformf_chained();
+                float ra = 0.0f, rc = 0.0f, rb = 0.0f;
+                if constexpr (POWER || GRID) ra = rng.uniformf_chained();
+                if constexpr (GRID) { rc = rng.uniformf_chained(); rb = rng.uniformf_chained(); }
                 bx_n = rng.uniformf_chained();
                 by_n = rng.uniformf_chained();
                 u_n = rng.uniformf_chained();
+                if constexpr (GRID) nth_n = grid_select(S.grid, gcell, rv0, ra, rc, rb, cp_n);
+                else
+                {
                 nth_n = (uint32_t)(rv0 * fL);
                 if (nth_n == (uint32_t)P.n_lights) nth_n = (uint32_t)P.n_lights - 1u;
                 if constexpr (POWER) nth_n = light_select_slot(S.light_alias[nth_n], nth_n, ra);
+                }
             }
             wave_gather_request_at(S.lights, nth_n, s_img, lane);
         };
@@ -789,6 +816,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
             float bx = bx_n, by = by_n;
             const float u = u_n;
             const uint32_t nth = nth_n;
+            const float cp = cp_n;
             if (i + 1 < P.ris_sample_count) draw_and_request();
             if (act)
             {
@@ -796,7 +824,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
                 warp_unit_triangle(bx, by);
                 const f3 lp = (1.0f - bx - by) * v0 + bx * v1 + by * v2;
                 const f3 ln = F3(L3n.x, L3n.y, L3n.z);
-                const float weight = ris_weight(sp, sn, lp, ln, L2.y, L2.z, L3n.w); /* p_hat (unshadowed always, :104) / pdf = 1/L * 1/area (:98-99) */
+                float light_pdf = L2.z, r1_pdf = L3n.w;
+                if constexpr (GRID) grid_pdf_of(cp, L2.z, light_pdf, r1_pdf);
+                const float weight = ris_weight(sp, sn, lp, ln, L2.y, light_pdf, r1_pdf); /* p_hat (unshadowed always, :104) / pdf = 1/L * 1/area (:98-99) */
                 r.w_sum += weight;
                 r.M += 1;
                 if (reservoir_accept(u, weight, r.w_sum))
@@ -808,18 +838,23 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
 #else
         for (int i = 0; i < P.ris_sample_count; ++i)
         {
-            float bx = 0.0f, by = 0.0f;
+            float bx = 0.0f, by = 0.0f, cp = 0.0f;
             uint32_t nth = 0u;
             if (act)
             {
                 const float rv0 = rng.uniformf();
-                float ra = 0.0f;
-                if constexpr (POWER) ra = rng.uniformf();
+                float ra = 0.0f, rc = 0.0f, rb = 0.0f;
+                if constexpr (POWER || GRID) ra = rng.uniformf();
+                if constexpr (GRID) { rc = rng.uniformf(); rb = rng.uniformf(); }
                 bx = rng.uniformf();
                 by = rng.uniformf();
+                if constexpr (GRID) nth = grid_select(S.grid, gcell, rv0, ra, rc, rb, cp);
+                else
+                {
                 nth = (uint32_t)(rv0 * fL);
                 if (nth == (uint32_t)P.n_lights) nth = (uint32_t)P.n_lights - 1u;
                 if constexpr (POWER) nth = light_select_slot(S.light_alias[nth], nth, ra);
+                }
             }
             float4 L0, L1, L2, L3n;
             wave_gather_records_at(S.lights, nth, s_img, lane, L0, L1, L2, L3n);
@@ -830,7 +865,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
                 const f3 lp = (1.0f - bx - by) * v0 + bx * v1 + by * v2;
                 const f3 ln = F3(L3n.x, L3n.y, L3n.z);
                 const float p_hat = target_unshadowed(sp, sn, lp, ln, L2.y); /* unshadowed always (:104) */
-                const float weight = div_pdf(p_hat, L2.z, L3n.w);           /* 1/L * 1/area (:98-99) */
+                float light_pdf = L2.z, r1_pdf = L3n.w;
+                if constexpr (GRID) grid_pdf_of(cp, L2.z, light_pdf, r1_pdf);
+                const float weight = div_pdf(p_hat, light_pdf, r1_pdf);     /* 1/L * 1/area (:98-99) */
                 const float u = rng.uniformf();
                 r.w_sum += weight;
                 r.M += 1;
@@ -898,16 +935,18 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
     else
     for (int i = 0; i < P.ris_sample_count; ++i)
     {
-        /* draw order rv0, rv1, rv2, u: left-to-right argument evaluation (hipcc); POWER: rv0, ra, rv1, rv2, u */
+        /* draw order rv0, rv1, rv2, u: left-to-right argument evaluation (hipcc); POWER: rv0, ra, rv1, rv2, u; GRID: rv0, ra, rc, rb, rv1, rv2, u */
         const float rv0 = rng.uniformf();
-        float ra = 0.0f;
-        if constexpr (POWER) ra = rng.uniformf();
+        float ra = 0.0f, rc = 0.0f, rb = 0.0f, cp = 0.0f;
+        if constexpr (POWER || GRID) ra = rng.uniformf();
+        if constexpr (GRID) { rc = rng.uniformf(); rb = rng.uniformf(); }
         float bx = rng.uniformf();
         float by = rng.uniformf();
         /* common/core.hpp:261-285 */
         uint32_t nth = (uint32_t)(rv0 * fL);
         if (nth == (uint32_t)P.n_lights) nth = (uint32_t)P.n_lights - 1u;
         if constexpr (POWER) nth = light_select_slot(S.light_alias[nth], nth, ra);
+        if constexpr (GRID) nth = grid_select(S.grid, gcell, rv0, ra, rc, rb, cp);
         /* 64-B light record: vertices + luminance(Ke) + pdf + the geometric normal (the reference's
          * exact expression, common/core.hpp:50-55, evaluated once at scene set: the loop is bound by
          * vector-ALU issue and a normalize costs 3 IEEE divisions + a square root); Ke is fetched
@@ -920,9 +959,10 @@ __global__ __launch_bounds__(TRACE_BLOCK, WS ? RT_GENERATE_WS_WAVES : (SHADOWED 
         const float4 L3n = L[3];
         const f3 ln = F3(L3n.x, L3n.y, L3n.z);
         const float lum = L2.y;
-        const float light_pdf = L2.z; /* 1/L * 1/area (:98-99) */
+        float light_pdf = L2.z, r1_pdf = L3n.w; /* 1/L * 1/area (:98-99) */
+        if constexpr (GRID) grid_pdf_of(cp, L2.z, light_pdf, r1_pdf);
         const float p_hat = target_unshadowed(sp, sn, lp, ln, lum); /* unshadowed always (:104) */
-        const float weight = div_pdf(p_hat, light_pdf, L3n.w);
+        const float weight = div_pdf(p_hat, light_pdf, r1_pdf);
         const float u = rng.uniformf();
         /* common/reservoir.hpp:22-29 */
         r.w_sum += weight;

@@ -201,6 +201,21 @@ struct rt_ctx
     bool alias_ok = false; /* some light has q > 0 */
     float4* d_lights_power = nullptr;
     AliasSlot* d_alias = nullptr;
+    /* rt_light_grid (light_grid.h): the request (0 cells = off), and only while it is on: a host copy of the
+     * scene's triangles (the bounds need every vertex, the runs the lights' vertices; rt_scene_update passes its span only), the
+     * tables as the host built them and their device copies with a light table and a Ke table in the runs' position order */
+    int grid_cells = 0, grid_clusters = 0;
+    std::vector<float> h_grid_tris; /* 15 floats per triangle */
+    LightGrid h_grid;
+    bool grid_built = false;
+    AliasSlot* d_grid_cells = nullptr;
+    float* d_grid_cell_prob = nullptr;
+    GridRun* d_grid_runs = nullptr;
+    AliasSlot* d_grid_run_slots = nullptr;
+    uint32_t* d_grid_cluster_of = nullptr;
+    float4* d_lights_grid = nullptr;
+    float4* d_light_ke_grid = nullptr;
+    float grid_build_ms = 0.0f; /* the last build, host tables and upload */
     uint32_t* d_light_ids = nullptr;
     uint32_t* d_refit_list = nullptr;
     float* d_refit_box = nullptr;
@@ -580,8 +595,26 @@ int rt_create(int device, int width, int height, int row_begin, int row_end, int
     return RT_OK;
 }
 
+/* rt_light_grid's device tables */
+static void free_light_grid_tables(rt_ctx* c)
+{
+    hipFree(c->d_grid_cells); hipFree(c->d_grid_cell_prob); hipFree(c->d_grid_runs); hipFree(c->d_grid_run_slots); hipFree(c->d_grid_cluster_of);
+    hipFree(c->d_lights_grid); hipFree(c->d_light_ke_grid);
+    c->d_grid_cells = nullptr; c->d_grid_cell_prob = nullptr; c->d_grid_runs = nullptr; c->d_grid_run_slots = nullptr; c->d_grid_cluster_of = nullptr;
+    c->d_lights_grid = nullptr; c->d_light_ke_grid = nullptr;
+    c->grid_built = false;
+}
+/* ... and the host state with them; the request (grid_cells, grid_clusters) stays */
+static void free_light_grid(rt_ctx* c)
+{
+    free_light_grid_tables(c);
+    c->h_grid = LightGrid();
+    std::vector<float>().swap(c->h_grid_tris);
+    c->grid_built = false;
+}
 static void free_scene(rt_ctx* c)
 {
+    free_light_grid(c);
     hipFree(c->d_tris); hipFree(c->d_tv); hipFree(c->d_nodes); hipFree(c->d_trimat); hipFree(c->d_lights); hipFree(c->d_light_ke); hipFree(c->d_wide);
     hipFree(c->d_lights_power); hipFree(c->d_alias);
     c->d_lights_power = nullptr; c->d_alias = nullptr;
@@ -1272,6 +1305,66 @@ static int build_light_alias(rt_ctx* c, std::vector<float>& w, const uint32_t* d
     return RT_OK;
 }
 
+/* The tables of rt_light_grid (host, light_grid.h) from the host copy of the scene's triangles, the light list `lights` and the kept
+ * weights (after build_light_alias), uploaded with a light table and a Ke table in the runs' position order: k_light_table over the
+ * permuted ids, its pdf the run's factor. Reads d_tris on `st` (behind the copies the caller enqueued there) and waits for `st`. */
+static int build_light_grid(rt_ctx* c, const std::vector<uint32_t>& lights, hipStream_t st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t L = (uint32_t)lights.size();
+    free_light_grid_tables(c);
+    LightGrid& g = c->h_grid;
+    grid_build(g, c->h_grid_tris.data(), 15, (size_t)c->n_tris, lights.data(), c->h_light_w.data(), L, c->grid_cells, c->grid_clusters);
+    if (L > 0)
+    {
+        const size_t n = g.cell_slots();
+        const uint32_t B = g.B;
+        std::vector<float> cell_prob(n), run_prob(L);
+        std::vector<uint32_t> ids(L);
+        for (size_t k = 0; k < n; ++k) cell_prob[k] = light_select_prob(g.cell_K[k], B);
+        for (uint32_t r = 0; r < B; ++r)
+            for (uint32_t p = g.runs[r].start; p < g.runs[r].start + g.runs[r].n; ++p)
+            {
+                run_prob[p] = light_select_prob(g.run_K[p], g.runs[r].n);
+                ids[p] = lights[g.perm[p]];
+            }
+        uint32_t* d_ids = nullptr;
+        float* d_prob = nullptr;
+        hipError_t e = hipMalloc(&c->d_grid_cells, n * sizeof(AliasSlot));
+        if (e == hipSuccess) e = hipMalloc(&c->d_grid_cell_prob, n * 4);
+        if (e == hipSuccess) e = hipMalloc(&c->d_grid_runs, (size_t)B * sizeof(GridRun));
+        if (e == hipSuccess) e = hipMalloc(&c->d_grid_run_slots, (size_t)L * sizeof(AliasSlot));
+        if (e == hipSuccess) e = hipMalloc(&c->d_grid_cluster_of, (size_t)L * 4);
+        if (e == hipSuccess) e = hipMalloc(&c->d_lights_grid, (size_t)L * 16 * RT_LIGHT_STRIDE);
+        if (e == hipSuccess) e = hipMalloc(&c->d_light_ke_grid, (size_t)L * 16);
+        if (e == hipSuccess) e = hipMalloc(&d_ids, (size_t)L * 4);
+        if (e == hipSuccess) e = hipMalloc(&d_prob, (size_t)L * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_grid_cells, g.cells.data(), n * sizeof(AliasSlot), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_grid_cell_prob, cell_prob.data(), n * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_grid_runs, g.runs.data(), (size_t)B * sizeof(GridRun), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_grid_run_slots, g.run_slots.data(), (size_t)L * sizeof(AliasSlot), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_grid_cluster_of, g.cluster_of.data(), (size_t)L * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_ids, ids.data(), (size_t)L * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_prob, run_prob.data(), (size_t)L * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+        {
+            k_light_table<<<((int)L + 255) / 256, 256, 0, st>>>((int)L, d_ids, c->d_tris, c->d_lights_grid, c->d_light_ke_grid, d_prob);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st); /* the vectors above are host memory */
+        hipFree(d_ids); hipFree(d_prob);
+        if (e != hipSuccess)
+        {
+            const std::string why = hipGetErrorString(e); /* an allocation that failed (about 100 MB at 32 cells and 256 clusters) ends here too */
+            free_light_grid_tables(c);
+            RT_FAIL(c, RT_ERR_HIP, "rt_light_grid: tables of %d^3 cells x %u clusters: %s", c->grid_cells, B, why.c_str());
+        }
+    }
+    c->grid_built = true;
+    c->grid_build_ms = (float)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() * 1e-3f;
+    return RT_OK;
+}
+
 int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
 {
     RT_CHECK_CTX(c);
@@ -1323,6 +1416,13 @@ int rt_scene_set(rt_ctx* c, const rt_triangle* triangles, uint32_t count)
         RT_HIP(c, hipStreamSynchronize(c->stream));
         hipFree(d_ids);
         if (ra != RT_OK) return ra;
+    }
+    if (c->grid_cells > 0)
+    {
+        c->h_grid_tris.resize((size_t)n * 15);
+        memcpy(c->h_grid_tris.data(), triangles, (size_t)n * 60);
+        const int rg = build_light_grid(c, lights, c->stream);
+        if (rg != RT_OK) return rg;
     }
     const int rc = build_bvh(c, triangles, n);
     if (rc != RT_OK) return rc;
@@ -1642,6 +1742,24 @@ int rt_scene_update(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uin
     {
         const int ra = build_light_alias(c, light_w, c->d_light_ids, lights.size() != c->h_lights.size(), st);
         if (ra != RT_OK) return ra;
+    }
+    /* rt_light_grid: the span goes into the host copy; the tables are rebuilt if the span holds or held a light (weights, vertices or
+     * the list can have changed) or the scene's bounds moved, and stay otherwise */
+    if (c->grid_cells > 0)
+    {
+        memcpy(c->h_grid_tris.data() + 15 * (size_t)first, triangles, (size_t)count * 60);
+        bool rebuild = span_has_light || lights != c->h_lights || !c->grid_built;
+        if (!rebuild)
+        {
+            LightGrid b;
+            grid_build_bounds(b, c->h_grid_tris.data(), 15, (size_t)c->n_tris, c->grid_cells);
+            rebuild = memcmp(b.lo, c->h_grid.lo, 12) != 0 || memcmp(b.hi, c->h_grid.hi, 12) != 0;
+        }
+        if (rebuild)
+        {
+            const int rg = build_light_grid(c, lights, st);
+            if (rg != RT_OK) return rg;
+        }
     }
     c->n_lights = (int)lights.size();
     /* refit: the pad's bounds grown by the span, then the inner records level by level, deepest first */
@@ -2170,7 +2288,18 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
     int* hints = nullptr;
     if (staged) { const int rc = staged_hints(c, &hints); if (rc != RT_OK) return rc; }
     SceneView S = make_scene(c);
-    const bool power = c->light_mode == RT_LIGHTS_POWER && c->opt.ris_sample_count > 0;
+    /* rt_light_grid decides the selection while it is on; rt_light_sampling's mode is kept and applies again when it goes off */
+    const bool grid = c->grid_cells > 0 && c->opt.ris_sample_count > 0;
+    SceneViewGrid SG;
+    if (grid)
+    {
+        if (!c->grid_built || !c->h_grid.ok) RT_FAIL(c, RT_ERR_STATE, "rt_light_grid: no light of the scene has a positive finite area x luminance");
+        S.lights = c->d_lights_grid;
+        S.light_ke = c->d_light_ke_grid;
+    }
+    static_cast<SceneView&>(SG) = S;
+    SG.grid = GridView{c->h_grid.bounds(), c->h_grid.B, c->d_grid_cells, c->d_grid_cell_prob, c->d_grid_runs, c->d_grid_run_slots}; /* null while off */
+    const bool power = !grid && c->light_mode == RT_LIGHTS_POWER && c->opt.ris_sample_count > 0;
     if (power)
     {
         if (!c->alias_ok) RT_FAIL(c, RT_ERR_STATE, "rt_light_sampling: no light of the scene has a positive finite area x luminance");
@@ -2204,9 +2333,11 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
     tag_reservoir(c, dst_phys);
     const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
     const int g = trace_grid(c, L);
-    /* every form of the kernel in both light samplings: <fused, shadowed, deferred, pipelined, work-sharing, with primary rays> */
+    /* every form of the kernel in both light samplings: <fused, shadowed, deferred, pipelined, work-sharing, with primary rays>; the
+     * light grid in the product's forms (the [exp] deferred and pipelined forms refuse it below) */
 #define GEN_LAUNCH(FT, SH, DF, PP, WS_, RC, ...)                                                                                  \
     do {                                                                                                                          \
+        if (grid && !(DF) && !(PP)) { const SceneViewGrid& S = SG; k_generate_candidate<FT, SH, false, false, WS_, RC, false, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); break; } \
         if (power) k_generate_candidate<FT, SH, DF, PP, WS_, RC, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);              \
         else k_generate_candidate<FT, SH, DF, PP, WS_, RC><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);                          \
     } while (0)
@@ -2214,12 +2345,16 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
 #define GEN_LAUNCH_RP(SH, WS_, RC, ...)                                                                                           \
     do {                                                                                                                          \
         if (!rp) GEN_LAUNCH(true, SH, false, false, WS_, RC, __VA_ARGS__);                                                         \
+        else if (mo && grid) { const SceneViewGrid& S = SG; k_generate_candidate<true, SH, false, false, WS_, RC, false, true, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); } \
+        else if (grid) { const SceneViewGrid& S = SG; k_generate_candidate<true, SH, false, false, WS_, RC, false, true, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); } \
         else if (mo && power) k_generate_candidate<true, SH, false, false, WS_, RC, true, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
         else if (mo) k_generate_candidate<true, SH, false, false, WS_, RC, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
         else if (power) k_generate_candidate<true, SH, false, false, WS_, RC, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
         else k_generate_candidate<true, SH, false, false, WS_, RC, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);     \
     } while (0)
 #ifdef RT_EXPERIMENTS
+    if (grid && fuse && !sh && (c->tune_defer_vis || c->tune_ris_pipe))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_light_grid: the [exp] stage-0 variants (rt_tuning keys 11 and 12) are not built for the light grid");
     if (rp && fuse && ((!sh && c->tune_defer_vis) || (!sh && c->tune_ris_pipe)))
         RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_reprojection / rt_temporal_motion: the [exp] stage-0 variants (rt_tuning keys 11 and 12) gather their history from the own pixel only");
     if (fuse && !sh && c->tune_defer_vis)
@@ -3526,6 +3661,113 @@ int rt_light_table(rt_ctx* c, uint32_t* thr, uint32_t* alias, uint64_t* K, uint3
         if (alias) alias[i] = c->h_alias[i].alias;
         if (K) K[i] = c->h_alias_K[i];
     }
+    return RT_OK;
+}
+/* Distance-aware light selection (light_grid.h). Like rt_light_sampling: changes results, so not an rt_tuning
+ * key; counts as an option change and drops the look-ahead; touches no reservoir buffer. With a scene present the tables are built
+ * here, from the device's triangles; otherwise by rt_scene_set. */
+int rt_light_grid(rt_ctx* c, int cells_per_axis, int clusters)
+{
+    RT_CHECK_CTX(c);
+    if (cells_per_axis != 0)
+    {
+        if (cells_per_axis < 1 || cells_per_axis > kGridMaxCells || clusters < 1 || clusters > kGridMaxClusters)
+            RT_FAIL(c, RT_ERR_ARG, "rt_light_grid: %d cells per axis (1..%d) and %d clusters (1..%d)", cells_per_axis, kGridMaxCells, clusters, kGridMaxClusters);
+        if (!whole_frame(c)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_light_grid: not built for strip contexts");
+    }
+    else clusters = 0;
+    if (cells_per_axis != c->grid_cells || clusters != c->grid_clusters)
+    {
+        if (c->has_scene)
+        {
+            /* every stream that may still read the tables, as rt_scene_set */
+            RT_HIP(c, hipSetDevice(c->device));
+            { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
+            if (c->own_stream && c->own_stream != c->stream) RT_HIP(c, hipStreamSynchronize(c->own_stream));
+            if (c->aux_stream) RT_HIP(c, hipStreamSynchronize(c->aux_stream));
+        }
+        if (cells_per_axis == 0) free_light_grid(c);
+        else if (c->has_scene && c->n_tris > 0)
+        {
+            if (c->h_grid_tris.size() != (size_t)c->n_tris * 15)
+            {
+                c->h_grid_tris.resize((size_t)c->n_tris * 15);
+                RT_HIP(c, hipMemcpy(c->h_grid_tris.data(), c->d_tris, (size_t)c->n_tris * 60, hipMemcpyDeviceToHost));
+            }
+            const int old_cells = c->grid_cells, old_clusters = c->grid_clusters;
+            c->grid_cells = cells_per_axis; c->grid_clusters = clusters;
+            const int rg = build_light_grid(c, c->h_lights, c->stream);
+            if (rg != RT_OK)
+            {
+                /* nothing changes: the old tables are gone, so the old request is built again (or the grid is off) */
+                c->grid_cells = old_cells; c->grid_clusters = old_clusters;
+                const std::string why = c->err;
+                if (old_cells == 0 || build_light_grid(c, c->h_lights, c->stream) != RT_OK) { c->grid_cells = c->grid_clusters = 0; free_light_grid(c); }
+                c->err = why;
+                return rg;
+            }
+        }
+        c->grid_cells = cells_per_axis; c->grid_clusters = clusters;
+    }
+    drop_look_ahead(c);
+    ++c->epoch;
+    return RT_OK;
+}
+int rt_light_grid_get(rt_ctx* c, int* cells_per_axis, int* clusters, int* clusters_built)
+{
+    RT_CHECK_CTX(c);
+    if (cells_per_axis) *cells_per_axis = c->grid_cells;
+    if (clusters) *clusters = c->grid_clusters;
+    if (clusters_built) *clusters_built = c->grid_built ? (int)c->h_grid.B : 0;
+    return RT_OK;
+}
+int rt_light_grid_build_ms(rt_ctx* c, float* ms)
+{
+    RT_CHECK_CTX(c);
+    if (!ms) return RT_ERR_ARG;
+    *ms = c->grid_build_ms;
+    return RT_OK;
+}
+int rt_light_grid_table(rt_ctx* c, float bounds[9], uint32_t* cluster_of, uint32_t* perm, uint32_t* run_start, uint32_t* run_thr, uint32_t* run_alias,
+                        uint64_t* run_K, uint32_t* cell_thr, uint32_t* cell_alias, uint64_t* cell_K, float* cell_prob, uint32_t n_lights,
+                        uint32_t n_cell_slots)
+{
+    RT_CHECK_CTX(c);
+    if (!c->has_scene) RT_FAIL(c, RT_ERR_STATE, "rt_light_grid_table before rt_scene_set");
+    if (c->grid_cells == 0 || !c->grid_built) RT_FAIL(c, RT_ERR_STATE, "rt_light_grid_table: the light grid is off");
+    const LightGrid& g = c->h_grid;
+    const size_t n = g.L ? g.cell_slots() : 0;
+    if (n_lights != g.L || (size_t)n_cell_slots != n)
+        RT_FAIL(c, RT_ERR_ARG, "rt_light_grid_table: %u lights and %u cell slots asked for, the grid has %u and %zu", n_lights, n_cell_slots, g.L, n);
+    if (bounds)
+        for (int a = 0; a < 3; ++a) { bounds[a] = g.lo[a]; bounds[3 + a] = g.hi[a]; bounds[6 + a] = g.inv[a]; }
+    if (perm) memcpy(perm, g.perm.data(), (size_t)g.L * 4);
+    for (uint32_t p = 0; p < g.L && run_K; ++p) run_K[p] = g.run_K[p];
+    for (size_t k = 0; k < n && cell_K; ++k) cell_K[k] = g.cell_K[k];
+    if (g.L == 0) { if (run_start) run_start[0] = 0u; return RT_OK; }
+    /* everything the device holds comes back from the device */
+    { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
+    if (cluster_of) RT_HIP(c, hipMemcpy(cluster_of, c->d_grid_cluster_of, (size_t)g.L * 4, hipMemcpyDeviceToHost));
+    if (run_start)
+    {
+        std::vector<GridRun> runs(g.B);
+        RT_HIP(c, hipMemcpy(runs.data(), c->d_grid_runs, (size_t)g.B * sizeof(GridRun), hipMemcpyDeviceToHost));
+        for (uint32_t r = 0; r < g.B; ++r) run_start[r] = runs[r].start;
+        run_start[g.B] = runs[g.B - 1].start + runs[g.B - 1].n;
+    }
+    if (run_thr || run_alias)
+    {
+        std::vector<AliasSlot> t(g.L);
+        RT_HIP(c, hipMemcpy(t.data(), c->d_grid_run_slots, (size_t)g.L * sizeof(AliasSlot), hipMemcpyDeviceToHost));
+        for (uint32_t p = 0; p < g.L; ++p) { if (run_thr) run_thr[p] = t[p].thr; if (run_alias) run_alias[p] = t[p].alias; }
+    }
+    if (cell_thr || cell_alias)
+    {
+        std::vector<AliasSlot> t(n);
+        RT_HIP(c, hipMemcpy(t.data(), c->d_grid_cells, n * sizeof(AliasSlot), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < n; ++k) { if (cell_thr) cell_thr[k] = t[k].thr; if (cell_alias) cell_alias[k] = t[k].alias; }
+    }
+    if (cell_prob) RT_HIP(c, hipMemcpy(cell_prob, c->d_grid_cell_prob, n * 4, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 int rt_primary_launches(rt_ctx* c, uint64_t* n)

@@ -449,6 +449,36 @@ int rt_temporal_light_motion_path(rt_ctx* ctx, int direct_max);
 /* the alias table and the realised counts (thr / alias / K per light, light list order; any pointer may be null), for tests; n = the
  * scene's light count (RT_ERR_ARG otherwise); RT_ERR_STATE without a scene */
 int rt_light_table(rt_ctx* ctx, uint32_t* thr, uint32_t* alias, uint64_t* K, uint32_t n);
+/* Distance-aware light selection of the ReSTIR candidates (csrc/light_grid.h), default off: every byte is then
+ * what it was without the call. On: the emissive triangles are grouped into min(clusters, lights) spatial clusters, a uniform grid of
+ * cells_per_axis^3 cells over the scene's bounding box holds per cell an alias table over the clusters (cluster power over squared
+ * distance), and a candidate draws a cluster from the table of its surface point's cell and a light from the cluster's own
+ * power-proportional alias table, with three more random numbers per candidate than the reference (rv0, ra, rc, rb, bx, by, u). The pdf
+ * divided by is the product of the two probabilities the tables realise, so the estimate keeps its expectation. Built on the host at
+ * rt_scene_set, at an rt_scene_update whose span holds or held an emissive triangle or that moves the scene's bounds, and at this
+ * call if a scene is present; while it is off nothing is built, kept or uploaded. cells_per_axis 1..32 and clusters 1..256 (suggested:
+ * 16 and 64); cells_per_axis = 0 (clusters: anything) switches it off; anything else: RT_ERR_ARG, and nothing changes. While it is on
+ * it decides the selection: rt_light_sampling's mode is kept, reported by its getter, and applies again when the grid goes off. A
+ * property of whole-frame contexts (strips: RT_ERR_UNSUPPORTED), set before or after the scene; applies to rt_generate_candidate,
+ * rt_frame and rt_frame_stage*, not to rt_path_trace. The call changes rt_state_epoch and drops look-ahead work, touches no reservoir
+ * buffer and needs no new temporal history. A scene in which no light has a positive finite area x luminance: RT_ERR_STATE from the
+ * launching call while the grid is on and ris_sample_count > 0. The experiments library's deferred and pipelined stage-0 forms
+ * (rt_tuning keys 11 and 12) refuse it with RT_ERR_UNSUPPORTED. Tables that do not fit the device: RT_ERR_HIP, the grid stays as it was.
+ * Not an rt_tuning key: tuning keys never change results. */
+int rt_light_grid(rt_ctx* ctx, int cells_per_axis, int clusters);
+/* the request as set (0, 0 = off) and the clusters the tables were built with (min(clusters, lights); 0 = no tables); any pointer may be null */
+int rt_light_grid_get(rt_ctx* ctx, int* cells_per_axis, int* clusters, int* clusters_built);
+/* wall time of the last table build (host tables and upload), ms; 0 before the first */
+int rt_light_grid_build_ms(rt_ctx* ctx, float* ms);
+/* The grid's tables, for tests; any pointer may be null. bounds: lo, hi, inv (3 floats each). Per light (n_lights = the scene's light
+ * count): cluster_of in light list order; perm (the light at each sorted position) and, by sorted position, the clusters' alias slots
+ * run_thr / run_alias (alias = a slot of the same cluster) with their realised counts run_K. run_start: clusters_built + 1 sorted
+ * positions. Per cell slot (n_cell_slots = cells_per_axis^3 x clusters_built, cell-major): cell_thr / cell_alias / cell_K and
+ * cell_prob, the binary32 probability the kernel multiplies by. cluster_of, run_start, the slots and cell_prob are read back from the
+ * device; perm and the counts are the host's. Wrong counts: RT_ERR_ARG; no scene, or the grid off: RT_ERR_STATE. */
+int rt_light_grid_table(rt_ctx* ctx, float bounds[9], uint32_t* cluster_of, uint32_t* perm, uint32_t* run_start, uint32_t* run_thr,
+                        uint32_t* run_alias, uint64_t* run_K, uint32_t* cell_thr, uint32_t* cell_alias, uint64_t* cell_K, float* cell_prob,
+                        uint32_t n_lights, uint32_t n_cell_slots);
 /* launches so far that traced primary rays over the context's rows: rt_raycast, stage-0 raycasts, the one-launch stage 0 and
  * look-ahead raycasts (counted when launched, taken or not). How the tests see reuse without timing anything. */
 int rt_primary_launches(rt_ctx* ctx, uint64_t* n);
