@@ -17,6 +17,7 @@
 #include <cstring>
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -26,6 +27,7 @@
 #include "bvh.h"
 #include "frame_roles.h"
 #include "history_provenance.h"
+#include "stage0_forms.h"
 #include "rt_device.h"
 
 using namespace rt;
@@ -2280,44 +2282,66 @@ static int staged_hints(rt_ctx* c, int** hints)
     return RT_OK;
 }
 
+/* one argument list for every form of k_generate_candidate: each takes all 14, S without its grid where the form has none */
+struct GenArgs
+{
+    SceneViewGrid S;
+    FrameParams P;
+    const float4 *g0, *g1, *prev_rec, *prev_rad;
+    float4 *out_rec, *out_rad;
+    uint32_t* vis_queue;
+    unsigned int* vis_count;
+    float4 *vis_w, *g0_w, *g1_w;
+    int* hints;
+};
+extern "C++" { /* templates cannot live inside extern "C" */
+/* row I of GEN_FORMS, if it is the wanted form: the statement that instantiates a form is the one that launches it */
+template <size_t I> static bool launch_gen_row(const GenForm& want, const GenArgs& A, int g, hipStream_t s)
+{
+    constexpr GenForm F = GEN_FORMS[I];
+    if (!(F == want)) return false;
+    if constexpr (F.grid)
+        k_generate_candidate<F.fuse, F.shadowed, F.defer, F.pipe, F.ws, F.raycast, F.power, F.reproject, F.motion, F.grid><<<g, TRACE_BLOCK, 0, s>>>(
+            A.S, A.P, A.g0, A.g1, A.prev_rec, A.prev_rad, A.out_rec, A.out_rad, A.vis_queue, A.vis_count, A.vis_w, A.g0_w, A.g1_w, A.hints);
+    else
+        k_generate_candidate<F.fuse, F.shadowed, F.defer, F.pipe, F.ws, F.raycast, F.power, F.reproject, F.motion, F.grid><<<g, TRACE_BLOCK, 0, s>>>(
+            static_cast<const SceneView&>(A.S), A.P, A.g0, A.g1, A.prev_rec, A.prev_rad, A.out_rec, A.out_rad, A.vis_queue, A.vis_count, A.vis_w, A.g0_w, A.g1_w, A.hints);
+    return true;
+}
+template <size_t... I> static bool launch_gen_form(const GenForm& want, const GenArgs& A, int g, hipStream_t s, std::index_sequence<I...>)
+{
+    return (... || launch_gen_row<I>(want, A, g, s));
+}
+} /* extern "C++" */
+
 /* staged: a launch of the staged frame (its stage 0 or the look-ahead's): the product's kernel then gets the context's occluder hints */
 static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, int prev_phys, bool fuse, float4* raycast_vis, bool staged)
 {
-    if (c->n_lights == 0 && c->opt.ris_sample_count > 0)
-        RT_FAIL(c, RT_ERR_STATE, "scene has no emissive triangle (the reference divides by zero here)");
+    GenArgs A = {};
+    A.P = make_params(c, L, frame, 0, K_GENERATE);
+    const int g = trace_grid(c, L);
+    Stage0Inputs in = {};
+    in.no_lights = c->n_lights == 0; in.ris = c->opt.ris_sample_count > 0;
+    in.grid_on = c->grid_cells > 0; in.grid_ok = c->grid_built && c->h_grid.ok;
+    in.power_on = c->light_mode == RT_LIGHTS_POWER; in.alias_ok = c->alias_ok;
+    in.shadowed = c->opt.use_shadowed_target_function; in.fuse = fuse;
+    /* before the tag below: dst may not be prev, but the order costs nothing. A motion launch is a reprojecting one */
+    in.history_motion = fuse && history_motion(c, prev_phys, A.P, L.vis);
+    in.history_camera = fuse && !in.history_motion && history_camera(c, prev_phys, A.P);
+    in.temporal_unbiased = c->temporal_unbiased; in.defer_vis = c->tune_defer_vis; in.ris_pipe = c->tune_ris_pipe;
+    in.ws = use_ws(c, g); in.raycast = raycast_vis != nullptr;
+    const Stage0Plan plan = stage0_plan(in); /* every refusal before the first side effect */
+    if (plan.code != RT_OK) RT_FAIL(c, plan.code, "%s", FORM_MESSAGE[plan.why]);
+    const GenForm& F = plan.form;
     int* hints = nullptr;
     if (staged) { const int rc = staged_hints(c, &hints); if (rc != RT_OK) return rc; }
     SceneView S = make_scene(c);
-    /* rt_light_grid decides the selection while it is on; rt_light_sampling's mode is kept and applies again when it goes off */
-    const bool grid = c->grid_cells > 0 && c->opt.ris_sample_count > 0;
-    SceneViewGrid SG;
-    if (grid)
-    {
-        if (!c->grid_built || !c->h_grid.ok) RT_FAIL(c, RT_ERR_STATE, "rt_light_grid: no light of the scene has a positive finite area x luminance");
-        S.lights = c->d_lights_grid;
-        S.light_ke = c->d_light_ke_grid;
-    }
-    static_cast<SceneView&>(SG) = S;
-    SG.grid = GridView{c->h_grid.bounds(), c->h_grid.B, c->d_grid_cells, c->d_grid_cell_prob, c->d_grid_runs, c->d_grid_run_slots}; /* null while off */
-    const bool power = !grid && c->light_mode == RT_LIGHTS_POWER && c->opt.ris_sample_count > 0;
-    if (power)
-    {
-        if (!c->alias_ok) RT_FAIL(c, RT_ERR_STATE, "rt_light_sampling: no light of the scene has a positive finite area x luminance");
-        S.lights = c->d_lights_power;
-        S.light_alias = c->d_alias;
-    }
-    FrameParams P = make_params(c, L, frame, 0, K_GENERATE);
-    const bool sh = c->opt.use_shadowed_target_function;
-    float4 *orec = c->d_rec[dst_phys], *orad = c->d_rad[dst_phys];
-    /* before the tag below: dst may not be prev, but the order costs nothing. A motion launch is a reprojecting one (mo implies rp) */
-    const bool mo = fuse && history_motion(c, prev_phys, P, L.vis);
-    const bool rp = mo || (fuse && history_camera(c, prev_phys, P));
-    /* rt_temporal_unbiased: a reprojecting launch becomes two, the candidates without the merge and k_temporal_unbiased in place on
-     * their buffer (below). A motion launch cannot be one: the two toggles refuse each other. */
-    const bool ub = rp && !mo && c->temporal_unbiased;
-    if (ub && sh) RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_unbiased: the shadowed target function is not built for the 1/Z merge");
-    const FrameParams Pu = P; /* the merge's: the history buffer's camera */
-    if (ub)
+    if (plan.tables == LIGHTS_GRID) { S.lights = c->d_lights_grid; S.light_ke = c->d_light_ke_grid; }
+    if (plan.tables == LIGHTS_POWER) { S.lights = c->d_lights_power; S.light_alias = c->d_alias; }
+    static_cast<SceneView&>(A.S) = S;
+    A.S.grid = GridView{c->h_grid.bounds(), c->h_grid.B, c->d_grid_cells, c->d_grid_cell_prob, c->d_grid_runs, c->d_grid_run_slots}; /* null while off */
+    const FrameParams Pu = A.P; /* the merge's: the history buffer's camera */
+    if (plan.unbiased_merge)
     {
         /* the product's fused form, whichever the tuning picks, made to merge nothing: the reprojecting instantiation under a history
          * camera of NaNs. The fused kernels merge by template, not by FrameParams::use_temporal, so the NaN camera alone does it: the
@@ -2328,39 +2352,20 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
          * shaded pixels as merged by a reprojecting launch, without a valid history (rt_temporal_reprojection_stats); the merge
          * below adds the valid and the moved ones and does not count the pixels again. */
         const float qnan = __builtin_nanf("");
-        P.prev_origin = P.prev_right = P.prev_up = F3(qnan, qnan, qnan);
+        A.P.prev_origin = A.P.prev_right = A.P.prev_up = F3(qnan, qnan, qnan);
     }
     tag_reservoir(c, dst_phys);
-    const float4 *prec = fuse ? c->d_rec[prev_phys] : nullptr, *prad = fuse ? c->d_rad[prev_phys] : nullptr;
-    const int g = trace_grid(c, L);
-    /* every form of the kernel in both light samplings: <fused, shadowed, deferred, pipelined, work-sharing, with primary rays>; the
-     * light grid in the product's forms (the [exp] deferred and pipelined forms refuse it below) */
-#define GEN_LAUNCH(FT, SH, DF, PP, WS_, RC, ...)                                                                                  \
-    do {                                                                                                                          \
-        if (grid && !(DF) && !(PP)) { const SceneViewGrid& S = SG; k_generate_candidate<FT, SH, false, false, WS_, RC, false, false, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); break; } \
-        if (power) k_generate_candidate<FT, SH, DF, PP, WS_, RC, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);              \
-        else k_generate_candidate<FT, SH, DF, PP, WS_, RC><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);                          \
-    } while (0)
-    /* the fused forms the product launches, with the history gathered by reprojection (rp) or from the own pixel */
-#define GEN_LAUNCH_RP(SH, WS_, RC, ...)                                                                                           \
-    do {                                                                                                                          \
-        if (!rp) GEN_LAUNCH(true, SH, false, false, WS_, RC, __VA_ARGS__);                                                         \
-        else if (mo && grid) { const SceneViewGrid& S = SG; k_generate_candidate<true, SH, false, false, WS_, RC, false, true, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); } \
-        else if (grid) { const SceneViewGrid& S = SG; k_generate_candidate<true, SH, false, false, WS_, RC, false, true, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); } \
-        else if (mo && power) k_generate_candidate<true, SH, false, false, WS_, RC, true, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
-        else if (mo) k_generate_candidate<true, SH, false, false, WS_, RC, false, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
-        else if (power) k_generate_candidate<true, SH, false, false, WS_, RC, true, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__); \
-        else k_generate_candidate<true, SH, false, false, WS_, RC, false, true><<<g, TRACE_BLOCK, 0, L.stream>>>(__VA_ARGS__);     \
-    } while (0)
+    /* the primary rays' form writes the G-buffer it does not read; the occluder hints are the work-sharing forms' */
+    A.g0 = F.raycast ? nullptr : L.g0; A.g1 = F.raycast ? nullptr : L.g1;
+    A.prev_rec = fuse ? c->d_rec[prev_phys] : nullptr; A.prev_rad = fuse ? c->d_rad[prev_phys] : nullptr;
+    A.out_rec = c->d_rec[dst_phys]; A.out_rad = c->d_rad[dst_phys];
+    if (F.raycast) { A.vis_w = raycast_vis; A.g0_w = L.g0; A.g1_w = L.g1; }
+    A.hints = F.ws ? hints : nullptr;
 #ifdef RT_EXPERIMENTS
-    if (grid && fuse && !sh && (c->tune_defer_vis || c->tune_ris_pipe))
-        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_light_grid: the [exp] stage-0 variants (rt_tuning keys 11 and 12) are not built for the light grid");
-    if (rp && fuse && ((!sh && c->tune_defer_vis) || (!sh && c->tune_ris_pipe)))
-        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_reprojection / rt_temporal_motion: the [exp] stage-0 variants (rt_tuning keys 11 and 12) gather their history from the own pixel only");
-    if (fuse && !sh && c->tune_defer_vis)
+    const int lane = (L.stream == c->aux_stream) ? 1 : 0;
+    if (plan.deferred_queue)
     {
         /* fused + unshadowed: the visibility-reuse rays that survive the temporal merge go through a queue */
-        const int lane = (L.stream == c->aux_stream) ? 1 : 0;
         const size_t npx = local_pixels(c);
         if (!c->d_visq[0])
         {
@@ -2373,9 +2378,16 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
         }
         if (c->visq_epoch != c->epoch) { c->h_visq_count[0] = c->h_visq_count[1] = 0xffffffffu; c->visq_epoch = c->epoch; }
         RT_HIP(c, hipMemsetAsync(c->d_visq_count + lane, 0, 4, L.stream));
-        if (c->tune_ris_pipe) GEN_LAUNCH(true, false, true, true, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
-        else GEN_LAUNCH(true, false, true, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad, c->d_visq[lane], c->d_visq_count + lane);
-        RT_HIP(c, hipGetLastError());
+        A.vis_queue = c->d_visq[lane]; A.vis_count = c->d_visq_count + lane;
+    }
+#endif
+    if (!launch_gen_form(F, A, g, L.stream, std::make_index_sequence<GEN_FORM_COUNT>()))
+        RT_FAIL(c, RT_ERR_STATE, "k_generate_candidate<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d> is not a row of GEN_FORMS (stage0_forms.h)", F.fuse,
+                F.shadowed, F.defer, F.pipe, F.ws, F.raycast, F.power, F.reproject, F.motion, F.grid);
+    RT_HIP(c, hipGetLastError());
+#ifdef RT_EXPERIMENTS
+    if (plan.deferred_queue)
+    {
         /* grid of the walk: one queue entry per lane if the count is like the last one that reached the host (+50 %),
          * every pixel of the launch if that is unknown (first frame, camera / option change); the kernel's stride loop
          * covers any count */
@@ -2386,30 +2398,15 @@ static int launch_generate(rt_ctx* c, const Launch& L, int frame, int dst_phys, 
             const unsigned long long want = ((unsigned long long)last * 3ull / 2ull + TRACE_BLOCK - 1) / TRACE_BLOCK + 64ull;
             gv = want < (unsigned long long)g ? (int)want : g;
         }
-        k_candidate_visibility<<<gv, TRACE_BLOCK, 0, L.stream>>>(S, L.g0, L.g1, orec, c->d_visq[lane], c->d_visq_count + lane);
+        k_candidate_visibility<<<gv, TRACE_BLOCK, 0, L.stream>>>(S, L.g0, L.g1, A.out_rec, c->d_visq[lane], c->d_visq_count + lane);
         RT_HIP(c, hipGetLastError());
         RT_HIP(c, hipMemcpyAsync(c->h_visq_count + lane, c->d_visq_count + lane, 4, hipMemcpyDeviceToHost, L.stream));
-        return RT_OK;
     }
 #endif
-    if (fuse && sh) GEN_LAUNCH_RP(true, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
-#ifdef RT_EXPERIMENTS
-    else if (fuse && c->tune_ris_pipe) GEN_LAUNCH(true, false, false, true, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
-#endif
-    else if (fuse && use_ws(c, g) && raycast_vis)
-        GEN_LAUNCH_RP(false, true, true, S, P, nullptr, nullptr, prec, prad, orec, orad, nullptr, nullptr, raycast_vis, L.g0, L.g1, hints);
-    else if (raycast_vis) RT_FAIL(c, RT_ERR_STATE, "the one-launch stage 0 needs the product's fused candidate kernel");
-    else if (fuse && use_ws(c, g)) GEN_LAUNCH_RP(false, true, false, S, P, L.g0, L.g1, prec, prad, orec, orad, nullptr, nullptr, nullptr, nullptr, nullptr, hints);
-    else if (fuse) GEN_LAUNCH_RP(false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
-    else if (sh) GEN_LAUNCH(false, true, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
-    else GEN_LAUNCH(false, false, false, false, false, false, S, P, L.g0, L.g1, prec, prad, orec, orad);
-#undef GEN_LAUNCH_RP
-#undef GEN_LAUNCH
-    RT_HIP(c, hipGetLastError());
-    if (ub)
+    if (plan.unbiased_merge)
     {
         /* same stream, same rows, same tag: reads the G-buffer the launch above read or wrote, merges the history in place */
-        k_temporal_unbiased<<<g, TRACE_BLOCK, 0, L.stream>>>(S, Pu, L.g0, L.g1, prec, prad, orec, orad, 0 /* the launch above has counted the merged pixels */);
+        k_temporal_unbiased<<<g, TRACE_BLOCK, 0, L.stream>>>(S, Pu, L.g0, L.g1, A.prev_rec, A.prev_rad, A.out_rec, A.out_rad, 0 /* the launch above has counted the merged pixels */);
         RT_HIP(c, hipGetLastError());
     }
     return RT_OK;
@@ -2427,6 +2424,22 @@ int rt_generate_candidate(rt_ctx* c, int frame, int dst)
     return launch_generate(c, whole_launch(c), frame, c->frame.res_map[dst], 0, false);
 }
 
+extern "C++" {
+/* row I of TEMPORAL_FORMS, if it is the wanted form (as launch_gen_row) */
+template <size_t I> static bool launch_temporal_row(rt_ctx* c, const TemporalForm& want, const SceneView& S, const FrameParams& P, const Launch& L, int pp, int pi)
+{
+    constexpr TemporalForm F = TEMPORAL_FORMS[I];
+    if (!(F == want)) return false;
+    k_temporal<F.shadowed, F.reproject, F.motion><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+    return true;
+}
+template <size_t... I>
+static bool launch_temporal_form(rt_ctx* c, const TemporalForm& want, const SceneView& S, const FrameParams& P, const Launch& L, int pp, int pi, std::index_sequence<I...>)
+{
+    return (... || launch_temporal_row<I>(c, want, S, P, L, pp, pi));
+}
+} /* extern "C++" */
+
 int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
 {
     RT_CHECK_CTX(c);
@@ -2441,30 +2454,21 @@ int rt_temporal_resampling(rt_ctx* c, int frame, int prev, int inout)
     const Launch L = whole_launch(c);
     FrameParams P = make_params(c, L, frame, 0);
     const int pp = c->frame.res_map[prev], pi = c->frame.res_map[inout];
-    const bool mo = history_motion(c, pp, P, c->gbuf.vis);
-    const bool rp = !mo && history_camera(c, pp, P);
-    const bool ub = rp && c->temporal_unbiased; /* rt_temporal_unbiased: the 1/Z merge wherever the history is gathered by reprojection */
-    if (ub && c->opt.use_shadowed_target_function)
-        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_temporal_unbiased: the shadowed target function is not built for the 1/Z merge");
+    TemporalInputs in = {};
+    in.shadowed = c->opt.use_shadowed_target_function; in.temporal_unbiased = c->temporal_unbiased;
+    in.history_motion = history_motion(c, pp, P, c->gbuf.vis);
+    in.history_camera = !in.history_motion && history_camera(c, pp, P);
+    const TemporalPlan plan = temporal_plan(in);
+    if (plan.code != RT_OK) RT_FAIL(c, plan.code, "%s", FORM_MESSAGE[plan.why]);
     tag_reservoir(c, pi, c->res_tag[pi].gserial); /* merged in place: its shaded bits stay those of the G-buffer it was made from */
-    if (ub)
+    if (plan.unbiased_merge) /* rt_temporal_unbiased: the 1/Z merge wherever the history is gathered by reprojection */
     {
         P = make_params(c, L, frame, 0, K_GENERATE); /* a tracing kernel on 8 x 8 tiles: the candidates' tile order */
         history_camera(c, pp, P);
         k_temporal_unbiased<<<trace_grid(c, L), TRACE_BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi], 1);
     }
-    else if (mo && c->opt.use_shadowed_target_function)
-        k_temporal<true, true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
-    else if (mo)
-        k_temporal<false, true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
-    else if (rp && c->opt.use_shadowed_target_function)
-        k_temporal<true, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
-    else if (rp)
-        k_temporal<false, true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
-    else if (c->opt.use_shadowed_target_function)
-        k_temporal<true><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
-    else
-        k_temporal<false><<<launch_grid(c, L), BLOCK, 0, c->stream>>>(S, P, c->gbuf.g0, c->gbuf.g1, c->d_rec[pp], c->d_rad[pp], c->d_rec[pi], c->d_rad[pi]);
+    else if (!launch_temporal_form(c, plan.form, S, P, L, pp, pi, std::make_index_sequence<sizeof(TEMPORAL_FORMS) / sizeof(TemporalForm)>()))
+        RT_FAIL(c, RT_ERR_STATE, "k_temporal<%d, %d, %d> is not a row of TEMPORAL_FORMS (stage0_forms.h)", plan.form.shadowed, plan.form.reproject, plan.form.motion);
     RT_HIP(c, hipGetLastError());
     return RT_OK;
 }

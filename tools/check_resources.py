@@ -12,35 +12,37 @@ import re
 import subprocess
 import sys
 
+from kernel_forms import ANY, generate_candidate as gc, temporal as kt
+
 # kernel (demangled name up to the argument list, regex) -> (max spilled VGPRs, min wavefronts per SIMD)
 # numbers = the build of round 5 (hipcc of ROCm 7.2.0, csrc/Makefile flags); the shadowed pass is the one kernel that is
 # ALLOWED to spill (72 VGPRs + spills at 7 wavefronts per SIMD beat 112 VGPRs at 4: docs/MEASUREMENT_LOG_r04.md section 9)
 BUDGET = [
     (r"^k_raycast<false>", 0, 8),
     (r"^k_raycast<true>", 0, 7),                                              # strips: work-sharing closest-hit walk
-    (r"^k_generate_candidate<true, false, false, false, true, true, (true|false), false, false, (true|false)>", 0, 6),   # the whole frame's stage 0: primary ray + candidates + temporal
-    (r"^k_generate_candidate<true, false, false, false, true, false, (true|false), false, false, (true|false)>", 0, 6),  # candidates + temporal (strips, rt_timing)
-    (r"^k_generate_candidate<true, false, false, false, false, false, (true|false), false, false, (true|false)>", 0, 5), # ... without the work-sharing walk (rt_tuning 13 = 0)
-    (r"^k_generate_candidate<false, false, false, false, false, false, (true|false), false, false, (true|false)>", 0, 6), # rt_generate_candidate
+    ("^" + gc(fuse=1, ws=1, raycast=1, power=ANY, grid=ANY), 0, 6),                          # the whole frame's stage 0: primary ray + candidates + temporal
+    ("^" + gc(fuse=1, ws=1, power=ANY, grid=ANY), 0, 6),                                     # candidates + temporal (strips, rt_timing)
+    ("^" + gc(fuse=1, power=ANY, grid=ANY), 0, 5),                                           # ... without the work-sharing walk (rt_tuning 13 = 0)
+    ("^" + gc(power=ANY, grid=ANY), 0, 6),                                                   # rt_generate_candidate
     # r23 rt_temporal_reprojection: the fused forms with the history gathered by reprojection (last argument), uniform and power lights
-    (r"^k_generate_candidate<true, false, false, false, true, true, (true|false), true, false, (true|false)>", 0, 6),    # one-launch stage 0: 79 VGPRs as the default form
-    (r"^k_generate_candidate<true, false, false, false, true, false, (true|false), true, false, (true|false)>", 0, 6),   # candidates + temporal: 79
-    (r"^k_generate_candidate<true, false, false, false, false, false, (true|false), true, false, (true|false)>", 0, 5),  # without the work-sharing walk: 82
-    (r"^k_generate_candidate<true, true, false, false, false, false, (true|false), true, false, (true|false)>", 0, 4),   # shadowed target function: 109
-    (r"^k_temporal<false, true, false>", 0, 7),                                      # rt_temporal_resampling: 66
-    (r"^k_temporal<true, true, false>", 0, 4),                                       # ... shadowed: 113
+    ("^" + gc(fuse=1, ws=1, raycast=1, power=ANY, reproject=1, grid=ANY), 0, 6),             # one-launch stage 0: 79 VGPRs as the default form
+    ("^" + gc(fuse=1, ws=1, power=ANY, reproject=1, grid=ANY), 0, 6),                        # candidates + temporal: 79
+    ("^" + gc(fuse=1, power=ANY, reproject=1, grid=ANY), 0, 5),                              # without the work-sharing walk: 82
+    ("^" + gc(fuse=1, shadowed=1, power=ANY, reproject=1, grid=ANY), 0, 4),                  # shadowed target function: 109
+    ("^" + kt(reproject=1), 0, 7),                                                           # rt_temporal_resampling: 66
+    ("^" + kt(shadowed=1, reproject=1), 0, 4),                                               # ... shadowed: 113
     # r24 rt_temporal_motion: the same forms with the history that follows moved triangles (last argument), uniform and power lights
-    (r"^k_generate_candidate<true, false, false, false, true, true, (true|false), true, true, (true|false)>", 0, 6),    # one-launch stage 0
-    (r"^k_generate_candidate<true, false, false, false, true, false, (true|false), true, true, (true|false)>", 0, 6),   # candidates + temporal
-    (r"^k_generate_candidate<true, false, false, false, false, false, (true|false), true, true, (true|false)>", 0, 5),  # without the work-sharing walk
-    (r"^k_generate_candidate<true, true, false, false, false, false, (true|false), true, true, (true|false)>", 0, 4),   # shadowed target function
-    (r"^k_temporal<false, true, true>", 0, 7),                                # rt_temporal_resampling
-    (r"^k_temporal<true, true, true>", 0, 4),                                 # ... shadowed
+    ("^" + gc(fuse=1, ws=1, raycast=1, power=ANY, reproject=1, motion=1, grid=ANY), 0, 6),   # one-launch stage 0
+    ("^" + gc(fuse=1, ws=1, power=ANY, reproject=1, motion=1, grid=ANY), 0, 6),              # candidates + temporal
+    ("^" + gc(fuse=1, power=ANY, reproject=1, motion=1, grid=ANY), 0, 5),                    # without the work-sharing walk
+    ("^" + gc(fuse=1, shadowed=1, power=ANY, reproject=1, motion=1, grid=ANY), 0, 4),        # shadowed target function
+    ("^" + kt(reproject=1, motion=1), 0, 7),                                                 # rt_temporal_resampling
+    ("^" + kt(shadowed=1, reproject=1, motion=1), 0, 4),                                     # ... shadowed
     (r"^k_temporal_unbiased", 0, 4),     # r31 rt_temporal_unbiased: 101 VGPRs without a budget, no spill (budget 5: 95, no spill; 6: 80 and 15 spilled)
     # r33 rt_light_grid: the last argument of every k_generate_candidate entry above; the grid forms hold their neighbours' budgets, and
     # the shadowed form without reprojection, in both
-    (r"^k_generate_candidate<true, true, false, false, false, false, false, false, false, (true|false)>", 0, 4),
-    (r"^k_generate_candidate<false, true, false, false, false, false, false, false, false, (true|false)>", 0, 4),
+    ("^" + gc(fuse=1, shadowed=1, grid=ANY), 0, 4),
+    ("^" + gc(shadowed=1, grid=ANY), 0, 4),
     (r"^k_spatial_coop<6, false, 256>", 0, 6),                                # the roofline kernel
     (r"^k_spatial_coop<6, true, 256>", 0, 5),                                 # strips: halo lists read / written in the pass
     (r"^k_resolve<", 0, 8),

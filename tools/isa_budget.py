@@ -27,6 +27,8 @@ import subprocess
 import sys
 import tempfile
 
+from kernel_forms import generate_candidate, temporal
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "cedec_2024_rt_amd", "csrc", "restir_rt.hip")
 # the product's flags (csrc/Makefile HIPFLAGS; r06: -fno-slp-vectorize had been missing here since round 4) + ISA_BUDGET_EXTRA
@@ -188,19 +190,40 @@ def summarise(ops):
     return cls, cyc, buckets
 
 
-# r06: the template argument lists of the product's kernels as they are now (k_generate_candidate: <FUSE, SHADOWED, DEFER, PIPE, WS, RAYCAST>;
-# k_spatial_coop: <WAVES, FUSED, TB>); the experiments library's forms (k_spatial_gather / _lds, k_resolve_stream) are found only when the
-# tool compiles with -DRT_EXPERIMENTS (ISA_BUDGET_EXTRA="-DRT_EXPERIMENTS")
+# r06: the template argument lists of the product's kernels as they are now (k_generate_candidate and k_temporal: tools/kernel_forms.py;
+# k_spatial_coop: <WAVES, FUSED, TB>); the experiments library's forms (EXP_ONLY: k_spatial_gather / _lds, k_resolve_stream) are looked for
+# only when the tool compiles with -DRT_EXPERIMENTS (ISA_BUDGET_EXTRA="-DRT_EXPERIMENTS")
 KERNELS = [("k_raycast", "k_raycast<false>("), ("k_raycast<WS>", "k_raycast<true>("),
-           ("stage 0 as one launch: k_generate_candidate<..., WS, RAYCAST>", "k_generate_candidate<true, false, false, false, true, true>("),
-           ("k_generate_candidate<true,false,WS>", "k_generate_candidate<true, false, false, false, true, false>("),
-           ("k_generate_candidate<true,false>", "k_generate_candidate<true, false, false, false, false, false>("),
+           ("stage 0 as one launch: k_generate_candidate<..., WS, RAYCAST>", generate_candidate(fuse=1, ws=1, raycast=1) + "("),
+           ("k_generate_candidate<true,false,WS>", generate_candidate(fuse=1, ws=1) + "("),
+           ("k_generate_candidate<true,false>", generate_candidate(fuse=1) + "("),
            ("k_resolve<WS>", "k_resolve<true>("), ("k_resolve_stream", "k_resolve_stream("),
            ("k_spatial_gather", "k_spatial_gather<6>("), ("k_spatial_coop", "k_spatial_coop<6, false, 256>("), ("k_spatial_coop<fused>", "k_spatial_coop<6, true, 256>("),
            ("k_halo_mark", "k_halo_mark<true>("), ("k_spatial_lds", "k_spatial_lds("), ("k_resolve", "k_resolve<false>("), ("k_spatial<true>", "k_spatial<true, true>("), ("k_spatial<true> per-lane records", "k_spatial<true, false>("),
-           ("k_temporal<false>", "k_temporal<false>("), ("k_tone_mapping", "k_tone_mapping("),
+           ("k_temporal<false>", temporal() + "("), ("k_tone_mapping", "k_tone_mapping("),
            ("k_path_trace<9,false>", "k_path_trace<9, false>(")]
+EXP_ONLY = {"k_resolve_stream", "k_spatial_gather", "k_spatial_lds"}
 LOOP_KERNELS = {"k_raycast", "k_generate_candidate<true,false,WS>", "stage 0 as one launch: k_generate_candidate<..., WS, RAYCAST>", "k_spatial_gather", "k_spatial_coop", "k_halo_mark", "k_resolve<WS>", "k_spatial<true>"}
+
+
+def select(names):
+    """[(label, needle, mangled name)] of KERNELS in a build. A selector of the product's that matches no function is an error (a
+    silent miss is how the stage-0 kernels once dropped out of the tables); the [exp] ones are skipped in a product build"""
+    exp = "-DRT_EXPERIMENTS" in FLAGS
+    picked, missing = [], []
+    for label, needle in KERNELS:
+        if label in EXP_ONLY and not exp:
+            continue
+        cand = [m for m, d in names.items() if needle in d.replace("void ", "")]
+        if cand:
+            picked.append((label, needle, cand[0]))
+        elif label in EXP_ONLY:
+            sys.stderr.write("isa_budget: [exp] selector %r (%s) matches no function\n" % (needle, label))
+        else:
+            missing.append("%r (%s)" % (needle, label))
+    if missing:
+        raise SystemExit("isa_budget: no function matches the selector " + ", ".join(missing) + " (renamed? update KERNELS)")
+    return picked
 
 
 def class_costs(path):
@@ -211,12 +234,9 @@ def class_costs(path):
     names = demangle(list(fns))
     out = {"costs_cycles": {"F": round(F_COST, 3), "FMA": round(FMA_COST, 3), "C": round(C_COST, 3), "T": round(T_COST, 3)},
            "source": "tools/isa_budget.py --class-costs: static gfx950 ISA of each kernel, instruction costs of profiles/r02_valu_rates.json"}
-    for label, needle in KERNELS:
-        cand = [m for m, d in names.items() if needle in d.replace("void ", "")]
-        if not cand:
-            continue
+    for label, needle, mang in select(names):
         agg = collections.defaultdict(lambda: [0, 0.0])
-        for op, n in histogram(fns[cand[0]]).items():
+        for op, n in histogram(fns[mang]).items():
             if not op.startswith("v_"):
                 continue
             _, cost = classify(op)
@@ -246,11 +266,7 @@ def main():
     print("| kernel | VGPR | AGPR | SGPR | scratch B/lane | LDS B | waves/SIMD | VALU static | F | C | T | SALU | VMEM | LDS ops |")
     print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     picked = []
-    for label, needle in KERNELS:
-        cand = [m for m, d in names.items() if needle in d.replace("void ", "")]
-        if not cand:
-            continue
-        mang = cand[0]
+    for label, _, mang in select(names):
         picked.append((label, mang))
         ops = histogram(fns[mang])
         cls, cyc, _ = summarise(ops)
