@@ -35,6 +35,10 @@ struct HistoryTag
     bool light_current(uint64_t geo_gen) const { return has && std::max(gen, light_gen) == geo_gen; }
     /* the update that ends generation geo_gen has re-based this buffer's samples (only a light_current buffer is re-based) */
     void light_rebased(uint64_t geo_gen) { light_gen = geo_gen + 1; }
+    /* the update that ends generation geo_gen is followed (the toggle is on) and its span held no emissive triangle: a light_current
+     * buffer's samples lie on triangles that keep their bytes, so they describe the next generation as they are. Without this a box
+     * moved before a lamp, with no frame between the two updates, would end the chain that the other order keeps. */
+    void light_untouched(uint64_t geo_gen) { if (light_current(geo_gen)) light_gen = geo_gen + 1; }
 };
 
 /* the two consumers of the kept vertices: the ReSTIR history (rt_temporal_motion) and the denoiser's (rt_denoise_temporal_motion) */

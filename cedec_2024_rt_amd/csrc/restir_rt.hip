@@ -1605,7 +1605,8 @@ static int refit_first_update(rt_ctx* c)
 /* rt_temporal_light_motion inside rt_scene_update(first, count), after the streams are drained and before anything of the old scene is
  * overwritten (light_follow.h, light_follow_kernels.h). Runs iff the toggle is on and the span holds an emissive
  * triangle in the OLD array; then every physical reservoir buffer whose light samples describe the generation this update ends
- * (HistoryTag::light_current) is re-based in place with its radiance side record, one launch each, and its light_gen advances. */
+ * (HistoryTag::light_current) is re-based in place with its radiance side record, one launch each, and its light_gen advances. With the
+ * toggle on and no emissive triangle in the old span nothing is launched and a current buffer stays current (light_untouched). */
 static int light_follow_rebase(rt_ctx* c, const rt_triangle* triangles, uint32_t first, uint32_t count)
 {
     c->lf_last = 0;
@@ -1615,7 +1616,12 @@ static int light_follow_rebase(rt_ctx* c, const rt_triangle* triangles, uint32_t
     const auto lo = std::lower_bound(c->h_lights.begin(), c->h_lights.end(), first);
     const auto hi = std::lower_bound(lo, c->h_lights.end(), first + count);
     const uint32_t n_ids = (uint32_t)(hi - lo);
-    if (n_ids == 0u) return RT_OK;
+    if (n_ids == 0u)
+    {
+        /* no emitter of the old array changes: the samples of a current buffer stay where they are and stay current */
+        for (int p = 0; p < 5; ++p) c->res_tag[p].light_untouched(c->moved.geo_gen);
+        return RT_OK;
+    }
     int phys[5], np = 0;
     for (int p = 0; p < 5; ++p)
         if (c->d_rec[p] && c->d_rad[p] && c->res_tag[p].light_current(c->moved.geo_gen)) phys[np++] = p;

@@ -425,7 +425,9 @@ int rt_temporal_unbiased_stats(rt_ctx* ctx, uint64_t out[4]);
  * radiance; after rt_scene_update moved the emitter it still points at where the emitter was. While the toggle is on,
  * rt_scene_update(first, count) whose span holds an emissive triangle in the OLD array re-bases, before it overwrites anything, every
  * physical reservoir buffer whose light samples describe the generation the update ends (written under it, or re-based to it by the
- * update before: two updates with no frame between them are both followed; an older or untagged buffer is left alone): a shaded
+ * update before: two updates with no frame between them are both followed, and an update whose span holds no emissive triangle in the old
+ * array moves no emitter, so a buffer that was current stays current over it - a box moved before the lamp ends nothing; an older or
+ * untagged buffer is left alone): a shaded
  * record with M > 0 whose sample lies on an old emissive triangle of the span (same normal and radiance bytes, on its plane and inside
  * it within measured tolerances; the nearest plane, then the lowest index) keeps every byte if the triangle's 60 bytes do not change,
  * becomes Reservoir{} (shaded bit kept) if the new triangle is non-emissive, degenerate or not finite, and is otherwise carried by

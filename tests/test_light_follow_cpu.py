@@ -305,12 +305,14 @@ extern "C" void hr_new() { g_t[0] = g_t[1] = HistoryTag(); g_m = MovedGeometry()
 extern "C" void hr_write(int k) { rt_raygen rg = {}; const float eye[3] = {0, 0, 0}; g_t[k].write(rg, g_m.geo_gen, eye, 0); g_m.tagged(FOLLOW_RESTIR); }
 extern "C" void hr_copy(int dst, int src) { g_t[dst] = g_t[src]; }
 extern "C" void hr_clear(int k) { g_t[k].has = false; }
-/* an update: re-bases the qualifying buffers if `follow` (toggle on and the span has a light), returns a bit per re-based buffer */
+/* an update: re-bases the qualifying buffers if `follow` is 1 (toggle on and the span has a light), returns a bit per re-based buffer;
+ * follow = 2: toggle on and no light in the span (nothing is re-based, a current buffer stays current) */
 extern "C" int hr_update(int follow)
 {
     int mask = 0;
     for (int k = 0; k < 2; ++k)
-        if (follow && g_t[k].light_current(g_m.geo_gen)) { g_t[k].light_rebased(g_m.geo_gen); mask |= 1 << k; }
+        if (follow == 2) g_t[k].light_untouched(g_m.geo_gen);
+        else if (follow && g_t[k].light_current(g_m.geo_gen)) { g_t[k].light_rebased(g_m.geo_gen); mask |= 1 << k; }
     g_m.update(0, 1);
     return mask;
 }
@@ -340,7 +342,7 @@ def test_light_gen_transitions(host):
     assert h.hr_update(1) == 0, "an untagged buffer is not re-based"
     h.hr_write(0)
     assert (h.hr_gen(0), h.hr_light_gen(0), h.hr_geo_gen()) == (1, 1, 1), "write sets light_gen with gen"
-    assert h.hr_update(0) == 0 and h.hr_light_gen(0) == 1, "toggle off, or no light in the span: nothing advances"
+    assert h.hr_update(0) == 0 and h.hr_light_gen(0) == 1, "toggle off: nothing advances"
     assert h.hr_update(1) == 0, "the buffer is now one generation behind: an older history is left alone"
     h.hr_write(0)
     g = h.hr_geo_gen()
@@ -355,6 +357,13 @@ def test_light_gen_transitions(host):
     assert h.hr_update(1) == 2, "only the freshly written buffer"
     h.hr_write(0)
     assert h.hr_gen(0) == h.hr_light_gen(0) == h.hr_geo_gen(), "write resets light_gen to gen"
+    # toggle on, a span without a light (a box moved before the lamp, no frame between): nothing is re-based, the chain goes on
+    g = h.hr_geo_gen()
+    assert h.hr_update(2) == 0 and (h.hr_gen(0), h.hr_light_gen(0)) == (g, g + 1), "a current buffer stays current over a span without lights"
+    assert h.hr_light_gen(1) == g + 1, "... and so does the other one, which the update before had re-based"
+    assert h.hr_update(1) == 3 and h.hr_light_gen(0) == h.hr_light_gen(1) == g + 2, "... and the lamp's update that follows re-bases both"
+    assert h.hr_update(0) == 0 and h.hr_update(2) == 0 and h.hr_light_gen(0) == h.hr_light_gen(1) == g + 2, "a buffer that is behind stays behind"
+    assert h.hr_update(1) == 0
 
 
 # -------------------------------------------------------------------------------------------------------------- restir_app
