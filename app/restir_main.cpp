@@ -13,7 +13,7 @@
  *              [--move-lights dx dy dz] [--denoise N [--denoise-temporal]] [--orbit dx dy] [--unbiased] [--reproject] [--unbiased-temporal]
  *              [--move-tris first count dx dy dz] [--follow-motion] [--follow-lights] [--denoise-follow-motion]
  *              [--denoise-antilag [radius lo hi floor]]
- *              [--light-sampling uniform|power] [--light-grid CELLS CLUSTERS]
+ *              [--light-sampling uniform|power] [--light-grid CELLS CLUSTERS] [--indirect N]
  *
  * --example 4: BASELINE config #1 — the `kernelMain` of examples/04_ao/04_ao.cu:31-88 as a host C++ loop over the
  * image rows (cedec_2024_rt_amd/csrc/host_path.h: brute-force closest hit, 64 ambient-occlusion rays per pixel,
@@ -25,6 +25,8 @@
  * --denoise-temporal (with --denoise N): rt_denoise_temporal (default alphas) in place of rt_denoise, one call per frame.
  * --unbiased (--example 10, one GPU): rt_spatial_unbiased, the spatial passes normalise by 1/Z; not with
  * --shadowed 1.
+ * --indirect N (--example 10, one GPU): rt_indirect, every frame adds N = 1..32 bounces of path-traced indirect light (08_nee's depth
+ * loop from depth 1, started at the G-buffer) between resolve and tone mapping.
  * --light-grid CELLS CLUSTERS (--example 10, one GPU): rt_light_grid, the candidates draw a cluster of lights from the table of their
  * surface point's grid cell (cluster power over squared distance) and a light from the cluster's alias table;
  * 1..32 cells per axis and 1..256 clusters, suggested 16 64; while it is given it decides over --light-sampling.
@@ -471,6 +473,7 @@ int main(int argc, char** argv)
     rt_denoise_antilag_params antilag = {4, 0.2f, 0.8f, 0.05f};
     int light_mode = RT_LIGHTS_UNIFORM;
     int grid_cells = 0, grid_clusters = 0;
+    int indirect = 0;
     float orbit_d[2] = {0.0f, 0.0f};
     LightMove mv;
     rt_options opt;
@@ -536,6 +539,12 @@ int main(int argc, char** argv)
                 i += 4;
             }
         }
+        else if (a == "--indirect")
+        {
+            if (i + 1 >= argc) { fprintf(stderr, "--indirect N\n"); return 2; }
+            indirect = atoi(argv[++i]);
+            if (indirect < 1 || indirect > 32) { fprintf(stderr, "--indirect: 1..32 bounces\n"); return 2; }
+        }
         else if (a == "--light-grid")
         {
             if (i + 2 >= argc) { fprintf(stderr, "--light-grid CELLS CLUSTERS\n"); return 2; }
@@ -573,6 +582,7 @@ int main(int argc, char** argv)
     if (unbiased_temporal && !reproject) { fprintf(stderr, "--unbiased-temporal needs --reproject\n"); return 2; }
     if (unbiased_temporal && follow_motion) { fprintf(stderr, "--unbiased-temporal and --follow-motion exclude each other\n"); return 2; }
     if (mv.all && move_lights_given) { fprintf(stderr, "--move-tris and --move-lights exclude each other\n"); return 2; }
+    if (indirect && (ranks > 1 || example != 10)) { fprintf(stderr, "--indirect applies to one GPU and --example 10\n"); return 2; }
     if (grid_cells && (ranks > 1 || example != 10)) { fprintf(stderr, "--light-grid applies to one GPU and --example 10\n"); return 2; }
     if (light_mode != RT_LIGHTS_UNIFORM && example != 10) { fprintf(stderr, "--light-sampling applies to --example 10\n"); return 2; }
     if (orbit && (ranks > 1 || example == 4 || example == 6)) { fprintf(stderr, "--orbit applies to one GPU and --example 10, 7, 8 and 9\n"); return 2; }
@@ -695,6 +705,7 @@ int main(int argc, char** argv)
     if (denoise_antilag) CK(rt_denoise_temporal_antilag(ctx, 1, antilag_given ? &antilag : nullptr));
     CK(rt_light_sampling(ctx, light_mode));
     if (grid_cells) CK(rt_light_grid(ctx, grid_cells, grid_clusters));
+    if (indirect) CK(rt_indirect(ctx, indirect));
     CK(rt_timing_enable(ctx, 1));
     CK(rt_clear(ctx)); /* :222-226 */
 
@@ -738,6 +749,7 @@ int main(int argc, char** argv)
                 CK(rt_spatial_resampling(ctx, frame, k, in, out));
             }
             CK(rt_resolve(ctx, out));
+            if (indirect) CK(rt_indirect_pass(ctx, frame, indirect));
             CK(rt_tone_mapping(ctx));
         }
         if (denoise >= 0)

@@ -54,6 +54,7 @@ INTERNAL_EXPORTS = [
     "rt_temporal_light_motion", "rt_temporal_light_motion_get", "rt_temporal_light_motion_stats", "rt_temporal_light_motion_timing",
     "rt_temporal_light_motion_path",
     "rt_light_grid", "rt_light_grid_get", "rt_light_grid_build_ms", "rt_light_grid_table",
+    "rt_indirect", "rt_indirect_get", "rt_indirect_pass", "rt_indirect_stats", "rt_indirect_timing",
 ]
 EXPORTS = PUBLIC_EXPORTS + INTERNAL_EXPORTS
 
@@ -233,6 +234,12 @@ def load_library(exp=False, path=None):
         L.rt_light_grid_get.argtypes = [vp, vp, vp, vp]
         L.rt_light_grid_build_ms.argtypes = [vp, vp]
         L.rt_light_grid_table.argtypes = [vp] * 12 + [C.c_uint32, C.c_uint32]
+    if hasattr(L, "rt_indirect"):  # r36; likewise
+        L.rt_indirect.argtypes = [vp, ci]
+        L.rt_indirect_get.argtypes = [vp, vp]
+        L.rt_indirect_pass.argtypes = [vp, ci, ci]
+        L.rt_indirect_stats.argtypes = [vp, vp]
+        L.rt_indirect_timing.argtypes = [vp, vp]
     if hasattr(L, "rt_temporal_light_motion"):  # r32; likewise
         L.rt_temporal_light_motion.argtypes = [vp, ci]
         L.rt_temporal_light_motion_get.argtypes = [vp, vp, vp]
@@ -570,8 +577,9 @@ class Renderer:
     def tone_mapping(self):
         self._ck(self.L.rt_tone_mapping(self.h))
 
-    def frame_by_kernels(self, frame, clear_first=False):
-        """The launch sequence of 10_restir_di.cpp:257-379, kernel by kernel."""
+    def frame_by_kernels(self, frame, clear_first=False, indirect=0):
+        """The launch sequence of 10_restir_di.cpp:257-379, kernel by kernel; indirect > 0: rt_indirect_pass with that many bounces
+        between resolve and tone mapping (what rt_frame runs while rt_indirect is on)."""
         if clear_first:
             self.clear()
         self.raycast()
@@ -585,6 +593,8 @@ class Renderer:
                 src, dst = dst, src
             self.spatial_resampling(frame, k, src, dst)
         self.resolve(dst)
+        if indirect:
+            self.indirect_pass(frame, indirect)
         self.tone_mapping()
         return dst
 
@@ -1076,6 +1086,39 @@ class Renderer:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self._ck(self.L.rt_light_grid_get(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def indirect(self, bounces=None):
+        """rt_indirect: path-traced indirect light on top of the ReSTIR frame. bounces 1..32: rt_frame runs the
+        pass between resolve and tone mapping; 0 switches it off; None queries. Returns the setting."""
+        if not hasattr(self.L, "rt_indirect"):  # an older build through RT_LIB_PATH: the call is not there, and that is an error
+            raise RtError("this build of librestir_rt has no rt_indirect")
+        if bounces is not None:
+            self._ck(self.L.rt_indirect(self.h, int(bounces)))
+        v = C.c_int()
+        self._ck(self.L.rt_indirect_get(self.h, C.byref(v)))
+        return v.value
+
+    def indirect_pass(self, frame, bounces):
+        """rt_indirect_pass: the pass alone, between resolve and tone_mapping of a kernel-by-kernel frame"""
+        if not hasattr(self.L, "rt_indirect_pass"):  # as above
+            raise RtError("this build of librestir_rt has no rt_indirect_pass")
+        self._ck(self.L.rt_indirect_pass(self.h, int(frame), int(bounces)))
+
+    def indirect_stats(self):
+        """the last indirect pass: paths started, raytrace()-equivalent rays, paths alive when its last bounce started"""
+        if not hasattr(self.L, "rt_indirect_stats"):  # as above
+            raise RtError("this build of librestir_rt has no rt_indirect_stats")
+        a = np.zeros(3, dtype=np.uint64)
+        self._ck(self.L.rt_indirect_stats(self.h, _p(a)))
+        return dict(paths=int(a[0]), rays=int(a[1]), alive_last=int(a[2]))
+
+    def indirect_timing(self):
+        """device ms of the last indirect pass (rt_timing_enable on)"""
+        if not hasattr(self.L, "rt_indirect_timing"):  # as above
+            raise RtError("this build of librestir_rt has no rt_indirect_timing")
+        ms = C.c_float()
+        self._ck(self.L.rt_indirect_timing(self.h, C.byref(ms)))
+        return ms.value
 
     def light_grid_build_ms(self):
         """wall time of the last build of the light grid's tables (host tables and upload), ms"""

@@ -17,6 +17,7 @@
 #include "temporal_reproject.h"
 #include "temporal_motion.h"
 #include "temporal_unbiased.h"
+#include "indirect.h"
 
 using namespace rt;
 
@@ -2945,20 +2946,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, RT_RESOLVE_STREAM_WAVES) void k_resolv
 #ifndef RT_PT_WS
 #define RT_PT_WS 1
 #endif
-/* common/core.hpp:76-89 with portable cos/sin [parity] */
-RT_DEV f3 sample_hemisphere(float r0, float r1, float r2)
-{
-    const float theta = r0 * 2.0f * kPI;
-    float radius = r1 + r2;
-    if (1.0f < radius) radius = 2.0f - radius;
-    float sn_t, cs_t;
-    pm_sincosf(theta, &sn_t, &cs_t);
-    const float x = cs_t * radius;
-    const float z = sn_t * radius;
-    const float a = 1.0f - radius * radius;
-    const float y = sqrtf((a < 0.0f) ? 0.0f : a);
-    return F3(x, y, z);
-}
+/* sample_hemisphere (common/core.hpp:76-89 with portable cos/sin [parity]): indirect.h, shared with the CPU restatement of rt_indirect */
 
 /* One path of examples/07_pt/07_pt.cu:11-90 (EXAMPLE 7) / examples/09_ris/09_ris.cu:11-166 (EXAMPLE 9). */
 struct PathState
@@ -3163,6 +3151,12 @@ RT_DEV void path_write(const FrameParams& P, float4* __restrict__ accum, size_t 
     }
     else { accum[li] = make_float4(radiance.x, radiance.y, radiance.z, 1.0f); }
 }
+/* path_write's sibling for rt_indirect (below): RGB added, .w left */
+RT_DEV void indirect_write(float4* __restrict__ accum, size_t li, f3 radiance)
+{
+    const float4 a = accum[li];
+    accum[li] = make_float4(a.x + radiance.x, a.y + radiance.y, a.z + radiance.z, a.w);
+}
 RT_DEV void count_rays(unsigned long long nrays, unsigned long long* __restrict__ rays)
 {
     for (int off = 32; off > 0; off >>= 1) nrays += __shfl_down(nrays, off);
@@ -3261,6 +3255,71 @@ __global__ __launch_bounds__(TRACE_BLOCK, EXAMPLE == 7 ? 1 : (EXAMPLE == 8 ? 6 :
         if (alive) path_store(out, (size_t)(base + __popcll(m & ((1ull << lane) - 1ull))), st, pixel);
     }
     count_rays(nrays, &counters[0]);
+}
+
+/* ---------------------------------------- rt_indirect: path-traced indirect light on top of the ReSTIR frame */
+/* A path per shaded pixel, started at the G-buffer's surface (indirect.h, indirect_start) and run through 08_nee's depth loop from
+ * depth 1 (path_bounce<8, false>, unchanged); its radiance is ADDED to the accumulation buffer's RGB, the sample count .w stays.
+ * g0 / g1 are the launch's G-buffer set (host: Launch::g0 / g1), never the context's current pointers: the look-ahead stage 0 of
+ * the next frame may already be writing the other set. Pixels without GB_SHADED (sky, emissive) start no path and keep their bytes.
+ * counters: [0] raytrace()-equivalent rays, [1] paths started, [2 + d] paths alive when bounce d starts (d = 1 .. bounces).
+ * One launch for the whole path. A compacted form (a path record per shaded pixel, then one k_pt_bounce-shaped launch per bounce) was
+ * built and measured slower at 1920 x 1080 on the bench stand-in at every bounce count (1: 1.62 against 1.39 ms, 5: 3.16 against
+ * 2.65 ms; docs/MEASUREMENT_LOG_r36.md) and is not in the sources.
+ * Register budget: 6 wavefronts per SIMD, 08_nee's (k_path_trace<8>), taken over and not timed against the others; what each budget
+ * compiles to (VGPRs, spills) is in the same log. */
+#ifndef RT_INDIRECT_WAVES
+#define RT_INDIRECT_WAVES 6
+#endif
+RT_DEV bool indirect_begin(const SceneView& S, const FrameParams& P, const float4* __restrict__ g0, const float4* __restrict__ g1, int x, int row,
+                           PathState& st)
+{
+    const size_t li = (size_t)x + (size_t)(row - P.lrow0) * P.W;
+    const float4 G1 = g1[li];
+    if (!(as_uint(G1.w) & GB_SHADED)) return false;
+    const float4 G0 = g0[li];
+    const int tri = as_int(G0.w);
+    const float4 kd4 = S.trimat[2 * (size_t)tri];
+    f3 v0, v1, v2;
+    load_tri(S.bvh.tv, tri, v0, v1, v2);
+    const IndirectStart s = indirect_start(x, P.H - 1 - row, P.frame, F3(G0.x, G0.y, G0.z), F3(G1.x, G1.y, G1.z), F3(kd4.x, kd4.y, kd4.z), v0, v1);
+    st.ro = s.ro; st.rd = s.rd; st.throughput = s.throughput; st.rng = s.rng;
+    st.radiance = F3(0.0f, 0.0f, 0.0f);
+    return true;
+}
+/* one atomic per wavefront; works under any exec mask */
+RT_DEV void count_lanes(bool flag, unsigned long long* __restrict__ counter)
+{
+    const unsigned long long m = __ballot(flag), act = __ballot(true);
+    if (m && (int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+/* one launch: one-wavefront workgroups on 8 x 8 tiles in the tracing kernels' tile order, LDS walk stack as k_path_trace<8> */
+__global__ __launch_bounds__(TRACE_BLOCK, RT_INDIRECT_WAVES) void k_indirect(SceneView S, FrameParams P, int bounces, const float4* __restrict__ g0,
+                                                                             const float4* __restrict__ g1, float4* __restrict__ accum,
+                                                                             unsigned long long* __restrict__ counters)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_stack[(RT_PT_WS ? WIDE_LDS_ROWS : WIDE_LDS_STACK) * TRACE_BLOCK];
+    int x, row;
+    const bool ok = tile_pixel<TRACE_BLOCK>(P, x, row);
+    unsigned long long nrays = 0;
+    bool started = false, last = false;
+    if (ok)
+    {
+        PathState st;
+        started = indirect_begin(S, P, g0, g1, x, row, st);
+        if (started)
+        {
+            for (int depth = 1; depth <= bounces; ++depth)
+            {
+                last = depth == bounces;
+                if (!path_bounce<8, false>(S, s_stack, P, depth, F3(0.0f, 0.0f, 0.0f), st, nrays)) break;
+            }
+            indirect_write(accum, (size_t)x + (size_t)(row - P.lrow0) * P.W, st.radiance);
+        }
+    }
+    count_rays(nrays, &counters[0]);
+    count_lanes(started, &counters[1]);
+    count_lanes(last, &counters[2 + bounces]);
 }
 
 /* ---------------------------------------- config #1 on the GPU: 04_ao / 06_ao_hiprt */

@@ -304,6 +304,12 @@ struct rt_ctx
     float4* d_paths[2] = {nullptr, nullptr}; /* wavefront path tracer: live-path lists (64 B per path) */
     unsigned long long* d_pt_counters = nullptr;
     int pt_wavefront = 2; /* rt_tuning key 6: 0 one launch per frame, 1 wavefront, 2 auto (wavefront for 09_ris) */
+    /* rt_indirect (r36, indirect.h): bounces of the pass rt_frame runs between resolve and tone mapping (0 = off);
+     * d_ind_counters: 64 words (frame_kernels.h, k_indirect), ind_bounces: the last pass's; ind_ev: its device time while rt_timing_enable is on */
+    int indirect = 0, ind_bounces = 0;
+    unsigned long long* d_ind_counters = nullptr;
+    hipEvent_t ind_ev[2] = {nullptr, nullptr};
+    bool ind_timed = false;
     int tune_ao_layout = 0; /* rt_tuning key 27: ambient occlusion (rt_path_trace 4 / 6) 0 pixel-major, 1 ray-major (frame_kernels.h k_ao) */
     /* rt_denoise (denoise_kernels.h), allocated at the first call: the guide (rt_visibility records, {x, f}, {n, word}), the colour
      * records {e, var} of the two ping-pong sides, the HDR output; per-kernel events while rt_timing_enable is on */
@@ -674,6 +680,8 @@ int rt_destroy(rt_ctx* c)
     if (c->al_ev) hipEventDestroy(c->al_ev);
     hipFree(c->d_lf_words); hipFree(c->d_lf_stage);
     for (hipEvent_t e : c->lf_ev) if (e) hipEventDestroy(e);
+    hipFree(c->d_ind_counters);
+    for (hipEvent_t e : c->ind_ev) if (e) hipEventDestroy(e);
     hipFree(c->d_counter); hipFree(c->d_stage); hipFree(c->d_paths[0]); hipFree(c->d_paths[1]); hipFree(c->d_pt_counters);
     if (c->ev_created) for (auto& e : c->ev) hipEventDestroy(e);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -2552,7 +2560,7 @@ static bool use_fused_final(const rt_ctx* c)
 #endif
     const int want = c->tune_fuse_final < 0 ? (whole_frame(c) ? RT_FUSE_FINAL_AUTO : 0) : c->tune_fuse_final;
     return want != 0 && !c->opt.use_shadowed_target_function && c->opt.use_spatial_resampling && !c->spatial_unbiased && c->tune_spatial_variant == 2 && !c->tune_stream &&
-           c->opt.spatial_resampling_passes >= 1;
+           c->opt.spatial_resampling_passes >= 1 && c->indirect == 0 /* rt_indirect runs between resolve and tone mapping */;
 }
 /* rt_spatial_unbiased: does the 1/Z pass run for the current options, and can it? (with use_spatial_resampling = 0 the pass copies its
  * input in either mode) */
@@ -2812,6 +2820,76 @@ int rt_path_trace_rays(rt_ctx* c, uint64_t* rays)
     RT_HIP(c, hipMemcpyAsync(&h, c->d_counter, 8, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     *rays = h;
+    return RT_OK;
+}
+
+/* ---- rt_indirect (indirect.h, frame_kernels.h k_indirect*) ---- */
+static const char* const kNoLights = "08_nee / 09_ris need at least one emissive triangle";
+/* the pass over the launch's rows, on its stream, reading ITS G-buffer set */
+static int launch_indirect(rt_ctx* c, const Launch& L, int frame, int bounces)
+{
+    if (c->n_lights == 0) RT_FAIL(c, RT_ERR_STATE, "%s", kNoLights);
+    if (!c->d_ind_counters) RT_HIP(c, hipMalloc(&c->d_ind_counters, 64 * 8));
+    const bool timed = c->timing && L.timed;
+    if (timed && !c->ind_ev[0]) for (auto& e : c->ind_ev) RT_HIP(c, hipEventCreate(&e));
+    const SceneView S = make_scene(c);
+    const FrameParams P = make_params(c, L, frame, 0, K_RAYCAST); /* the tracing kernels' tile order and its tuning key */
+    const int g = trace_grid(c, L);
+    if (timed) RT_HIP(c, hipEventRecord(c->ind_ev[0], L.stream));
+    RT_HIP(c, hipMemsetAsync(c->d_ind_counters, 0, 64 * 8, L.stream));
+    k_indirect<<<g, TRACE_BLOCK, 0, L.stream>>>(S, P, bounces, L.g0, L.g1, c->d_accum, c->d_ind_counters);
+    RT_HIP(c, hipGetLastError());
+    if (timed) RT_HIP(c, hipEventRecord(c->ind_ev[1], L.stream));
+    c->ind_timed = timed;
+    c->ind_bounces = bounces;
+    return RT_OK;
+}
+int rt_indirect(rt_ctx* c, int bounces)
+{
+    RT_CHECK_CTX(c);
+    if (!whole_frame(c))
+        RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_indirect: strip contexts hold no path lists and their frame is the strip driver's (rows [%d,%d) of %d)", c->row_begin, c->row_end, c->H);
+    if (bounces < 0 || bounces > 32) RT_FAIL(c, RT_ERR_ARG, "rt_indirect: bounces %d outside 0..32", bounces);
+    c->indirect = bounces;
+    ++c->epoch;
+    return RT_OK;
+}
+int rt_indirect_get(rt_ctx* c, int* bounces)
+{
+    RT_CHECK_CTX(c);
+    if (!bounces) return RT_ERR_ARG;
+    *bounces = c->indirect;
+    return RT_OK;
+}
+int rt_indirect_pass(rt_ctx* c, int frame, int bounces)
+{
+    RT_CHECK_CTX(c);
+    if (!whole_frame(c)) RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_indirect_pass is for whole-frame contexts (rows [%d,%d) of %d)", c->row_begin, c->row_end, c->H);
+    JOIN_TAIL(c);
+    NEED_SCENE(c);
+    if (bounces < 1 || bounces > 32) RT_FAIL(c, RT_ERR_ARG, "rt_indirect_pass: bounces %d outside 1..32", bounces);
+    if (!c->gbuf.valid || c->gbuf.traced_epoch != c->epoch)
+        RT_FAIL(c, RT_ERR_STATE, "rt_indirect_pass: no traced G-buffer of the current camera and scene (rt_raycast or rt_frame first)");
+    return launch_indirect(c, whole_launch(c), frame, bounces);
+}
+int rt_indirect_stats(rt_ctx* c, uint64_t out[3])
+{
+    RT_CHECK_CTX(c);
+    if (!out) return RT_ERR_ARG;
+    if (!c->d_ind_counters || c->ind_bounces < 1) RT_FAIL(c, RT_ERR_STATE, "rt_indirect_stats: no indirect pass has run");
+    { const int rs = rt_sync(c); if (rs != RT_OK) return rs; }
+    unsigned long long h[64];
+    RT_HIP(c, hipMemcpy(h, c->d_ind_counters, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[1]; out[1] = h[0]; out[2] = h[2 + c->ind_bounces];
+    return RT_OK;
+}
+int rt_indirect_timing(rt_ctx* c, float* ms)
+{
+    RT_CHECK_CTX(c);
+    if (!ms) return RT_ERR_ARG;
+    if (!c->ind_timed) RT_FAIL(c, RT_ERR_STATE, "no timed indirect pass (rt_timing_enable, then rt_indirect_pass or rt_frame with rt_indirect on)");
+    RT_HIP(c, hipEventSynchronize(c->ind_ev[1]));
+    RT_HIP(c, hipEventElapsedTime(ms, c->ind_ev[0], c->ind_ev[1]));
     return RT_OK;
 }
 
@@ -3137,6 +3215,7 @@ int rt_frame_stage_begin(rt_ctx* c, int frame, int stage, int clear_first)
     RT_CHECK_CTX(c);
     NEED_SCENE(c);
     if (stage == 0 && c->opt.spatial_resampling_passes > 0) { const int rc = unbiased_check(c); if (rc != RT_OK) return rc; } /* before the frame starts */
+    if (stage == 0 && c->indirect > 0 && c->n_lights == 0) RT_FAIL(c, RT_ERR_STATE, "%s", kNoLights); /* rt_indirect: likewise */
     c->last_frame = frame;
     /* a spatial stage reads the shaded-bit rows from both lanes: (re)built here, on the main stream, if the halo flags
      * arrived after the raycast (cold frame of a strip) */
@@ -3245,6 +3324,9 @@ static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part,
     else
     {
         for (int k = passes; k < 3; ++k) mark(4 + k);
+        /* rt_indirect: the resolve stage runs the pass, once, over all owned rows (the pass's counters are the context's, not a lane's) */
+        if (c->indirect > 0 && !whole)
+            RT_FAIL(c, RT_ERR_UNSUPPORTED, "rt_indirect: the resolve stage must run over all owned rows in one range while the toggle is on");
         /* passes == 0: the reference resolves reservoir_buffer1, which no kernel of that frame wrote
          * (10_restir_di.cpp:324-368): zeros after start-up, else what an earlier frame's last odd pass
          * left there. Logical RT_RES_1 (physical Z) holds exactly that content here, frame by frame
@@ -3272,9 +3354,12 @@ static int stage_run_ranges(rt_ctx* c, Launch L, int frame, int stage, int part,
         else rc = join_tail(c, L);
         /* tone_mapping reads the pixel's own accumulation value only (common/kernels/common.cu:30-74): k_resolve maps what it
          * has just written (r05; not the persistent-wavefront A/B form, which has no such parameter) */
-        const bool fuse_tm = c->tune_fuse_tonemap != 0 && !c->tune_stream;
+        const bool fuse_tm = c->tune_fuse_tonemap != 0 && !c->tune_stream && c->indirect == 0;
         if (rc == RT_OK) rc = launch_resolve(c, R, final_phys, fuse_tm ? (uint32_t*)c->d_pixels : nullptr);
         mark(7);
+        /* rt_indirect: the pass on the resolve's stream, over R's G-buffer set (the look-ahead stage 0 of the next frame may be writing
+         * the other one); tone mapping then maps the sum in a launch of its own. Inside rt_timing's ms[7] */
+        if (rc == RT_OK && c->indirect > 0) rc = launch_indirect(c, R, frame, c->indirect);
         if (rc == RT_OK && !fuse_tm) rc = launch_tone_mapping(c, R);
         mark(8);
         if (tail && rc == RT_OK)

@@ -481,6 +481,32 @@ int rt_light_grid_build_ms(rt_ctx* ctx, float* ms);
 int rt_light_grid_table(rt_ctx* ctx, float bounds[9], uint32_t* cluster_of, uint32_t* perm, uint32_t* run_start, uint32_t* run_thr,
                         uint32_t* run_alias, uint64_t* run_K, uint32_t* cell_thr, uint32_t* cell_alias, uint64_t* cell_K, float* cell_prob,
                         uint32_t n_lights, uint32_t n_cell_slots);
+/* (r36) Path-traced indirect light on top of the ReSTIR frame (csrc/indirect.h), default off: with bounces = 0
+ * rt_frame issues the launches it issued without the call and nothing else. The frame's resolve writes the direct term of the primary
+ * hit; with bounces = 1 .. 32 rt_frame (and the resolve stage of rt_frame_stage*, which must then run over all owned rows in one range:
+ * RT_ERR_UNSUPPORTED otherwise) runs one more pass after resolve and before tone mapping, on the resolve's stream: every pixel whose
+ * G-buffer entry is shaded starts a path at that surface with the random stream examples/08_nee gives the pixel for this frame number
+ * (after the three draws of 08_nee's depth-0 light sample), and the path runs 08_nee's depth loop from depth 1 for `bounces`
+ * iterations: closest hit, one uniformly picked light sample with one shadow ray, next direction; it ends on the sky or on an emissive
+ * triangle without a contribution. Its radiance is added to RT_BUF_ACCUMULATION's RGB, the sample count .w stays; sky and emissive
+ * pixels keep their bytes. Direct + indirect is what 08_nee estimates at max_depth = bounces + 1, term for term. The resolve kernel
+ * then does not tone-map its own pixel (rt_tuning key 20 has no effect): tone mapping is a launch of its own behind the pass, and both
+ * lie in rt_timing's ms[7], whose nine slots stay as they are. Light selection inside the bounces is uniform whatever
+ * rt_light_sampling and rt_light_grid say. rt_ray_count keeps counting the reference's ReSTIR rays only. Other values of bounces:
+ * RT_ERR_ARG; strip contexts: RT_ERR_UNSUPPORTED; a frame on a scene without lights while it is on: RT_ERR_STATE. The call changes
+ * rt_state_epoch and touches no buffer. Not an rt_tuning key: tuning keys never change results. */
+int rt_indirect(rt_ctx* ctx, int bounces);
+int rt_indirect_get(rt_ctx* ctx, int* bounces);
+/* the pass alone on the context's stream, for the kernel-by-kernel sequence between rt_resolve and rt_tone_mapping; bounces 1 .. 32.
+ * RT_ERR_STATE without a traced G-buffer of the current camera and scene (rt_raycast, or a frame, since the last change of either)
+ * and on a scene without lights; RT_ERR_UNSUPPORTED on strip contexts. rt_indirect itself changes rt_state_epoch, so it counts as such
+ * a change: the pass takes its bounces as an argument and needs no toggle, and a caller who sets the toggle does so before rt_raycast. */
+int rt_indirect_pass(rt_ctx* ctx, int frame, int bounces);
+/* the last pass: out[0] = paths started (= shaded pixels), out[1] = raytrace()-equivalent rays (closest-hit + shadow), out[2] = paths
+ * alive when its last bounce started. RT_ERR_STATE before the first pass. Synchronises. */
+int rt_indirect_stats(rt_ctx* ctx, uint64_t out[3]);
+/* device ms of the last pass if rt_timing_enable was on during it, else RT_ERR_STATE */
+int rt_indirect_timing(rt_ctx* ctx, float* ms);
 /* launches so far that traced primary rays over the context's rows: rt_raycast, stage-0 raycasts, the one-launch stage 0 and
  * look-ahead raycasts (counted when launched, taken or not). How the tests see reuse without timing anything. */
 int rt_primary_launches(rt_ctx* ctx, uint64_t* n);

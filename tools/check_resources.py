@@ -67,6 +67,8 @@ BUDGET = [
     (r"^k_denoise_temporal_motion", 0, 8),  # r25 rt_denoise_temporal_motion: the followed call's form, 41 VGPRs / 46 SGPRs (its sibling: 41 / 44)
     # r32 rt_temporal_light_motion: the re-basing pass of rt_scene_update
     (r"^k_light_follow<true>", 0, 8),    # loop over the span's lights: 49 VGPRs
+    # r36 rt_indirect: 08_nee's depth loop from the G-buffer, at 08_nee's budget (k_path_trace<8>: 80 VGPRs, 15 spilled)
+    (r"^k_indirect$", 14, 6),            # one launch: 80 VGPRs, 14 spilled (budget 5: 96, none; 7: 72, 23; 8: 64, 36)
     (r"^k_light_follow<false>", 0, 7),   # point query on the old tree: 66 VGPRs, 14 336 B of LDS (the stack), 208 B of scratch (its overflow, as trace_wide)
 ]
 
